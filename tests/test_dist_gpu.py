@@ -98,10 +98,11 @@ def test_two_ranks_weld_one_cloud(tmp_path):
 
 def test_bench_two_ranks_one_sharded_cloud():
     """bench.py as the driver starts it for N = 2 (here both ranks on GPU 0, gloo): the cfg4 slab family at 2 %% of the
-    splat count; the line reports two ranks with 25 buckets each of ONE cloud, and refuses a mismatching --gpus."""
+    splat count; with --full the line reports two ranks with 25 buckets each of ONE cloud and the legs, a plain run the
+    headline of both ranks, and a mismatching --gpus is refused."""
     env = {"MLSGPU_BENCH_BACKEND": "gloo"}
     out = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1",
-                      "--no-timing"], env)
+                      "--full", "--no-timing"], env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
@@ -127,14 +128,14 @@ def test_bench_two_ranks_one_sharded_cloud():
 
 
 def test_driver_shaped_call_finishes_in_time():
-    """`bench.py --gpus 2 --steps 20 --warmup 5` exactly as the driver launches it, at FULL size (two slabs of cfg4: 200 M-splat
-    cloud per rank, 25 buckets each), both ranks on this box's one GPU: the line arrives within 300 s whatever the secondary
+    """`bench.py --gpus 2 --steps 20 --warmup 5 --full` (the driver's call, with the secondary legs), at FULL size (two
+    slabs of cfg4: 200 M-splat cloud per rank, 25 buckets each), both ranks on this box's one GPU: the line arrives within 300 s whatever the secondary
     legs do -- they share a wall-clock budget (--leg-budget-s, 150 s by default at N > 1) and a leg that does not fit is
     skipped and named in leg_errors -- and the headline with the in-run per-GPU reference is on stderr before any leg starts."""
     import time
     env = {"MLSGPU_BENCH_BACKEND": "gloo"}
     t0 = time.time()
-    out = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"], env)
+    out = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full"], env)
     elapsed = time.time() - t0
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert elapsed < 300, elapsed
@@ -150,7 +151,7 @@ def test_driver_shaped_call_finishes_in_time():
         assert leg in d or any(k.startswith(leg) for k in d.get("leg_errors", {})), leg
     # and --legs none is the headline alone
     out = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scale", "0.02", "--steps", "2", "--warmup", "1",
-                      "--legs", "none"], env)
+                      "--full", "--legs", "none"], env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert "transfer_inclusive" not in d and "single_process" not in d and d["per_gpu_reference"]["value"] > 0
@@ -162,7 +163,7 @@ def test_bench_rccl_code_path_with_one_rank():
     GPU -- the shared-GPU runs above use gloo, and a one-GPU box cannot hold two RCCL ranks."""
     env = {"MLSGPU_BENCH_FORCE_DIST": "1", "MLSGPU_BENCH_BACKEND": "nccl"}
     out = _launch(1, [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "cfg4slab", "--scale", "0.02", "--steps", "2",
-                      "--warmup", "1", "--no-timing"], env)
+                      "--warmup", "1", "--full", "--no-timing"], env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and "debug_forced_dist" in d and d["per_rank"]["buckets"] == [25]

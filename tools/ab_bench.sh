@@ -4,7 +4,7 @@
 # AB_TESTS="tests/test_gpu_marching.py ..." runs those GPU tests first (with the library that is in place).
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
-args="$1"; shift
+args="--full $1"; shift
 cp mlsgpu_amd/libmlsgpu_hip.so /tmp/orig.so
 if [ -n "$AB_TESTS" ]; then python -m pytest $AB_TESTS -m gpu -x -q 2>&1 | tail -2; fi
 for rep in 1 2 3; do

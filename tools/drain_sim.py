@@ -2,7 +2,7 @@
 """What-ifs for the drain of processCorners (variant 5) on the candidate masks of real tiles.
 
 A library built with -DMLSGPU_MLS5_DUMP=<words> leaves, for a sample of blocks, every tile's 64 candidate masks behind the
-work counters (bench.py: MLSGPU_BENCH_MLS_STATS_WORDS / MLSGPU_BENCH_MLS_STATS_FILE).  This script replays them, wave by
+work counters (bench.py --full: MLSGPU_BENCH_MLS_STATS_WORDS / MLSGPU_BENCH_MLS_STATS_FILE).  This script replays them, wave by
 wave and round by round, under several ways of walking the masks and prints the iterations a wave spends (one iteration =
 one candidate for every lane that still has one: the ~29 vector instructions of the drain's body).
 

@@ -3,7 +3,7 @@
 #   make -C mlsgpu_amd/csrc HIPFLAGS_EXTRA=-DMLSGPU_MLS5_CLOCK   (or compile mls.o by hand) and copy it to ab/clock.so, then
 #   gpurun -- 'bash tools/mls_clock.sh [uniform|shells]'
 # The plain kernel reads s_memtime at its barriers and leaves per-phase sums over all waves in the work-counter words 0-7
-# (bench.py prints them with MLSGPU_BENCH_DUMP_MLS_COUNTERS=1): head, staging, barrier 1, compaction, tiles + drains, barrier 2,
+# (bench.py --full prints them with MLSGPU_BENCH_DUMP_MLS_COUNTERS=1): head, staging, barrier 1, compaction, tiles + drains, barrier 2,
 # whole wave, number of waves.
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
@@ -11,7 +11,7 @@ mkdir -p gpurun_out
 cp mlsgpu_amd/libmlsgpu_hip.so /tmp/orig.so
 cp ab/${CLOCK_SO:-clock}.so mlsgpu_amd/libmlsgpu_hip.so
 for cloud in "${@:-uniform}"; do
-  MLSGPU_BENCH_DUMP_MLS_COUNTERS=1 timeout 300 python3 bench.py --headline-only --no-timing --no-cross-check --workers 1 --batch 4 --steps 1 --warmup 0 --dist $cloud 2> /tmp/clock_$cloud.err > /tmp/clock_$cloud.out
+  MLSGPU_BENCH_DUMP_MLS_COUNTERS=1 timeout 300 python3 bench.py --full --headline-only --no-timing --no-cross-check --workers 1 --batch 4 --steps 1 --warmup 0 --dist $cloud 2> /tmp/clock_$cloud.err > /tmp/clock_$cloud.out
   grep "mls counters" /tmp/clock_$cloud.err | python3 -c "
 import sys
 w = [int(x) for x in sys.stdin.read().split()[2:10]]

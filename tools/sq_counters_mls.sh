@@ -6,7 +6,7 @@ v=$1; label=$2; out=$3; shift 3
 case $v in 5) k="processCornersMatrixKernel<0, false>";; 4) k="processCornersCubeKernel<0, false>";; *) k="processCornersKernel<0, false>";; esac
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
-args="bench.py --headline-only --no-timing --no-cross-check --workers 1 --batch 4 --steps 1 --warmup 0 --variant $v $*"
+args="bench.py --full --headline-only --no-timing --no-cross-check --workers 1 --batch 4 --steps 1 --warmup 0 --variant $v $*"
 rm -rf /tmp/sqm_a /tmp/sqm_b /tmp/sqm_c /tmp/sqm_d
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY -d /tmp/sqm_a -o run -- python3 $args > /dev/null 2>&1
 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM SQ_WAVES -d /tmp/sqm_b -o run -- python3 $args > /dev/null 2>&1
