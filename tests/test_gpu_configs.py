@@ -197,6 +197,39 @@ def test_cfg2_full_size(ctx, dist):
         del batches, w
 
 
+def test_cfg2_full_size_plane_fit(ctx):
+    """test_cfg2_full_size's whole-bucket oracle parity with the plane fit (shape 1) and boundary limit 1.5, on the uniform
+    cloud: the plane kernels had met the oracle only on the small fixtures and cfg1 before."""
+    import torch
+    import mlsgpu_amd as m
+    from mlsgpu_amd import synth
+    dev = torch.device("cuda", 0)
+    cloud, g = synth.make_cloud_device("cfg2", dev, dist="uniform")
+    assert len(cloud) == 5_000_000 and g == 256
+    record_size("cfg2 uniform, plane fit, boundary limit 1.5",
+                "%d splats, one bucket of 255^3 cells, whole bucket against the oracle" % len(cloud))
+    bucketed, buckets = synth.bucketize_device(cloud, synth.grid_buckets((g, g, g), 255))
+    del cloud
+    assert len(buckets) == 1
+    b = buckets[0]
+    nbytes = bucketed.numel() * 4
+    pristine = m.DeviceBuffer(ctx, nbytes=nbytes, borrow=bucketed.data_ptr())
+    work = m.DeviceBuffer(ctx, nbytes=nbytes)
+    mm = 1 << 30
+    host = bucketed[b.first:b.first + b.count].cpu().numpy().view(m.SPLAT_DTYPE).reshape(-1)
+    exp_b, st = ob.bucket(host, 0, b.count, b.num_vertices, b.low, boundary_limit=1.5, shape=1, max_cells=255,
+                          max_swathe=256, mesh_memory=mm)
+    assert st["welded"] > 0
+    for variant in (5, 4):
+        w = m.Worker(ctx, b.count, max_cells=255, mesh_memory=mm, boundary_limit=1.5, shape=m.binding.SHAPE_PLANE)
+        w.set_mls_variant(variant)
+        work.copy_from(pristine)
+        batches = w.process(work, b.first, b.count, b.low, b.num_vertices)
+        assert st["shipouts"] == len(batches) >= 1
+        assert_batches_equal(batches, exp_b)
+        del batches, w
+
+
 @pytest.mark.parametrize("dist", ["uniform", "shells"])
 def test_cfg4_bucket_pins(ctx, dist):
     """BASELINE configs[3] WHOLE (1024^3 grid, 200 M splats, 125 buckets of <= 255 cells per side), bucket by bucket on one
