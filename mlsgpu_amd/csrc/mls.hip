@@ -129,6 +129,54 @@ __device__ __forceinline__ void fitAdd(Fit &f, float w, float px, float py, floa
     f.hits++;
 }
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+/* a splat seen from a corner (kernels/mls.cl:362-370): p - c with x and y as a pair, |p - c|^2 and d = |p - c|^2 / r^2 */
+struct SplatOffset
+{
+    f32x2 pxy;
+    float pz, pp, d;
+};
+
+__device__ __forceinline__ SplatOffset splatOffset(const float4 pr, const f32x2 cxy, const float cz)
+{
+    SplatOffset o;
+    o.pxy = f32x2{pr.x, pr.y} - cxy;
+    o.pz = pr.z - cz;
+    o.pp = fmaf(o.pxy.x, o.pxy.x, fmaf(o.pxy.y, o.pxy.y, o.pz * o.pz));
+    o.d = o.pp * pr.w;
+    return o;
+}
+
+/* fitAdd of a hit (kernels/mls.cl:374-390) for the drains of variants 4 and 5, without the hit count: sumWpx/y and sumWnx/y
+ * are the pairs sWpxy / sWnxy, one packed fma each (fitUnpack moves them into the Fit) */
+__device__ __forceinline__ void fitAddPacked(Fit &fit, f32x2 &sWpxy, f32x2 &sWnxy, const SplatOffset &o, const float4 nq)
+{
+    float w = 1.0f - o.d;
+    w *= w;
+    w *= w;
+    w *= nq.w;
+    const f32x2 ww = {w, w};
+    const f32x2 nxy = {nq.x, nq.y};
+    const f32x2 wnxy = ww * nxy;
+    const float wnz = w * nq.z;
+    fit.sumW = fit.sumW + w;
+    sWpxy = __builtin_elementwise_fma(ww, o.pxy, sWpxy);
+    fit.sumWpz = fmaf(w, o.pz, fit.sumWpz);
+    sWnxy = __builtin_elementwise_fma(ww, nxy, sWnxy);
+    fit.sumWnz = fmaf(w, nq.z, fit.sumWnz);
+    fit.sumWpp = fmaf(w, o.pp, fit.sumWpp);
+    fit.sumWpn = fit.sumWpn + fmaf(wnxy.x, o.pxy.x, fmaf(wnxy.y, o.pxy.y, wnz * o.pz));
+}
+
+__device__ __forceinline__ void fitUnpack(Fit &fit, const f32x2 sWpxy, const f32x2 sWnxy)
+{
+    fit.sumWpx = sWpxy.x;
+    fit.sumWpy = sWpxy.y;
+    fit.sumWnx = sWnxy.x;
+    fit.sumWny = sWnxy.y;
+}
+
 /* kernels/mls.cl:237-248 */
 __device__ __forceinline__ float solveQuadratic(float a, float b, float c)
 {
@@ -137,6 +185,31 @@ __device__ __forceinline__ float solveQuadratic(float a, float b, float c)
     if (!isfinite(x))
         x = bdet / (-2.0f * a);
     return isfinite(x) ? x : __int_as_float(0x7FC00000);
+}
+
+/* fitSphere, kernels/mls.cl:210-229: the algebraic sphere c + b.x + a |x|^2 (and the denominator of q, which the
+ * acceptance test reuses) */
+struct Sphere
+{
+    float a, bx, by, bz, c, qDen;
+};
+
+__device__ __forceinline__ Sphere fitSphere(const Fit &fit)
+{
+    Sphere s;
+    const float invSumW = 1.0f / fit.sumW;
+    const float mx = fit.sumWpx * invSumW, my = fit.sumWpy * invSumW, mz = fit.sumWpz * invSumW;
+    const float qNum = fit.sumWpn - dot3(mx, my, mz, fit.sumWnx, fit.sumWny, fit.sumWnz);
+    s.qDen = fit.sumWpp - dot3(mx, my, mz, fit.sumWpx, fit.sumWpy, fit.sumWpz);
+    float q = qNum / s.qDen;
+    if (fabsf(s.qDen) < (4 * 1.1920928955078125e-07f) * (float) fit.hits * fabsf(fit.sumWpp) || !isfinite(q))
+        q = 0.0f;
+    s.a = 0.5f * q;
+    s.bx = (fit.sumWnx - q * fit.sumWpx) * invSumW;
+    s.by = (fit.sumWny - q * fit.sumWpy) * invSumW;
+    s.bz = (fit.sumWnz - q * fit.sumWpz) * invSumW;
+    s.c = (-s.a * fit.sumWpp - dot3(s.bx, s.by, s.bz, fit.sumWpx, fit.sumWpy, fit.sumWpz)) * invSumW;
+    return s;
 }
 
 /* fitSphere + projectOriginSphere + acceptance tests, kernels/mls.cl:210-229,263-267,394-408;
@@ -149,27 +222,16 @@ __device__ __forceinline__ float finishCorner(const Fit &fit, float boundaryFact
     {
         if (SHAPE == MLSGPU_SHAPE_SPHERE)
         {
-            const float invSumW = 1.0f / fit.sumW;
-            const float mx = fit.sumWpx * invSumW, my = fit.sumWpy * invSumW, mz = fit.sumWpz * invSumW;
-            const float qNum = fit.sumWpn - dot3(mx, my, mz, fit.sumWnx, fit.sumWny, fit.sumWnz);
-            const float qDen = fit.sumWpp - dot3(mx, my, mz, fit.sumWpx, fit.sumWpy, fit.sumWpz);
-            float q = qNum / qDen;
-            if (fabsf(qDen) < (4 * 1.1920928955078125e-07f) * (float) fit.hits * fabsf(fit.sumWpp) || !isfinite(q))
-                q = 0.0f;
-            const float a = 0.5f * q;
-            const float bx = (fit.sumWnx - q * fit.sumWpx) * invSumW;
-            const float by = (fit.sumWny - q * fit.sumWpy) * invSumW;
-            const float bz = (fit.sumWnz - q * fit.sumWpz) * invSumW;
-            const float c = (-a * fit.sumWpp - dot3(bx, by, bz, fit.sumWpx, fit.sumWpy, fit.sumWpz)) * invSumW;
-            const float b2 = dot3(bx, by, bz, bx, by, bz);
-            const float l = solveQuadratic(a * b2, b2, c);
-            const float ax = l * bx, ay = l * by, az = l * bz;
+            const Sphere s = fitSphere(fit);
+            const float b2 = dot3(s.bx, s.by, s.bz, s.bx, s.by, s.bz);
+            const float l = solveQuadratic(s.a * b2, b2, s.c);
+            const float ax = l * s.bx, ay = l * s.by, az = l * s.bz;
             const float aa = dot3(ax, ay, az, ax, ay, az);
             if (aa < 3.0f)
             {
                 const float rhs = (fit.sumWpp - 2 * dot3(fit.sumWpx, fit.sumWpy, fit.sumWpz, ax, ay, az) + fit.sumW * aa);
-                if (qDen > boundaryFactor * rhs)
-                    f = -dot3(bx, by, bz, ax, ay, az) * (1.0f / sqrtf(b2));   /* half_rsqrt -> exact, DESIGN.md */
+                if (s.qDen > boundaryFactor * rhs)
+                    f = -dot3(s.bx, s.by, s.bz, ax, ay, az) * (1.0f / sqrtf(b2));   /* half_rsqrt -> exact, DESIGN.md */
             }
         }
         else
@@ -264,6 +326,69 @@ __device__ __forceinline__ uint32_t xcdRemap(uint32_t id, uint32_t n, uint32_t c
     return g * super + (j % 8) * chunk + j / 8;
 }
 
+/* the splat id at list position pos + slot of the current run, -1 beyond its end */
+__device__ __forceinline__ int32_t listedId(const MlsArgs &A, int32_t pos, int32_t end, uint32_t slot)
+{
+    const int32_t lpos = pos + (int32_t) slot;
+    return lpos < end ? A.commands[lpos] : -1;
+}
+
+/* the list walk past a round of `stage` staged positions: returns how many of them were listed, and leaves pos / end at the
+ * next round, following the jump at the end of a run (kernels/mls.cl:354-358): negative terminates */
+struct ListRound
+{
+    int32_t staged, pos, end;
+};
+
+__device__ __forceinline__ ListRound listStep(const MlsArgs &A, int32_t pos, int32_t end, int32_t stage)
+{
+    const int32_t staged = min(end - pos, stage);
+    pos += stage;
+    if (pos >= end)
+    {
+        pos = A.commands[end];
+        if (pos >= 0)
+        {
+            const int32_t *const head = A.commands + pos;
+            pos = pos + 1;
+            end = *head;
+        }
+        else
+            end = INT32_MIN;
+    }
+    return ListRound{staged, pos, end};
+}
+
+/* The work counters (mlsgpu_hip_mls_set_stats) that every kernel adds: 0 listed splats, 1 distance tests, 2 hits.  With
+ * DRAINS (variants 4 and 5) also 3 drain calls, 4 the sum of their waves' largest hit (candidate) counts, 6 the same per
+ * round, 7 per block, and 8 + n lanes with n hits in a drain call (sHist, counted in LDS: flushed after a barrier). */
+template<bool DRAINS>
+__device__ __forceinline__ void addStats(const MlsArgs &A, uint32_t hits, unsigned long long nListed, unsigned long long nTests,
+                                         uint32_t drainCalls, uint32_t sumMost, uint32_t sumMostRound, const uint32_t *sHist)
+{
+    const unsigned long long hitSum = waveSum(hits);
+    const uint32_t mostBlock = DRAINS ? waveMax(hits) : 0u;
+    if ((threadIdx.x & 63) == 0)
+    {
+        atomicAdd(&A.stats[0], nListed);
+        atomicAdd(&A.stats[1], nTests);
+        atomicAdd(&A.stats[2], hitSum);
+        if (DRAINS)
+        {
+            atomicAdd(&A.stats[3], (unsigned long long) drainCalls);
+            atomicAdd(&A.stats[4], (unsigned long long) sumMost);
+            atomicAdd(&A.stats[6], (unsigned long long) sumMostRound);
+            atomicAdd(&A.stats[7], (unsigned long long) mostBlock);
+        }
+    }
+    if (DRAINS)
+    {
+        __syncthreads();
+        if (threadIdx.x < 33 && sHist[threadIdx.x] != 0)
+            atomicAdd(&A.stats[8 + threadIdx.x], (unsigned long long) sHist[threadIdx.x]);
+    }
+}
+
 /* Variant 1: the reference's loop (kernels/mls.cl:342-390) -- every corner tests every listed splat, 512 staged per round */
 template<int SHAPE, bool STATS>
 __global__ __launch_bounds__(512) void processCornersKernel(Lanes<MlsArgs> lanes)
@@ -300,8 +425,7 @@ __global__ __launch_bounds__(512) void processCornersKernel(Lanes<MlsArgs> lanes
         while (pos < end)
         {
             /* stage up to STAGE listed splats (kernels/mls.cl:342-352 stages 256) */
-            const int32_t lpos = pos + (int32_t) tid;
-            const int32_t mine = lpos < end ? A.commands[lpos] : -1;
+            const int32_t mine = listedId(A, pos, end, tid);
             if (mine >= 0)
             {
                 sPosRad[tid] = stagedPosRad(A, mine);
@@ -309,15 +433,10 @@ __global__ __launch_bounds__(512) void processCornersKernel(Lanes<MlsArgs> lanes
             }
             if (STATS)
                 nListed += __popcll(__ballot(mine >= 0));
-            const int32_t staged = min(end - pos, (int32_t) STAGE);
-
-            pos += STAGE;
-            if (pos >= end)
-            {
-                /* follow the jump (kernels/mls.cl:354-358): negative terminates */
-                pos = A.commands[end];
-                end = (pos >= 0) ? A.commands[pos++] : INT32_MIN;
-            }
+            const ListRound r = listStep(A, pos, end, STAGE);
+            pos = r.pos;
+            end = r.end;
+            const int32_t staged = r.staged;
             __syncthreads();
 
             for (int32_t i = 0; i < staged; i++)
@@ -342,22 +461,11 @@ __global__ __launch_bounds__(512) void processCornersKernel(Lanes<MlsArgs> lanes
         }
         f = finishCorner<SHAPE>(fit, A.boundaryFactor);
         if (STATS)
-        {
-            const unsigned long long hits = waveSum(fit.hits);
-            if (lane == 0)
-            {
-                atomicAdd(&A.stats[0], nListed);
-                atomicAdd(&A.stats[1], nTests);
-                atomicAdd(&A.stats[2], hits);
-            }
-        }
+            addStats<false>(A, fit.hits, nListed, nTests, 0, 0, 0, nullptr);
     }
-
     const int64_t row = (int64_t) (wy + ly) + (int64_t) (wz + lz) * A.zStride + A.zBias;
     A.field[row * (int64_t) A.pitch + (wx + lx)] = f;
 }
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 /*
  * Variant 4 ("cube streams").  What is left of variant 3's time is vector work, and more than half of its vector
@@ -455,32 +563,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
              * maximum is computed for a counted loop: 577 -> 572.5 us per launch) */
             while (cur != 0)
             {
-                {
-                    const uint32_t t = (uint32_t) __builtin_clz(cur);
-                    cur ^= 0x80000000u >> t;
-                    const uint32_t off = chunk[t];
-                    const float4 pr = *(const float4 *) ((const char *) sPosRad + off);
-                    const float4 nq = *(const float4 *) ((const char *) sNormQ + off);
-                    const f32x2 pxy = f32x2{pr.x, pr.y} - cxy;
-                    const float pz = pr.z - cz;
-                    const float pp = fmaf(pxy.x, pxy.x, fmaf(pxy.y, pxy.y, pz * pz));
-                    const float d = pp * pr.w;
-                    float w = 1.0f - d;
-                    w *= w;
-                    w *= w;
-                    w *= nq.w;
-                    const f32x2 ww = {w, w};
-                    const f32x2 nxy = {nq.x, nq.y};
-                    const f32x2 wnxy = ww * nxy;
-                    const float wnz = w * nq.z;
-                    fit.sumW = fit.sumW + w;
-                    sWpxy = __builtin_elementwise_fma(ww, pxy, sWpxy);
-                    fit.sumWpz = fmaf(w, pz, fit.sumWpz);
-                    sWnxy = __builtin_elementwise_fma(ww, nxy, sWnxy);
-                    fit.sumWnz = fmaf(w, nq.z, fit.sumWnz);
-                    fit.sumWpp = fmaf(w, pp, fit.sumWpp);
-                    fit.sumWpn = fit.sumWpn + fmaf(wnxy.x, pxy.x, fmaf(wnxy.y, pxy.y, wnz * pz));
-                }
+                const uint32_t t = (uint32_t) __builtin_clz(cur);
+                cur ^= 0x80000000u >> t;
+                const uint32_t off = chunk[t];
+                const float4 pr = *(const float4 *) ((const char *) sPosRad + off);
+                const float4 nq = *(const float4 *) ((const char *) sNormQ + off);
+                const SplatOffset o = splatOffset(pr, cxy, cz);
+                fitAddPacked(fit, sWpxy, sWnxy, o, nq);
             }
         };
 
@@ -542,12 +631,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 #pragma unroll 4
                 for (uint32_t k = 0; k < K; k++)
                 {
-                    const uint32_t o = chunk[k];
-                    const float4 a = *(const float4 *) ((const char *) sPosRad + o);
-                    const f32x2 pxy = f32x2{a.x, a.y} - cxy;
-                    const float pz = a.z - cz;
-                    const float pp = fmaf(pxy.x, pxy.x, fmaf(pxy.y, pxy.y, pz * pz));
-                    const float d = pp * a.w;
+                    const float4 pr = *(const float4 *) ((const char *) sPosRad + chunk[k]);
+                    const float d = splatOffset(pr, cxy, cz).d;
                     acc = __builtin_amdgcn_alignbit(acc, __float_as_uint(d - RADIUS_CUTOFF), 31);     /* acc = 2 acc + hitBit(d) */
                 }
                 if (STATS)
@@ -562,7 +647,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 
         int32_t end = A.commands[pos++];
         /* a round's splat ids are requested while the round before it is processed */
-        int32_t idAhead = pos + (int32_t) tid < end ? A.commands[pos + (int32_t) tid] : -1;
+        int32_t idAhead = listedId(A, pos, end, tid);
         while (pos < end)
         {
 #pragma unroll
@@ -607,6 +692,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 if (STATS)
                     nListed += __popcll(__ballot(mine >= 0));
             }
+            /* (listStep here flips one branch of the compiled kernel: the step stays written out) */
             const int32_t staged = min(end - pos, (int32_t) CUBE_STAGE);
             pos += CUBE_STAGE;
             if (pos >= end)
@@ -614,7 +700,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 pos = A.commands[end];
                 end = (pos >= 0) ? A.commands[pos++] : INT32_MIN;
             }
-            idAhead = pos + (int32_t) tid < end ? A.commands[pos + (int32_t) tid] : -1;
+            idAhead = listedId(A, pos, end, tid);
             __syncthreads();
 
             for (int32_t g = 0; g < staged; g += 64)
@@ -653,32 +739,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             }
             __syncthreads();
         }
-        fit.sumWpx = sWpxy.x;
-        fit.sumWpy = sWpxy.y;
-        fit.sumWnx = sWnxy.x;
-        fit.sumWny = sWnxy.y;
+        fitUnpack(fit, sWpxy, sWnxy);
         f = finishCorner<SHAPE>(fit, A.boundaryFactor);
         if (STATS)
         {
-            const unsigned long long hits = waveSum(fit.hits);
-            const uint32_t mostBlock = waveMax(fit.hits);
             if (lane == 0)
-            {
-                atomicAdd(&A.stats[0], nListed);
-                atomicAdd(&A.stats[1], nTests);
-                atomicAdd(&A.stats[2], hits);
-                atomicAdd(&A.stats[3], (unsigned long long) drainCalls);
-                atomicAdd(&A.stats[4], (unsigned long long) sumMost);
                 atomicAdd(&A.stats[5], (unsigned long long) sumMostPairs);
-                atomicAdd(&A.stats[6], (unsigned long long) sumMostRound);
-                atomicAdd(&A.stats[7], (unsigned long long) mostBlock);
-            }
-            __syncthreads();
-            if (tid < 33 && sHist[tid] != 0)
-                atomicAdd(&A.stats[8 + tid], (unsigned long long) sHist[tid]);
+            addStats<true>(A, fit.hits, nListed, nTests, drainCalls, sumMost, sumMostRound, sHist);
         }
     }
-
     const int64_t row = (int64_t) (wy + ly) + (int64_t) (wz + lz) * A.zStride + A.zBias;
     A.field[row * (int64_t) A.pitch + (wx + lx)] = f;
 }
@@ -759,10 +828,12 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
     __shared__ float4 sNormQ[MATRIX_STAGE];
     __shared__ uint4 sColLo[MATRIX_STAGE];      /* k = 0..7 of a splat's column: x pieces, y pieces, constant hi, mid */
     __shared__ uint4 sColHi[MATRIX_STAGE];      /* k = 8..15: z pieces, 1/r^2 pieces, constant lo, 0 */
-    __shared__ uint8_t sMask[MATRIX_STAGE];
+    __shared__ alignas(8) uint8_t sMask[MATRIX_STAGE];    /* read eight at a time in the compaction */
     __shared__ uint16_t sSlot[8][MATRIX_SLOTS + 40];  /* per wave: byte offsets of the round's relevant splats (flushed when
                                                        * full), a tile of slack; 40 KB in all: four workgroups per CU */
     __shared__ uint32_t sHist[STATS ? 33 : 1];
+    static_assert(sizeof(sPosRad) + sizeof(sNormQ) + sizeof(sColLo) + sizeof(sColHi) + sizeof(sMask) + sizeof(sSlot) <= 40960,
+                  "four workgroups per CU");
 
     const MlsArgs A = lanes.a[blockIdx.y];
     if (blockIdx.x >= A.numBlocks)
@@ -817,6 +888,7 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
     if (pos >= 0)       /* uniform over the workgroup */
     {
         const float cx = (float) (wx + lx + A.ox), cy = (float) (wy + ly + A.oy), cz = (float) (wz + lz + A.oz);
+
         /* wave-uniform floats live in scalar registers (a float made by a vector instruction would be hoisted out of the
          * loops into a vector register each: twelve of the kernel's 64) */
         /* (the builtin is folded away for a value the compiler knows to be uniform.)  The wait states are part of the
@@ -877,27 +949,10 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
         /* one candidate: the reference's test and sums (kernels/mls.cl:362-390) */
         auto accumulate = [&](const float4 pr, const float4 nq)
         {
-            const f32x2 pxy = f32x2{pr.x, pr.y} - cxy;
-            const float pz = pr.z - cz;
-            const float pp = fmaf(pxy.x, pxy.x, fmaf(pxy.y, pxy.y, pz * pz));
-            const float d = pp * pr.w;
-            if (d < RADIUS_CUTOFF)
+            const SplatOffset o = splatOffset(pr, cxy, cz);
+            if (o.d < RADIUS_CUTOFF)
             {
-                float w = 1.0f - d;
-                w *= w;
-                w *= w;
-                w *= nq.w;
-                const f32x2 ww = {w, w};
-                const f32x2 nxy = {nq.x, nq.y};
-                const f32x2 wnxy = ww * nxy;
-                const float wnz = w * nq.z;
-                fit.sumW = fit.sumW + w;
-                sWpxy = __builtin_elementwise_fma(ww, pxy, sWpxy);
-                fit.sumWpz = fmaf(w, pz, fit.sumWpz);
-                sWnxy = __builtin_elementwise_fma(ww, nxy, sWnxy);
-                fit.sumWnz = fmaf(w, nq.z, fit.sumWnz);
-                fit.sumWpp = fmaf(w, pp, fit.sumWpp);
-                fit.sumWpn = fit.sumWpn + fmaf(wnxy.x, pxy.x, fmaf(wnxy.y, pxy.y, wnz * pz));
+                fitAddPacked(fit, sWpxy, sWnxy, o, nq);
                 fit.hits++;
             }
         };
@@ -955,7 +1010,7 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
 
         int32_t end = A.commands[pos++];
         /* a round's splat ids are requested while the round before it is processed */
-        int32_t idAhead = pos + (int32_t) tid < end ? A.commands[pos + (int32_t) tid] : -1;
+        int32_t idAhead = listedId(A, pos, end, tid);
         MLS5_CLOCK(clkHead);
         bool laterRound = false;
         while (pos < end)
@@ -1030,14 +1085,11 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
                 if (STATS)
                     nListed += __popcll(__ballot(mine >= 0));
             }
-            const int32_t staged = min(end - pos, (int32_t) MATRIX_STAGE);
-            pos += MATRIX_STAGE;
-            if (pos >= end)
-            {
-                pos = A.commands[end];
-                end = (pos >= 0) ? A.commands[pos++] : INT32_MIN;
-            }
-            idAhead = pos + (int32_t) tid < end ? A.commands[pos + (int32_t) tid] : -1;
+            const ListRound r = listStep(A, pos, end, MATRIX_STAGE);
+            pos = r.pos;
+            end = r.end;
+            const int32_t staged = r.staged;
+            idAhead = listedId(A, pos, end, tid);
             MLS5_CLOCK(clkStage);
             __syncthreads();
             MLS5_CLOCK(clkBar1);
@@ -1105,9 +1157,7 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
                     uint32_t exact = 0;
                     for (uint32_t s = 0; s < v; s++)
                     {
-                        const float4 pr = *(const float4 *) ((const char *) sPosRad + tile[s]);
-                        const float px = pr.x - cx, py = pr.y - cy, pz = pr.z - cz;
-                        const float d = dot3(px, py, pz, px, py, pz) * pr.w;
+                        const float d = splatOffset(posRadAt(tile[s]), cxy, cz).d;
                         exact |= d < RADIUS_CUTOFF ? 0x80000000u >> s : 0u;
                     }
                     nMissed += waveSum((uint32_t) __popc(exact & ~cur));
@@ -1140,10 +1190,7 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
                 roundCnt = 0;
             }
         }
-        fit.sumWpx = sWpxy.x;
-        fit.sumWpy = sWpxy.y;
-        fit.sumWnx = sWnxy.x;
-        fit.sumWny = sWnxy.y;
+        fitUnpack(fit, sWpxy, sWnxy);
         f = finishCorner<SHAPE>(fit, A.boundaryFactor);
 #ifdef MLSGPU_MLS5_CLOCK
         if (A.stats != nullptr && lane == 0 && blockIdx.x % 61 == 0)     /* a sample: 18 M atomics on eight words would be the measurement */
@@ -1162,26 +1209,14 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
 #endif
         if (STATS)
         {
-            const unsigned long long hits = waveSum(fit.hits);
-            const uint32_t mostBlock = waveMax(fit.hits);
             if (lane == 0)
             {
-                atomicAdd(&A.stats[0], nListed);
-                atomicAdd(&A.stats[1], nTests);
-                atomicAdd(&A.stats[2], hits);
-                atomicAdd(&A.stats[3], (unsigned long long) drainCalls);
-                atomicAdd(&A.stats[4], (unsigned long long) sumMost);
-                atomicAdd(&A.stats[6], (unsigned long long) sumMostRound);
-                atomicAdd(&A.stats[7], (unsigned long long) mostBlock);
                 atomicAdd(&A.stats[41], nCand);                         /* candidates the prefilter passed to the drain */
                 atomicAdd(&A.stats[42], nMissed);                       /* hits it missed: must stay 0 */
             }
-            __syncthreads();
-            if (tid < 33 && sHist[tid] != 0)
-                atomicAdd(&A.stats[8 + tid], (unsigned long long) sHist[tid]);
+            addStats<true>(A, fit.hits, nListed, nTests, drainCalls, sumMost, sumMostRound, sHist);
         }
     }
-
     const int64_t row = (int64_t) (wy + ly) + (int64_t) (wz + lz) * A.zStride + A.zBias;
     A.field[row * (int64_t) A.pitch + (wx + lx)] = f;
 }
@@ -1452,19 +1487,8 @@ __global__ void testMlsKernel(int op, const float *in, uint32_t n, float *out)
             const float *s = in + 8 * i;
             fitAdd(fit, s[7], s[0], s[1], s[2], dot3(s[0], s[1], s[2], s[0], s[1], s[2]), s[4], s[5], s[6]);
         }
-        const float invSumW = 1.0f / fit.sumW;
-        const float mx = fit.sumWpx * invSumW, my = fit.sumWpy * invSumW, mz = fit.sumWpz * invSumW;
-        const float qNum = fit.sumWpn - dot3(mx, my, mz, fit.sumWnx, fit.sumWny, fit.sumWnz);
-        const float qDen = fit.sumWpp - dot3(mx, my, mz, fit.sumWpx, fit.sumWpy, fit.sumWpz);
-        float q = qNum / qDen;
-        if (fabsf(qDen) < (4 * 1.1920928955078125e-07f) * (float) fit.hits * fabsf(fit.sumWpp) || !isfinite(q))
-            q = 0.0f;
-        const float a = 0.5f * q;
-        const float bx = (fit.sumWnx - q * fit.sumWpx) * invSumW;
-        const float by = (fit.sumWny - q * fit.sumWpy) * invSumW;
-        const float bz = (fit.sumWnz - q * fit.sumWpz) * invSumW;
-        out[0] = bx; out[1] = by; out[2] = bz; out[3] = a;
-        out[4] = (-a * fit.sumWpp - dot3(bx, by, bz, fit.sumWpx, fit.sumWpy, fit.sumWpz)) * invSumW;
+        const Sphere s = fitSphere(fit);
+        out[0] = s.bx; out[1] = s.by; out[2] = s.bz; out[3] = s.a; out[4] = s.c;
     }
 }
 

@@ -9,6 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 cp mlsgpu_amd/libmlsgpu_hip.so /tmp/orig.so
+trap 'cp /tmp/orig.so mlsgpu_amd/libmlsgpu_hip.so' EXIT
 cp ab/${CLOCK_SO:-clock}.so mlsgpu_amd/libmlsgpu_hip.so
 for cloud in "${@:-uniform}"; do
   MLSGPU_BENCH_DUMP_MLS_COUNTERS=1 timeout 300 python3 bench.py --full --headline-only --no-timing --no-cross-check --workers 1 --batch 4 --steps 1 --warmup 0 --dist $cloud 2> /tmp/clock_$cloud.err > /tmp/clock_$cloud.out
@@ -23,4 +24,3 @@ for n, v in zip(names, w[:6]):
 print('  %-16s %6.1f %%' % ('rest', 100.0 * (tot - sum(w[:6])) / tot))
 " | tee -a gpurun_out/mls_clock.txt
 done
-cp /tmp/orig.so mlsgpu_amd/libmlsgpu_hip.so
