@@ -156,9 +156,7 @@ int mlsgpu::HostMailbox::publish(hipStream_t stream, const void *src, uint32_t w
 int mlsgpu::HostMailbox::publishGather(hipStream_t stream, const void *const *srcs, uint32_t count, uint32_t wordsEach)
 {
     REQUIRE(host != nullptr && count >= 1 && count <= MAX_LANES && count * wordsEach <= WORDS, MLSGPU_ERR_INVALID);
-    Lanes<const uint32_t *> s;
-    for (uint32_t k = 0; k < MAX_LANES; k++)
-        s.a[k] = static_cast<const uint32_t *>(srcs[k < count ? k : 0]);
+    const auto s = packLanes<const uint32_t *>(count, [&](uint32_t k) { return static_cast<const uint32_t *>(srcs[k]); });
     reserve();
     hipLaunchKernelGGL(mailboxGatherKernel, dim3(1), dim3(64), 0, stream, s, count, wordsEach, dev, seq);
     HIP_CHECK(hipGetLastError());
@@ -232,11 +230,10 @@ int mlsgpu_ctx::scanFlags(uint32_t **flags, uint32_t *epoch, uint32_t **tickets,
     *flags = dScanFlags;
     *epoch = scanEpoch;
     *tickets = dScanFlags + flagWords;
-    for (uint32_t k = 0; k < MLSGPU_MAX_BATCH; k++)
+    for (uint32_t k = 0; k < count; k++)
     {
         bases[k] = scanTicketBase[k];
-        if (k < count)
-            scanTicketBase[k] += gridX;         /* every workgroup of the lane draws one (wraps with the counter) */
+        scanTicketBase[k] += gridX;             /* every workgroup of the lane draws one (wraps with the counter) */
     }
     return MLSGPU_OK;
 }

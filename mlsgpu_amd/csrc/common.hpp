@@ -195,6 +195,9 @@ struct HostMailbox
  * A kernel COPIES its lane's element (`const Args A = lanes.a[blockIdx.y];`): the fields then live in scalar registers as
  * those of a by-value parameter do.  Through a reference the compiler re-loads a field wherever it is used under a condition
  * -- latticeMask, bound by scalar / vector issue, ran 18 % slower with ~100 kernel-argument loads in its loop.
+ * The host fills the array with packLanes(count, make) and nothing else does: the slots at or beyond the live count are
+ * value-initialised and never read.  A launch's grid.y -- or the lane count of a kernel that loops over the lanes -- MUST be
+ * the count its lanes were packed with.
  */
 enum { MAX_LANES = MLSGPU_MAX_BATCH };
 template<typename A>
@@ -202,6 +205,26 @@ struct Lanes
 {
     A a[MAX_LANES];
 };
+
+/* a[k] = make(k) for the live lanes k < count (<= MAX_LANES: the callers' REQUIREs) */
+template<typename A, typename Make>
+static inline Lanes<A> packLanes(uint32_t count, Make make)
+{
+    Lanes<A> lanes{};
+    for (uint32_t k = 0; k < count; k++)
+        lanes.a[k] = make(k);
+    return lanes;
+}
+
+/* the largest extent(k) over the live lanes: a launch's grid.x */
+template<typename Extent>
+static inline uint32_t mostOfLanes(uint32_t count, Extent extent)
+{
+    uint32_t most = 0;
+    for (uint32_t k = 0; k < count; k++)
+        most = extent(k) > most ? extent(k) : most;
+    return most;
+}
 
 static inline uint32_t divUp(uint64_t a, uint64_t b) { return (uint32_t) ((a + b - 1) / b); }
 static inline uint32_t roundUp(uint32_t a, uint32_t b) { return (a + b - 1) / b * b; }

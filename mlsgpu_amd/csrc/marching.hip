@@ -1800,6 +1800,12 @@ struct mlsgpu_marching
     FieldView view(const mlsgpu_swathe &sw) const { return FieldView{dField, imageWidth, sw.zStride, sw.zBias}; }
     CodeView codeView(const mlsgpu_swathe &sw) const { return CodeView{dCellCode, sw.width - 1, sw.height - 1, codeZ0}; }
     DevTables devTables() const { return DevTables{dCount, dStart, dData, dKey, dCodeRec}; }
+    /* keyOffset as the vertex keys carry it (one fractional bit per axis), src/marching.cpp:594-597 */
+    uint64_t packedKeyOffset() const
+    {
+        return ((uint64_t) keyOffset[2] << (2 * KEY_AXIS_BITS + 1)) | ((uint64_t) keyOffset[1] << (KEY_AXIS_BITS + 1))
+            | ((uint64_t) keyOffset[0] << 1);
+    }
 
     int generateCells(const mlsgpu_swathe &sw, U3 *totals);
     int sliceHistogram(const mlsgpu_swathe &sw);
@@ -2063,12 +2069,9 @@ int mlsgpu_marching::weld(uint32_t nv, uint32_t zMax)
     SortResult<K> sorted;
     PROPAGATE(radixSort<K>(ctx, "kernel.marching.sortVertices.time", keysA, dValsA, keysB, dValsB, nv, layout.bits(),
                            true, dHist, dTileSums, &sorted));
-    const uint64_t keyOffsetL = ((uint64_t) keyOffset[2] << (2 * KEY_AXIS_BITS + 1))
-        | ((uint64_t) keyOffset[1] << (KEY_AXIS_BITS + 1))
-        | ((uint64_t) keyOffset[0] << 1);                                   /* src/marching.cpp:594-597 */
     UniqueIn<K> in{sorted.keys, nv};
     CompactVerticesOut<K> outF{sorted.keys, sorted.vals, dVertices, dWelded, dWeldedKeys, dIndexRemap,
-                               &dReadback->firstExternal, layout, 2 * zMax, keyOffsetL, nv, transform};
+                               &dReadback->firstExternal, layout, 2 * zMax, packedKeyOffset(), nv, transform};
     return exclusiveScan<uint32_t>(ctx, "kernel.marching.compactVertices.time", in, outF, nv, 0u, dTileSums,
                                    &dReadback->numWelded);
 }
@@ -2086,25 +2089,14 @@ CellCodeArgs mlsgpu_marching::cellCodeArgs(const mlsgpu_swathe &sw)
 static int computeCodesLanes(mlsgpu_marching *const *ms, const mlsgpu_swathe *sws, uint32_t count)
 {
     mlsgpu_ctx *ctx = ms[0]->ctx;
-    Lanes<CellCodeArgs> L;
-    uint32_t maxRows = 0;
-    for (uint32_t k = 0; k < MAX_LANES; k++)
-    {
-        if (k < count)
-        {
-            L.a[k] = ms[k]->cellCodeArgs(sws[k]);
-            maxRows = std::max(maxRows, L.a[k].numRows);
-        }
-        else
-            L.a[k] = L.a[0];
-    }
-    if (maxRows > 0)
+    const auto L = packLanes<CellCodeArgs>(count, [&](uint32_t k) { return ms[k]->cellCodeArgs(sws[k]); });
+    if (mostOfLanes(count, [&](uint32_t k) { return L.a[k].numRows; }) > 0)
     {
         /* a wave per 2 x 2 group of rows: the grid covers the lane with the most groups */
-        uint32_t maxGroups = 0;
-        for (uint32_t k = 0; k < count; k++)
-            if (L.a[k].ch > 0)
-                maxGroups = std::max(maxGroups, (L.a[k].ch + 1) / 2 * ((L.a[k].numRows / L.a[k].ch + 1) / 2));
+        const uint32_t maxGroups = mostOfLanes(count, [&](uint32_t k) {
+            const CellCodeArgs &A = L.a[k];
+            return A.ch > 0 ? (A.ch + 1) / 2 * ((A.numRows / A.ch + 1) / 2) : 0u;
+        });
         LAUNCH(ctx, "kernel.marching.genOccupied.time", cellCodeKernel, dim3(divUp(maxGroups, 4), count), dim3(256), L);
     }
     return MLSGPU_OK;
@@ -2150,18 +2142,26 @@ static int shipOutLatticeLanes(ShipLane *lanes, uint32_t count)
 {
     REQUIRE(count >= 1 && count <= MAX_LANES, MLSGPU_ERR_INVALID);
     mlsgpu_ctx *ctx = lanes[0].m->ctx;
-    Lattice Ls[MAX_LANES];
-    CodeView Cs[MAX_LANES];
-    uint32_t numRows[MAX_LANES], cornerRows[MAX_LANES], cellRows[MAX_LANES];
-    const U3 *firstRow[MAX_LANES];
-    uint64_t keyOffsetL[MAX_LANES];
+    /* what the launches below take from one bucket */
+    struct Rec
+    {
+        mlsgpu_marching *m;
+        const ShipLane *ship;
+        Lattice L;
+        CodeView C;
+        uint32_t numRows, cornerRows, cellRows;     /* rows of the lattice, of corners, of cells */
+        const U3 *firstRow;                         /* the counts of the first row of cells */
+    };
+    Rec recs[MAX_LANES];
     for (uint32_t k = 0; k < count; k++)
     {
-        mlsgpu_marching *m = lanes[k].m;
+        Rec &r = recs[k];
+        mlsgpu_marching *m = r.m = lanes[k].m;
+        r.ship = &lanes[k];
         const mlsgpu_swathe &sw = lanes[k].sw;
         const uint32_t zTop = lanes[k].zTop, zMax = lanes[k].zMax;
         const uint32_t W = sw.width, H = sw.height;
-        Lattice &L = Ls[k];
+        Lattice &L = r.L;
         L.words = m->dLatWords;
         L.rowCounts = m->dLatRows;
         L.totals = &m->dReadback->classTotals;
@@ -2173,42 +2173,34 @@ static int shipOutLatticeLanes(ShipLane *lanes, uint32_t count)
         L.z2Last = 2 * zMax;
         L.cw = W - 1;
         L.ch = H - 1;
-        numRows[k] = (2 * (zMax - zTop) + 1) * L.rowsPerLayer;
-        REQUIRE(numRows[k] <= m->latRowsMax && L.nw <= m->latWords, MLSGPU_ERR_LENGTH);
-        Cs[k] = m->codeView(sw);
-        cornerRows[k] = (zMax - zTop + 1) * H;
-        cellRows[k] = (zMax - zTop) * L.ch;
-        firstRow[k] = m->dRowCounts + (uint64_t) (zTop - m->codeZ0) * L.ch;
-        keyOffsetL[k] = ((uint64_t) m->keyOffset[2] << (2 * KEY_AXIS_BITS + 1))
-            | ((uint64_t) m->keyOffset[1] << (KEY_AXIS_BITS + 1))
-            | ((uint64_t) m->keyOffset[0] << 1);                                /* src/marching.cpp:594-597 */
+        r.numRows = (2 * (zMax - zTop) + 1) * L.rowsPerLayer;
+        REQUIRE(r.numRows <= m->latRowsMax && L.nw <= m->latWords, MLSGPU_ERR_LENGTH);
+        r.C = m->codeView(sw);
+        r.cornerRows = (zMax - zTop + 1) * H;
+        r.cellRows = (zMax - zTop) * L.ch;
+        r.firstRow = m->dRowCounts + (uint64_t) (zTop - m->codeZ0) * L.ch;
     }
-    auto lane = [&](uint32_t k) { return k < count ? k : 0u; };
     /* existence masks */
     {
-        Lanes<LatticeMaskArgs> A;
-        uint32_t most = 0;
-        for (uint32_t j = 0; j < MAX_LANES; j++)
-        {
-            const uint32_t k = lane(j);
-            A.a[j] = LatticeMaskArgs{Ls[k], Cs[k], (const U3 *) lanes[k].m->dRowCounts, lanes[k].zTop, lanes[k].zMax,
-                                     lanes[k].sw.height, j < count ? cornerRows[k] : 0u};
-            most = std::max(most, A.a[j].numCornerRows);
-        }
+        const auto A = packLanes<LatticeMaskArgs>(count, [&](uint32_t k) {
+            const Rec &r = recs[k];
+            return LatticeMaskArgs{r.L, r.C, (const U3 *) r.m->dRowCounts, r.ship->zTop, r.ship->zMax, r.ship->sw.height, r.cornerRows};
+        });
         static const bool byRowsEnv = getenv("MLSGPU_HIP_LATTICE_MASK_ROWS") != nullptr && atoi(getenv("MLSGPU_HIP_LATTICE_MASK_ROWS")) != 0;
         bool byRows = byRowsEnv;
-        for (uint32_t j = 0; j < count; j++)
-            byRows = byRows || A.a[j].L.nw > 64;        /* (rows wider than 2 048 corners: more words than a wave has lanes) */
+        for (uint32_t k = 0; k < count; k++)
+            byRows = byRows || recs[k].L.nw > 64;       /* (rows wider than 2 048 corners: more words than a wave has lanes) */
         if (byRows)
+        {
+            const uint32_t most = mostOfLanes(count, [&](uint32_t k) { return recs[k].cornerRows; });
             LAUNCH(ctx, "kernel.marching.countUniqueVertices.time", latticeMaskKernel, dim3(divUp(most, 4), count), dim3(256), A,
                    (const uint64_t *) lanes[0].m->dEdgeLut);
+        }
         else
         {
             /* a thread per word: 64 / nw rows of corners per wave, four waves per workgroup */
-            uint32_t groups = 1;
-            for (uint32_t j = 0; j < count; j++)
-                groups = std::max(groups, divUp(A.a[j].numCornerRows, 4 * (64u / A.a[j].L.nw)));
-            LAUNCH(ctx, "kernel.marching.countUniqueVertices.time", latticeMaskWordKernel, dim3(groups, count), dim3(256), A,
+            const uint32_t groups = mostOfLanes(count, [&](uint32_t k) { return divUp(recs[k].cornerRows, 4 * (64u / recs[k].L.nw)); });
+            LAUNCH(ctx, "kernel.marching.countUniqueVertices.time", latticeMaskWordKernel, dim3(std::max(groups, 1u), count), dim3(256), A,
                    (const uint16_t *) lanes[0].m->dEdgeLut16);
         }
     }
@@ -2217,53 +2209,46 @@ static int shipOutLatticeLanes(ShipLane *lanes, uint32_t count)
         RowJob jobs[MAX_LANES];
         for (uint32_t k = 0; k < count; k++)
         {
-            mlsgpu_marching *m = lanes[k].m;
-            jobs[k] = RowJob{ArrayIn<U3>{m->dLatRows}, ArrayIn<U3>{m->dLatRows}, ArrayOut<U3>{m->dLatRows}, numRows[k],
+            mlsgpu_marching *m = recs[k].m;
+            jobs[k] = RowJob{ArrayIn<U3>{m->dLatRows}, ArrayIn<U3>{m->dLatRows}, ArrayOut<U3>{m->dLatRows}, recs[k].numRows,
                              U3{0, 0, 0}, m->dTileSums3, &m->dReadback->classTotals, nullptr};
         }
         PROPAGATE((exclusiveScanBatch<U3, ArrayIn<U3>, ArrayIn<U3>, ArrayOut<U3> >(ctx, "kernel.marching.scanUint.time", jobs, count)));
     }
     {
-        Lanes<LatticePatchArgs> A;
-        uint32_t most = 0;
-        for (uint32_t j = 0; j < MAX_LANES; j++)
-        {
-            const uint32_t k = lane(j);
-            A.a[j] = LatticePatchArgs{Ls[k], j < count ? numRows[k] * Ls[k].nw : 0u};
-            most = std::max(most, A.a[j].numWords);
-        }
-        LAUNCH(ctx, "kernel.marching.scanUint.time", latticePatchKernel, dim3(divUp(most, 256), count), dim3(256), A);
+        auto numWords = [&](uint32_t k) { return recs[k].numRows * recs[k].L.nw; };
+        const auto A = packLanes<LatticePatchArgs>(count, [&](uint32_t k) { return LatticePatchArgs{recs[k].L, numWords(k)}; });
+        LAUNCH(ctx, "kernel.marching.scanUint.time", latticePatchKernel, dim3(divUp(mostOfLanes(count, numWords), 256), count), dim3(256), A);
     }
     {
-        Lanes<LatticeVerticesArgs> A;
-        uint32_t most = 0;
-        for (uint32_t j = 0; j < MAX_LANES; j++)
-        {
-            const uint32_t k = lane(j);
-            mlsgpu_marching *m = lanes[k].m;
-            A.a[j] = LatticeVerticesArgs{Ls[k], m->view(lanes[k].sw), m->dWelded, m->dWeldedKeys, m->keyOffset[0], m->keyOffset[1],
-                                         m->keyOffset[2], keyOffsetL[k], m->transform,
-                                         j < count ? (numRows[k] / Ls[k].rowsPerLayer + 1) / 2 * ((Ls[k].rowsPerLayer + 1) / 2) : 0u};
-            most = std::max(most, A.a[j].numPairs);
-        }
+        auto numPairs = [&](uint32_t k) {
+            const Rec &r = recs[k];
+            return (r.numRows / r.L.rowsPerLayer + 1) / 2 * ((r.L.rowsPerLayer + 1) / 2);
+        };
+        const auto A = packLanes<LatticeVerticesArgs>(count, [&](uint32_t k) {
+            mlsgpu_marching *m = recs[k].m;
+            return LatticeVerticesArgs{recs[k].L, m->view(recs[k].ship->sw), m->dWelded, m->dWeldedKeys, m->keyOffset[0], m->keyOffset[1],
+                                       m->keyOffset[2], m->packedKeyOffset(), m->transform, numPairs(k)};
+        });
+        const dim3 grid(divUp(mostOfLanes(count, numPairs), 4), count);
         uint32_t enabled = 0;
         for (uint32_t k = 0; k < count; k++)
-            enabled += lanes[k].m->transform.enabled ? 1u : 0u;
+            enabled += recs[k].m->transform.enabled ? 1u : 0u;
         if (enabled == count)
-            LAUNCH(ctx, "kernel.marching.compactVertices.time", latticeVerticesKernel<1>, dim3(divUp(most, 4), count), dim3(256), A);
+            LAUNCH(ctx, "kernel.marching.compactVertices.time", latticeVerticesKernel<1>, grid, dim3(256), A);
         else if (enabled == 0)
-            LAUNCH(ctx, "kernel.marching.compactVertices.time", latticeVerticesKernel<0>, dim3(divUp(most, 4), count), dim3(256), A);
+            LAUNCH(ctx, "kernel.marching.compactVertices.time", latticeVerticesKernel<0>, grid, dim3(256), A);
         else
-            LAUNCH(ctx, "kernel.marching.compactVertices.time", latticeVerticesKernel<2>, dim3(divUp(most, 4), count), dim3(256), A);
+            LAUNCH(ctx, "kernel.marching.compactVertices.time", latticeVerticesKernel<2>, grid, dim3(256), A);
     }
     /* first cell / index slot of every row of cells of the batch, the compacted cells, then the triangles */
     {
         RowJob jobs[MAX_LANES];
         for (uint32_t k = 0; k < count; k++)
         {
-            mlsgpu_marching *m = lanes[k].m;
-            jobs[k] = RowJob{ArrayIn<U3>{firstRow[k]}, ArrayIn<U3>{firstRow[k]}, ArrayOut<U3>{m->dRowStarts}, cellRows[k],
-                             U3{0, 0, 0}, m->dTileSums3, &m->dReadback->batchTotals, nullptr};
+            const Rec &r = recs[k];
+            jobs[k] = RowJob{ArrayIn<U3>{r.firstRow}, ArrayIn<U3>{r.firstRow}, ArrayOut<U3>{r.m->dRowStarts}, r.cellRows,
+                             U3{0, 0, 0}, r.m->dTileSums3, &r.m->dReadback->batchTotals, nullptr};
         }
         PROPAGATE((exclusiveScanBatch<U3, ArrayIn<U3>, ArrayIn<U3>, ArrayOut<U3> >(ctx, "kernel.marching.scanElements.time", jobs, count)));
     }
@@ -2278,56 +2263,48 @@ static int shipOutLatticeLanes(ShipLane *lanes, uint32_t count)
          * compaction first): the slabs of the 1024^3 cloud, a third to a half occupied, 10.83 ms per step by cells and 10.60 by
          * rows; the shells cloud (under a sixth) 0.51 against 0.90 ms of emission */
         const uint32_t rowsFactor = 4;
-        uint32_t byCells[MAX_LANES], byRows[MAX_LANES], nc = 0, nr = 0;
+        const Rec *byCells[MAX_LANES], *byRows[MAX_LANES];
+        uint32_t nc = 0, nr = 0;
         for (uint32_t k = 0; k < count; k++)
         {
-            const uint32_t cellsInBatch = lanes[k].m->bufferedCells;
-            if (cellRows[k] == 0 || cellsInBatch == 0)
+            const Rec &r = recs[k];
+            const uint32_t cellsInBatch = r.m->bufferedCells;
+            if (r.cellRows == 0 || cellsInBatch == 0)
                 continue;
             /* (the rows kernel stages 9 x nw lattice words per wave in LDS and divides by nw with a 16-bit reciprocal:
              * a lattice wider than 64 words -- 2047 cells -- takes the cells route whatever its density) */
-            const bool cellsRoute = Ls[k].nw > 64
+            const bool cellsRoute = r.L.nw > 64
                                     || (routeEnv != nullptr ? routeEnv[0] != '0'
-                                                            : (uint64_t) cellsInBatch * rowsFactor < (uint64_t) cellRows[k] * Ls[k].cw);
-            if (cellsRoute) byCells[nc++] = k; else byRows[nr++] = k;
+                                                            : (uint64_t) cellsInBatch * rowsFactor < (uint64_t) r.cellRows * r.L.cw);
+            if (cellsRoute) byCells[nc++] = &r; else byRows[nr++] = &r;
         }
         if (nc > 0)
         {
-            Lanes<CompactRowCellsArgs> A;
-            Lanes<LatticeTrianglesArgs> B;
-            uint32_t mostRows = 0, mostCells = 0;
-            for (uint32_t j = 0; j < MAX_LANES; j++)
-            {
-                const uint32_t k = byCells[j < nc ? j : 0];
-                mlsgpu_marching *m = lanes[k].m;
-                A.a[j] = CompactRowCellsArgs{(const uint8_t *) m->dCellCode, Ls[k].cw, Ls[k].ch, m->codeZ0, lanes[k].zTop,
-                                             (const U3 *) m->dRowStarts, (const uchar2 *) m->dCount, m->dCells, m->dViStart,
-                                             j < nc ? cellRows[k] : 0u};
-                B.a[j] = LatticeTrianglesArgs{Ls[k], m->devTables(), (const uint2 *) m->dCells, (const uint2 *) m->dViStart,
-                                              m->dIndices, (const U3 *) &m->dReadback->batchTotals};
-                mostRows = std::max(mostRows, A.a[j].numRows);
-                if (j < nc)
-                    mostCells = std::max(mostCells, m->bufferedCells);
-            }
+            const auto A = packLanes<CompactRowCellsArgs>(nc, [&](uint32_t j) {
+                const Rec &r = *byCells[j];
+                return CompactRowCellsArgs{(const uint8_t *) r.m->dCellCode, r.L.cw, r.L.ch, r.m->codeZ0, r.ship->zTop,
+                                           (const U3 *) r.m->dRowStarts, (const uchar2 *) r.m->dCount, r.m->dCells, r.m->dViStart,
+                                           r.cellRows};
+            });
+            const auto B = packLanes<LatticeTrianglesArgs>(nc, [&](uint32_t j) {
+                const Rec &r = *byCells[j];
+                return LatticeTrianglesArgs{r.L, r.m->devTables(), (const uint2 *) r.m->dCells, (const uint2 *) r.m->dViStart,
+                                            r.m->dIndices, (const U3 *) &r.m->dReadback->batchTotals};
+            });
+            const uint32_t mostRows = mostOfLanes(nc, [&](uint32_t j) { return byCells[j]->cellRows; });
+            const uint32_t mostCells = mostOfLanes(nc, [&](uint32_t j) { return byCells[j]->m->bufferedCells; });
             LAUNCH(ctx, "kernel.marching.scanElements.time", compactRowCellsKernel, dim3(divUp(mostRows, 4), nc), dim3(256), A);
             LAUNCH(ctx, "kernel.marching.generateElements.time", latticeTrianglesKernel, dim3(divUp(mostCells, 256), nc), dim3(256), B);
         }
         if (nr > 0)
         {
-            Lanes<LatticeTrianglesRowArgs> A;
-            uint32_t most = 0;
-            for (uint32_t j = 0; j < MAX_LANES; j++)
-            {
-                const uint32_t k = byRows[j < nr ? j : 0];
-                mlsgpu_marching *m = lanes[k].m;
-                A.a[j] = LatticeTrianglesRowArgs{Ls[k], Cs[k], m->devTables(), firstRow[k], (const U3 *) m->dRowStarts,
-                                                 lanes[k].zTop, m->dIndices, j < nr ? cellRows[k] : 0u,
-                                                 (uint32_t *) (m->dReadback + 1)};
-                most = std::max(most, A.a[j].numRows);
-            }
-            uint32_t nwMax = 0;
-            for (uint32_t j = 0; j < nr; j++)
-                nwMax = std::max(nwMax, A.a[j].L.nw);
+            const auto A = packLanes<LatticeTrianglesRowArgs>(nr, [&](uint32_t j) {
+                const Rec &r = *byRows[j];
+                return LatticeTrianglesRowArgs{r.L, r.C, r.m->devTables(), r.firstRow, (const U3 *) r.m->dRowStarts, r.ship->zTop,
+                                               r.m->dIndices, r.cellRows, (uint32_t *) (r.m->dReadback + 1)};
+            });
+            const uint32_t most = mostOfLanes(nr, [&](uint32_t j) { return byRows[j]->cellRows; });
+            const uint32_t nwMax = mostOfLanes(nr, [&](uint32_t j) { return byRows[j]->L.nw; });
             /* dynamic LDS: the nine lattice rows of each of the four waves' rows of cells */
             LAUNCH_LDS(ctx, "kernel.marching.generateElements.time", latticeTrianglesRowKernel, dim3(divUp(most, 4), nr), dim3(256),
                        4 * 9 * nwMax * 16, A);
@@ -2666,15 +2643,12 @@ MLSGPU_API int mlsgpu_hip_marching_generate_batch(mlsgpu_marching *const *ms, co
     PROPAGATE(computeCodesLanes(ms, sws, count));
     /* generateCells (src/marching.cpp:500-551): the swathe totals of every bucket, one read-back */
     {
-        Lanes<RowTotalsArgs> rt;
-        for (uint32_t k = 0; k < MAX_LANES; k++)
-        {
-            mlsgpu_marching *m = ms[k < count ? k : 0];
-            const mlsgpu_swathe &sw = sws[k < count ? k : 0];
+        const auto rt = packLanes<RowTotalsArgs>(count, [&](uint32_t k) {
+            const mlsgpu_swathe &sw = sws[k];
             const uint32_t cw = sw.width - 1, ch = sw.height - 1;
             const uint64_t rows = cw > 0 ? (uint64_t) ch * (sw.zLast - sw.zFirst) : 0;
-            rt.a[k] = RowTotalsArgs{m->dRowCounts, rows, &m->dReadback->totals};
-        }
+            return RowTotalsArgs{ms[k]->dRowCounts, rows, &ms[k]->dReadback->totals};
+        });
         uint32_t *const gate = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ms[0]->dReadback) + sizeof(Readback) + 64);
         const uint32_t seq = ms[0]->box.reserve();
         LAUNCH(ctx, "kernel.marching.genOccupied.time", rowTotalsKernel, dim3(count), dim3(1024), rt, count, gate, ms[0]->box.dev, seq);

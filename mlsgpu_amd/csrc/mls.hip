@@ -1375,15 +1375,8 @@ static int mlsEnqueueLanes(mlsgpu_mls *const *ms, const MlsArgs *args, uint32_t 
         REQUIRE(ms[k]->ctx == ctx && ms[k]->shape == m->shape && ms[k]->variant == m->variant
                 && (ms[k]->dStats != nullptr) == (m->dStats != nullptr), MLSGPU_ERR_INVALID);
     HIP_CHECK(hipSetDevice(ctx->device));
-    Lanes<MlsArgs> L;
-    uint32_t maxBlocks = 0;
-    for (uint32_t k = 0; k < MAX_LANES; k++)
-    {
-        L.a[k] = args[k < count ? k : 0];
-        if (k < count)
-            maxBlocks = std::max(maxBlocks, L.a[k].numBlocks);
-    }
-    const dim3 grid(maxBlocks, count), block(512);
+    const auto L = packLanes<MlsArgs>(count, [&](uint32_t k) { return args[k]; });
+    const dim3 grid(mostOfLanes(count, [&](uint32_t k) { return args[k].numBlocks; }), count), block(512);
     const char *stat = "kernel.mls.processCorners.time";      /* src/mls.cpp:57 */
     /* tuning aid: dynamic LDS that the kernel never touches lowers its occupancy (3 workgroups per CU from 8 KB, 2 from
      * 20 KB), leaving wave slots to the memory-bound kernels of the other device workers */

@@ -865,21 +865,17 @@ static int treeBuildBatch(mlsgpu_tree *const *trees, const mlsgpu_tree_build *re
         if (direct && !packedOff && (keyBits - perPass) + bits <= 32)
             idBits = bits;
     }
-    Lanes<int32_t *> jump;
-    Lanes<WriteStartArgs> ws;
-    for (uint32_t k = 0; k < MAX_LANES; k++)
+    for (uint32_t k = 0; k < count; k++)
     {
-        mlsgpu_tree *t = trees[k < count ? k : 0];
-        if (k < count)
-        {
-            REQUIRE(numStart <= t->maxStart, MLSGPU_ERR_LENGTH);
-            t->numLevels = (uint32_t) (maxShift - minShift + 1);
-            t->dSplats = reqs[k].dSplats;
-        }
-        jump.a[k] = direct ? reinterpret_cast<int32_t *>(t->dNodeCounts) : t->dJumpPos;
-        ws.a[k] = WriteStartArgs{t->dStart, t->dCommands, t->dJumpPos};
+        mlsgpu_tree *t = trees[k];
+        REQUIRE(numStart <= t->maxStart, MLSGPU_ERR_LENGTH);
+        t->numLevels = (uint32_t) (maxShift - minShift + 1);
+        t->dSplats = reqs[k].dSplats;
     }
     /* fill(jumpPos, -1), kernels/octree.cl:346 -- or, on the direct route, the node counters (NodeOut writes jumpPos) */
+    const auto jump = packLanes<int32_t *>(count, [&](uint32_t k) {
+        return direct ? reinterpret_cast<int32_t *>(trees[k]->dNodeCounts) : trees[k]->dJumpPos;
+    });
     LAUNCH(ctx, "kernel.octree.fill.time", fillKernel, dim3(divUp(numStart, 256), count), dim3(256), jump, numStart,
            (int32_t) (direct ? 0 : -1));
 
@@ -901,24 +897,24 @@ static int treeBuildBatch(mlsgpu_tree *const *trees, const mlsgpu_tree_build *re
         {
             /* writeEntries + the sort's first pass as one count / digit scan / scatter, see entryScatterKernel */
             const char *stat = "kernel.octree.writeEntries.time";
-            Lanes<EntryHistArgs> eh;
-            Lanes<SortDigitScanArgs> ds;
-            Lanes<EntryTotalArgs> et;
-            Lanes<EntryScatterArgs> es;
-            uint32_t maxTiles = 0;
-            for (uint32_t a = 0; a < MAX_LANES; a++)
-            {
-                const uint32_t k = act[a < na ? a : 0];
-                mlsgpu_tree *t = trees[k];
-                const uint32_t tilesE = a < na ? divUp(reqs[k].numSplats, ENT_TILE) : 0u;
-                uint32_t *const dDigitTotals = t->dHist + (uint64_t) (1u << perPass) * divUp(reqs[k].numSplats, ENT_TILE);
-                const EntryParams P = params(k);
-                eh.a[a] = EntryHistArgs{P, t->dEntryNotes, t->dHist, tilesE, reqs[k].numSplats};
-                ds.a[a] = SortDigitScanArgs{t->dHist, dDigitTotals, tilesE};
-                et.a[a] = EntryTotalArgs{dDigitTotals, t->dNumEntries, t->dDigitBase};
-                es.a[a] = EntryScatterArgs{P, t->dEntryNotes, t->dHist, dDigitTotals, tilesE, reqs[k].numSplats, t->dKeysB, t->dValsB, idBits};
-                maxTiles = std::max(maxTiles, tilesE);
-            }
+            auto tilesE = [&](uint32_t a) { return divUp(reqs[act[a]].numSplats, ENT_TILE); };
+            auto digitTotals = [&](uint32_t a) { return trees[act[a]]->dHist + (uint64_t) (1u << perPass) * tilesE(a); };
+            const auto eh = packLanes<EntryHistArgs>(na, [&](uint32_t a) {
+                mlsgpu_tree *t = trees[act[a]];
+                return EntryHistArgs{params(act[a]), t->dEntryNotes, t->dHist, tilesE(a), reqs[act[a]].numSplats};
+            });
+            const auto ds = packLanes<SortDigitScanArgs>(na, [&](uint32_t a) {
+                return SortDigitScanArgs{trees[act[a]]->dHist, digitTotals(a), tilesE(a)};
+            });
+            const auto et = packLanes<EntryTotalArgs>(na, [&](uint32_t a) {
+                return EntryTotalArgs{digitTotals(a), trees[act[a]]->dNumEntries, trees[act[a]]->dDigitBase};
+            });
+            const auto es = packLanes<EntryScatterArgs>(na, [&](uint32_t a) {
+                mlsgpu_tree *t = trees[act[a]];
+                return EntryScatterArgs{params(act[a]), t->dEntryNotes, t->dHist, digitTotals(a), tilesE(a), reqs[act[a]].numSplats,
+                                        t->dKeysB, t->dValsB, idBits};
+            });
+            const uint32_t maxTiles = mostOfLanes(na, tilesE);
             LAUNCH(ctx, stat, entryHistKernel, dim3(maxTiles, na), dim3(ENT_THREADS), eh, perPass);
             LAUNCH(ctx, stat, (sortDigitScanKernel<uint32_t>), dim3(1u << perPass, na), dim3(PRIM_BLOCK), ds);
             /* The entry counts (2.4 .. 3.8 per splat on the BASELINE clouds, 8 at most) come back to the host: the remaining
@@ -970,19 +966,15 @@ static int treeBuildBatch(mlsgpu_tree *const *trees, const mlsgpu_tree_build *re
         {
             /* the sort's last pass: histogram + whole-key counts */
             const uint32_t shift = perPass, digitBits = keyBits - perPass;
-            Lanes<SortHistArgs<uint32_t> > h;
-            Lanes<SortDigitScanArgs> d;
-            uint32_t maxTiles = 0;
-            for (uint32_t a = 0; a < MAX_LANES; a++)
-            {
-                const SortJob<uint32_t> &j = sortJobs[a < na ? a : 0];
-                mlsgpu_tree *t = trees[act[a < na ? a : 0]];
-                const uint32_t tiles = a < na ? sortTiles(j.n) : 0u;
-                uint32_t *const dDigitTotals = j.dHist + (uint64_t) SORT_MAX_BINS * sortTiles(j.n);
-                h.a[a] = SortHistArgs<uint32_t>{j.keysA, j.dHist, j.n, j.nDev, tiles, t->dNodeCounts, t->dDigitBase, idBits};
-                d.a[a] = SortDigitScanArgs{j.dHist, dDigitTotals, tiles};
-                maxTiles = std::max(maxTiles, tiles);
-            }
+            const auto h = packLanes<SortHistArgs<uint32_t> >(na, [&](uint32_t a) {
+                const SortJob<uint32_t> &j = sortJobs[a];
+                return SortHistArgs<uint32_t>{j.keysA, j.dHist, j.n, j.nDev, sortTiles(j.n), trees[act[a]]->dNodeCounts,
+                                              trees[act[a]]->dDigitBase, idBits};
+            });
+            const auto d = packLanes<SortDigitScanArgs>(na, [&](uint32_t a) {
+                return SortDigitScanArgs{sortJobs[a].dHist, sortDigitTotals(sortJobs[a]), sortTiles(sortJobs[a].n)};
+            });
+            const uint32_t maxTiles = mostOfLanes(na, [&](uint32_t a) { return sortTiles(sortJobs[a].n); });
             if (maxTiles > 0)
             {
                 LAUNCH(ctx, "kernel.octree.sort.time", (sortHistKernel<uint32_t, true>), dim3(maxTiles, na), dim3(PRIM_BLOCK), h, shift,
@@ -1023,24 +1015,22 @@ static int treeBuildBatch(mlsgpu_tree *const *trees, const mlsgpu_tree_build *re
         {
             /* ... and the last scatter: every id to its command position */
             const uint32_t shift = perPass, digitBits = keyBits - perPass;
-            Lanes<SortScatterArgs<uint32_t> > sc;
-            uint32_t maxTiles = 0;
-            for (uint32_t a = 0; a < MAX_LANES; a++)
-            {
-                const SortJob<uint32_t> &j = sortJobs[a < na ? a : 0];
-                mlsgpu_tree *t = trees[act[a < na ? a : 0]];
-                const uint32_t tiles = a < na ? sortTiles(j.n) : 0u;
-                uint32_t *const dDigitTotals = j.dHist + (uint64_t) SORT_MAX_BINS * sortTiles(j.n);
-                sc.a[a] = SortScatterArgs<uint32_t>{j.keysA, j.valsA, (uint32_t *) nullptr, reinterpret_cast<uint32_t *>(t->dCommands), j.dHist,
-                                                   dDigitTotals, j.n, j.nDev, tiles, t->dNodeBase, t->dDigitBase, idBits,
-                                                   (uint32_t) reqs[act[a < na ? a : 0]].firstSplat};
-                maxTiles = std::max(maxTiles, tiles);
-            }
+            const auto sc = packLanes<SortScatterArgs<uint32_t> >(na, [&](uint32_t a) {
+                const SortJob<uint32_t> &j = sortJobs[a];
+                mlsgpu_tree *t = trees[act[a]];
+                return SortScatterArgs<uint32_t>{j.keysA, j.valsA, (uint32_t *) nullptr, reinterpret_cast<uint32_t *>(t->dCommands), j.dHist,
+                                                 sortDigitTotals(j), j.n, j.nDev, sortTiles(j.n), t->dNodeBase, t->dDigitBase, idBits,
+                                                 (uint32_t) reqs[act[a]].firstSplat};
+            });
+            const uint32_t maxTiles = mostOfLanes(na, [&](uint32_t a) { return sortTiles(sortJobs[a].n); });
             if (maxTiles > 0)
                 LAUNCH(ctx, "kernel.octree.sort.time", (sortScatterKernel<uint32_t, false, 8, true>), dim3(maxTiles, na), dim3(PRIM_BLOCK), sc,
                        shift, digitBits);
         }
     }
+    const auto ws = packLanes<WriteStartArgs>(count, [&](uint32_t k) {
+        return WriteStartArgs{trees[k]->dStart, trees[k]->dCommands, trees[k]->dJumpPos};
+    });
     LAUNCH(ctx, "kernel.octree.writeStart.time", writeStartKernel, dim3(divUp(numStart, 256), count), dim3(256),
            ws, lo, minShift, maxShift, numStart);
     return MLSGPU_OK;

@@ -423,17 +423,15 @@ template<typename T, typename In1, typename In2, typename Out>
 static int scanPhase1Batch(mlsgpu_ctx *ctx, const char *statName, const ScanJob<T, In1, In2, Out> *jobs, uint32_t count)
 {
     REQUIRE(count >= 1 && count <= MAX_LANES, MLSGPU_ERR_INVALID);
-    Lanes<ScanReduceArgs<T, In1> > r;
-    Lanes<ScanTileSumsArgs<T> > t;
-    uint32_t maxTiles = 0;
-    for (uint32_t k = 0; k < MAX_LANES; k++)
-    {
-        const ScanJob<T, In1, In2, Out> &j = jobs[k < count ? k : 0];
-        const uint32_t tiles = k < count ? scanTiles(j.n) : 0u;
-        r.a[k] = ScanReduceArgs<T, In1>{j.in1, j.dTileSums, j.n, j.nDev, tiles};
-        t.a[k] = ScanTileSumsArgs<T>{j.dTileSums, tiles, j.seed, j.dTotal};
-        maxTiles = tiles > maxTiles ? tiles : maxTiles;
-    }
+    const auto r = packLanes<ScanReduceArgs<T, In1> >(count, [&](uint32_t k) {
+        const ScanJob<T, In1, In2, Out> &j = jobs[k];
+        return ScanReduceArgs<T, In1>{j.in1, j.dTileSums, j.n, j.nDev, scanTiles(j.n)};
+    });
+    const auto t = packLanes<ScanTileSumsArgs<T> >(count, [&](uint32_t k) {
+        const ScanJob<T, In1, In2, Out> &j = jobs[k];
+        return ScanTileSumsArgs<T>{j.dTileSums, scanTiles(j.n), j.seed, j.dTotal};
+    });
+    const uint32_t maxTiles = mostOfLanes(count, [&](uint32_t k) { return scanTiles(jobs[k].n); });
     if (maxTiles > 0)
         LAUNCH(ctx, statName, (scanReduceKernel<T, In1>), dim3(maxTiles, count), dim3(PRIM_BLOCK), r);
     LAUNCH(ctx, statName, (scanTileSumsKernel<T>), dim3(1, count), dim3(PRIM_BLOCK), t);
@@ -445,15 +443,11 @@ template<typename T, typename In1, typename In2, typename Out>
 static int scanPhase2Batch(mlsgpu_ctx *ctx, const char *statName, const ScanJob<T, In1, In2, Out> *jobs, uint32_t count)
 {
     REQUIRE(count >= 1 && count <= MAX_LANES, MLSGPU_ERR_INVALID);
-    Lanes<ScanApplyArgs<T, In2, Out> > a;
-    uint32_t maxTiles = 0;
-    for (uint32_t k = 0; k < MAX_LANES; k++)
-    {
-        const ScanJob<T, In1, In2, Out> &j = jobs[k < count ? k : 0];
-        const uint32_t tiles = k < count ? scanTiles(j.n) : 0u;
-        a.a[k] = ScanApplyArgs<T, In2, Out>{j.in2, j.out, (const T *) j.dTileSums, j.n, j.nDev, zeroOf(T()), (T *) nullptr, tiles};
-        maxTiles = tiles > maxTiles ? tiles : maxTiles;
-    }
+    const auto a = packLanes<ScanApplyArgs<T, In2, Out> >(count, [&](uint32_t k) {
+        const ScanJob<T, In1, In2, Out> &j = jobs[k];
+        return ScanApplyArgs<T, In2, Out>{j.in2, j.out, (const T *) j.dTileSums, j.n, j.nDev, zeroOf(T()), (T *) nullptr, scanTiles(j.n)};
+    });
+    const uint32_t maxTiles = mostOfLanes(count, [&](uint32_t k) { return scanTiles(jobs[k].n); });
     if (maxTiles > 0)
         LAUNCH(ctx, statName, (scanApplyKernel<T, In2, Out, false>), dim3(maxTiles, count), dim3(PRIM_BLOCK), a);
     return MLSGPU_OK;
@@ -464,40 +458,34 @@ template<typename T, typename In1, typename In2, typename Out>
 static int exclusiveScanBatch(mlsgpu_ctx *ctx, const char *statName, const ScanJob<T, In1, In2, Out> *jobs, uint32_t count)
 {
     REQUIRE(count >= 1 && count <= MAX_LANES, MLSGPU_ERR_INVALID);
-    uint32_t maxTiles = 0;
-    for (uint32_t k = 0; k < count; k++)
-        maxTiles = std::max(maxTiles, scanTiles(jobs[k].n));
+    /* (the one- and two-launch forms: an empty lane still runs its tile 0, which reports the total) */
+    auto tilesOf = [&](uint32_t k) { return std::max(scanTiles(jobs[k].n), 1u); };
+    const uint32_t maxTiles = mostOfLanes(count, tilesOf);
     if (std::is_same<In1, In2>::value && maxTiles <= SCAN_ONEPASS_MAX_TILES && !scanOnePassOff())
     {
-        /* one launch (scanOnePassKernel).  An empty lane still runs its tile 0, which reports the total. */
+        /* one launch (scanOnePassKernel) */
         uint32_t *flags = nullptr, *tickets = nullptr, epoch = 0, bases[MAX_LANES];
-        maxTiles = std::max(maxTiles, 1u);
         PROPAGATE(ctx->scanFlags(&flags, &epoch, &tickets, bases, maxTiles, count));
-        Lanes<ScanOnePassArgs<T, In2, Out> > a;
-        for (uint32_t k = 0; k < MAX_LANES; k++)
-        {
-            const ScanJob<T, In1, In2, Out> &j = jobs[k < count ? k : 0];
-            const uint32_t tiles = k < count ? std::max(scanTiles(j.n), 1u) : 0u;
-            a.a[k] = ScanOnePassArgs<T, In2, Out>{j.in2, j.out, j.dTileSums, flags + (uint64_t) k * SCAN_ONEPASS_MAX_TILES,
-                                                  tickets + (uint64_t) k * SCAN_TICKET_STRIDE, bases[k], j.n, j.nDev,
-                                                  j.seed, j.dTotal, tiles};
-        }
+        const auto a = packLanes<ScanOnePassArgs<T, In2, Out> >(count, [&](uint32_t k) {
+            const ScanJob<T, In1, In2, Out> &j = jobs[k];
+            return ScanOnePassArgs<T, In2, Out>{j.in2, j.out, j.dTileSums, flags + (uint64_t) k * SCAN_ONEPASS_MAX_TILES,
+                                                tickets + (uint64_t) k * SCAN_TICKET_STRIDE, bases[k], j.n, j.nDev,
+                                                j.seed, j.dTotal, tilesOf(k)};
+        });
         LAUNCH(ctx, statName, (scanOnePassKernel<T, In2, Out>), dim3(maxTiles, count), dim3(PRIM_BLOCK), a, epoch);
         return MLSGPU_OK;
     }
     if (maxTiles <= SCAN_FUSED_MAX_TILES)
     {
-        /* two launches: raw tile sums, then the scan proper.  An empty lane still runs its tile 0, which reports the total. */
-        Lanes<ScanReduceArgs<T, In1> > r;
-        Lanes<ScanApplyArgs<T, In2, Out> > a;
-        for (uint32_t k = 0; k < MAX_LANES; k++)
-        {
-            const ScanJob<T, In1, In2, Out> &j = jobs[k < count ? k : 0];
-            const uint32_t tiles = k < count ? std::max(scanTiles(j.n), 1u) : 0u;
-            r.a[k] = ScanReduceArgs<T, In1>{j.in1, j.dTileSums, j.n, j.nDev, tiles};
-            a.a[k] = ScanApplyArgs<T, In2, Out>{j.in2, j.out, (const T *) j.dTileSums, j.n, j.nDev, j.seed, j.dTotal, tiles};
-        }
-        maxTiles = std::max(maxTiles, 1u);
+        /* two launches: raw tile sums, then the scan proper */
+        const auto r = packLanes<ScanReduceArgs<T, In1> >(count, [&](uint32_t k) {
+            const ScanJob<T, In1, In2, Out> &j = jobs[k];
+            return ScanReduceArgs<T, In1>{j.in1, j.dTileSums, j.n, j.nDev, tilesOf(k)};
+        });
+        const auto a = packLanes<ScanApplyArgs<T, In2, Out> >(count, [&](uint32_t k) {
+            const ScanJob<T, In1, In2, Out> &j = jobs[k];
+            return ScanApplyArgs<T, In2, Out>{j.in2, j.out, (const T *) j.dTileSums, j.n, j.nDev, j.seed, j.dTotal, tilesOf(k)};
+        });
         LAUNCH(ctx, statName, (scanReduceKernel<T, In1>), dim3(maxTiles, count), dim3(PRIM_BLOCK), r);
         LAUNCH(ctx, statName, (scanApplyKernel<T, In2, Out, true>), dim3(maxTiles, count), dim3(PRIM_BLOCK), a);
         return MLSGPU_OK;
@@ -1107,6 +1095,10 @@ struct SortJob
     SortResult<K> result;       /* out */
 };
 
+/* the digit totals of a lane's sort: behind its per-tile histograms */
+template<typename K>
+static inline uint32_t *sortDigitTotals(const SortJob<K> &j) { return j.dHist + (uint64_t) SORT_MAX_BINS * sortTiles(j.n); }
+
 /*
  * Sorts every lane's pairs.  iota: values are 0..n-1 and valsA is not read.  doneBits: the lowest doneBits key bits have
  * been sorted already (by a pass of that width fused into the producer of the keys); the remaining passes keep the split of
@@ -1144,22 +1136,21 @@ static int radixSortBatch(mlsgpu_ctx *ctx, const char *statName, SortJob<K> *job
     for (uint32_t p = 0; shift < bits; p++)
     {
         const uint32_t digitBits = (bits - shift) < perPass ? (bits - shift) : perPass;
-        Lanes<SortHistArgs<K> > h;
-        Lanes<SortDigitScanArgs> d;
-        Lanes<SortScatterArgs<K> > s;
-        for (uint32_t k = 0; k < MAX_LANES; k++)
-        {
-            const SortJob<K> &j = jobs[k < count ? k : 0];
-            const uint32_t t = k < count ? tiles[k] : 0u;
-            /* keysWanted = false: the caller reads the sorted VALUES only, so the last pass leaves the keys unwritten */
-            const bool lastPass = shift + digitBits >= bits;
-            K *const kin = flipped ? j.keysB : j.keysA, *const kout = !keysWanted && lastPass ? (K *) nullptr : flipped ? j.keysA : j.keysB;
+        /* keysWanted = false: the caller reads the sorted VALUES only, so the last pass leaves the keys unwritten */
+        const bool keysOut = keysWanted || shift + digitBits < bits;
+        const auto h = packLanes<SortHistArgs<K> >(count, [&](uint32_t k) {
+            const SortJob<K> &j = jobs[k];
+            return SortHistArgs<K>{flipped ? j.keysB : j.keysA, j.dHist, j.n, j.nDev, tiles[k]};
+        });
+        const auto d = packLanes<SortDigitScanArgs>(count, [&](uint32_t k) {
+            return SortDigitScanArgs{jobs[k].dHist, sortDigitTotals(jobs[k]), tiles[k]};
+        });
+        const auto s = packLanes<SortScatterArgs<K> >(count, [&](uint32_t k) {
+            const SortJob<K> &j = jobs[k];
+            K *const kin = flipped ? j.keysB : j.keysA, *const kout = !keysOut ? (K *) nullptr : flipped ? j.keysA : j.keysB;
             uint32_t *const vin = flipped ? j.valsB : j.valsA, *const vout = flipped ? j.valsA : j.valsB;
-            uint32_t *const dDigitTotals = j.dHist + (uint64_t) SORT_MAX_BINS * sortTiles(j.n);
-            h.a[k] = SortHistArgs<K>{kin, j.dHist, j.n, j.nDev, t};
-            d.a[k] = SortDigitScanArgs{j.dHist, dDigitTotals, t};
-            s.a[k] = SortScatterArgs<K>{kin, vin, kout, vout, j.dHist, dDigitTotals, j.n, j.nDev, t};
-        }
+            return SortScatterArgs<K>{kin, vin, kout, vout, j.dHist, sortDigitTotals(j), j.n, j.nDev, tiles[k]};
+        });
         LAUNCH(ctx, statName, (sortHistKernel<K>), dim3(maxTiles, count), dim3(PRIM_BLOCK), h, shift, digitBits);
         LAUNCH(ctx, statName, (sortDigitScanKernel<uint32_t>), dim3(1u << digitBits, count), dim3(PRIM_BLOCK), d);
 #define SORT_SCATTER(IOTA, BITS)                                                                                       \
