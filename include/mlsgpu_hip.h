@@ -226,7 +226,8 @@ int mlsgpu_hip_marching_create(mlsgpu_ctx *ctx, uint32_t maxWidth, uint32_t maxH
 void mlsgpu_hip_marching_destroy(mlsgpu_marching *m);
 uint64_t mlsgpu_hip_marching_resource_usage(uint32_t maxWidth, uint32_t maxHeight, uint32_t maxDepth,
                                             uint32_t maxSwathe, uint64_t meshMemory, const uint32_t alignment[3]);
-/* Marching::generate, src/marching.cpp:745-824.  Blocks until the bucket is done (as the reference's does). */
+/* Marching::generate, src/marching.cpp:745-824: mlsgpu_hip_marching_generate_batch (below) with one bucket.  Blocks until
+ * the bucket is done (as the reference's does). */
 int mlsgpu_hip_marching_generate(mlsgpu_marching *m, const mlsgpu_generator *generator,
                                  mlsgpu_output_fn output, void *outputUser,
                                  const uint32_t size[3], const uint32_t keyOffset[3]);
@@ -275,9 +276,10 @@ int mlsgpu_hip_mls_enqueue_batch(mlsgpu_mls *const *mls, float *const *dFields, 
 typedef int (*mlsgpu_batch_output_fn)(void *user, uint32_t index, void *stream, const mlsgpu_mesh *mesh);
 /* Marching::generate (src/marching.cpp:745-824) for `count` buckets in lock-step: marchings[k] (distinct objects of one
  * context) takes generators[k], sizes[3k..] and keyOffsets[3k..]; one set of launches with a bucket dimension, the swathe
- * totals and the welded counts of all buckets read back together.  Per bucket the meshes are those of
- * mlsgpu_hip_marching_generate, bit for bit, delivered bucket by bucket in order.  Buckets that need several swathes, or
- * whose swathe overflows the mesh memory, take the one-bucket path behind the shared launches.  Blocks. */
+ * totals and the welded counts of all buckets read back together.  A bucket's meshes do not depend on the buckets it shares
+ * the launches with; they are delivered bucket by bucket in order.  A bucket whose swathe overflows the mesh memory is split
+ * behind the shared launches; when a bucket needs several swathes (or MLSGPU_HIP_WELD=sort) the buckets of the call go
+ * through the reference's swathe loop one at a time.  Blocks. */
 int mlsgpu_hip_marching_generate_batch(mlsgpu_marching *const *marchings, const mlsgpu_generator *generators, uint32_t count,
                                        mlsgpu_batch_output_fn output, void *outputUser,
                                        const uint32_t *sizes, const uint32_t *keyOffsets);
@@ -304,7 +306,8 @@ void mlsgpu_hip_worker_destroy(mlsgpu_worker *w);
 uint64_t mlsgpu_hip_worker_resource_usage(const mlsgpu_worker_config *cfg);
 uint64_t mlsgpu_hip_worker_resource_usage_lanes(const mlsgpu_worker_config *cfg, uint32_t lanes);
 /* One SubItem of a WorkItem (src/workers.cpp:235-285): lowExtent = sub.grid.getExtent(i).first,
- * numVertices = sub.grid.numVertices(i).  dSplats is the WorkItem's device splat buffer. */
+ * numVertices = sub.grid.numVertices(i).  dSplats is the WorkItem's device splat buffer.  It is
+ * mlsgpu_hip_worker_process_batch (below) with one item. */
 int mlsgpu_hip_worker_process(mlsgpu_worker *w, mlsgpu_splat *dSplats, uint64_t firstSplat, uint64_t numSplats,
                               const int32_t lowExtent[3], const uint32_t numVertices[3],
                               mlsgpu_output_fn output, void *outputUser);
@@ -328,13 +331,13 @@ int mlsgpu_hip_worker_set_marching_group(mlsgpu_worker *w, uint32_t buckets);
 uint32_t mlsgpu_hip_worker_marching_group(const mlsgpu_worker *w);
 /* The loop over the SubItems of a WorkItem (src/workers.cpp:232-286) with the buckets taken `lanes` at a time: per group
  * one set of launches (octree build, processCorners, marching, each with a bucket dimension) and three host decisions.
- * Every bucket's meshes equal mlsgpu_hip_worker_process's bit for bit; `output` receives them bucket by bucket, in order,
- * with the bucket's index in `items`. */
+ * A bucket's meshes do not depend on the buckets it shares launches with; `output` receives them bucket by bucket, in
+ * order, with the bucket's index in `items`. */
 int mlsgpu_hip_worker_process_batch(mlsgpu_worker *w, mlsgpu_splat *dSplats, const mlsgpu_subitem *items, uint32_t numItems,
                                     mlsgpu_batch_output_fn output, void *outputUser);
 /* How many leading items of the last _process_batch call had delivered all their meshes when it returned (numItems after a
  * success; after a failure in mid-batch the rest of the items were not processed): src/workers.cpp:281-284 accounts per
- * bucket, and so can a caller of the batch. */
+ * bucket, and so can a caller of the batch.  mlsgpu_hip_worker_process counts as a call with one item: 1 or 0 after it. */
 uint32_t mlsgpu_hip_worker_batch_completed(const mlsgpu_worker *w);
 mlsgpu_tree *mlsgpu_hip_worker_lane_tree(mlsgpu_worker *w, uint32_t lane);
 mlsgpu_marching *mlsgpu_hip_worker_lane_marching(mlsgpu_worker *w, uint32_t lane);

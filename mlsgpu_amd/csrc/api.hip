@@ -442,8 +442,6 @@ struct mlsgpu_worker
     std::vector<WorkerLane> lanes;          /* lanes[0] is the worker of the reference */
     bool keepSplats = false;
     uint32_t marchingGroup = 2;     /* buckets per processCorners / marching launch; 0: all the lanes (see set_marching_group) */
-    mlsgpu_output_fn userOutput = nullptr;
-    void *userOutputData = nullptr;
     mlsgpu_batch_output_fn batchOutput = nullptr;
     void *batchOutputData = nullptr;
     uint32_t batchBase = 0;                 /* index of the first bucket of the group that is being processed */
@@ -597,14 +595,6 @@ MLSGPU_API uint32_t mlsgpu_hip_worker_marching_group(const mlsgpu_worker *w) { r
 /* MeshFilterChain::operator() with the one ScaleBiasFilter the worker installs
  * (src/workers.cpp:226-230, src/mesh_filter.cpp:45-66): filter, then the user's output functor.
  * (Scale / bias is folded into Marching's vertex emission, mlsgpu_hip_marching_set_vertex_transform.) */
-static int workerOutput(void *user, void *stream, const mlsgpu_mesh *mesh)
-{
-    mlsgpu_worker *w = static_cast<mlsgpu_worker *>(user);
-    if (w->userOutput)
-        return w->userOutput(w->userOutputData, stream, mesh);
-    return 0;
-}
-
 static int workerBatchOutput(void *user, uint32_t index, void *stream, const mlsgpu_mesh *mesh)
 {
     mlsgpu_worker *w = static_cast<mlsgpu_worker *>(user);
@@ -613,42 +603,43 @@ static int workerBatchOutput(void *user, uint32_t index, void *stream, const mls
     return 0;
 }
 
+/* One SubItem on its own: a batch of one, on lane 0 */
+struct SingleOutput
+{
+    mlsgpu_output_fn fn;
+    void *user;
+};
+
+static int singleOutput(void *user, uint32_t, void *stream, const mlsgpu_mesh *mesh)
+{
+    const SingleOutput *s = static_cast<const SingleOutput *>(user);
+    return s->fn != nullptr ? s->fn(s->user, stream, mesh) : 0;
+}
+
 MLSGPU_API int mlsgpu_hip_worker_process(mlsgpu_worker *w, mlsgpu_splat *dSplats, uint64_t firstSplat, uint64_t numSplats,
                                          const int32_t lowExtent[3], const uint32_t numVertices[3],
                                          mlsgpu_output_fn output, void *outputUser)
 {
     REQUIRE(w != nullptr && dSplats != nullptr && lowExtent != nullptr && numVertices != nullptr, MLSGPU_ERR_INVALID);
-    /* src/workers.cpp:237-261 */
-    uint32_t keyOffset[3], size[3], expanded[3];
+    mlsgpu_subitem item;
+    item.firstSplat = firstSplat;
+    item.numSplats = numSplats;
+    item.dSplats = nullptr;
     for (int i = 0; i < 3; i++)
     {
-        REQUIRE(lowExtent[i] >= 0, MLSGPU_ERR_INVALID);     /* keyOffset is cl_uint in the reference */
-        keyOffset[i] = (uint32_t) lowExtent[i];
-        size[i] = numVertices[i];
-        expanded[i] = roundUp(size[i], 8);
+        item.lowExtent[i] = lowExtent[i];
+        item.numVertices[i] = numVertices[i];
     }
-    WorkerLane &l = w->lanes[0];
-    w->userOutput = output;
-    w->userOutputData = outputUser;
-    int pend = -1;
-    if (w->ctx->timing) pend = w->ctx->beginTiming(w->ctx->statId("device.compute"));
-    /* a failing step skips the rest, never the end of the timing region or the release of the borrowed splats */
-    mlsgpu_generator gen;
-    int rc = mlsgpu_hip_tree_build(l.tree, dSplats, firstSplat, numSplats, expanded, lowExtent, w->cfg.subsampling);
-    if (rc == MLSGPU_OK) rc = mlsgpu_hip_mls_set(l.mls, lowExtent, l.tree, w->cfg.subsampling);
-    if (rc == MLSGPU_OK) rc = mlsgpu_hip_mls_generator(l.mls, &gen);
-    if (rc == MLSGPU_OK) rc = mlsgpu_hip_marching_generate(l.marching, &gen, workerOutput, w, size, keyOffset);
-    if (pend >= 0) w->ctx->endTiming(pend);
-    mlsgpu_hip_tree_clear_splats(l.tree);
-    return rc;
+    SingleOutput single{output, outputUser};
+    return mlsgpu_hip_worker_process_batch(w, dSplats, &item, 1, singleOutput, &single);
 }
 
 /*
  * The SubItems of a WorkItem (src/workers.h:148-181; the reference's worker walks them one by one, src/workers.cpp:232-286)
  * through the path in groups of as many buckets as the worker has lanes (mlsgpu_hip_worker_set_batch): per group ONE set of
  * launches -- octree build, processCorners, marching -- with a bucket dimension, and three host decisions instead of three
- * per bucket.  Every bucket's meshes are those of mlsgpu_hip_worker_process, bit for bit; `output` gets them bucket by
- * bucket, in order, with the bucket's index.
+ * per bucket.  A bucket's meshes do not depend on the buckets it shares launches with; `output` gets them bucket by bucket,
+ * in order, with the bucket's index.
  */
 MLSGPU_API int mlsgpu_hip_worker_process_batch(mlsgpu_worker *w, mlsgpu_splat *dSplats, const mlsgpu_subitem *items,
                                                uint32_t numItems, mlsgpu_batch_output_fn output, void *outputUser)

@@ -411,12 +411,9 @@ struct CompactCellsOut
     }
 };
 
-/* per-slice (vertices, indices) histogram, only needed by the overflow path (src/marching.cpp:652-701):
- * one wave per slice sums that slice's row totals */
 /* The swathe totals of every bucket of a batch -- the sum of its row totals -- and their way to the host in ONE launch: a
- * workgroup per bucket adds up the bucket's rows, the last one to finish (a counter that wraps by itself) writes all the
- * totals and the sequence number into the mailbox.  (Before: a reduction, a scan of its tile sums and the mailbox kernel,
- * three launches of a few microseconds each behind one another.) */
+ * workgroup per bucket adds up the bucket's rows, the last one to finish (a counter that wraps by itself; with one bucket
+ * the only one) writes all the totals and the sequence number into the mailbox.  rowTotalsLanes is its one caller. */
 struct RowTotalsArgs
 {
     const U3 *rowCounts;
@@ -457,6 +454,8 @@ __global__ __launch_bounds__(1024) void rowTotalsKernel(Lanes<RowTotalsArgs> lan
     __hip_atomic_store(box, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+/* per-slice (vertices, indices) histogram, only needed by the overflow path (src/marching.cpp:652-701):
+ * one wave per slice sums that slice's row totals */
 __global__ __launch_bounds__(64) void sliceHistogramKernel(const U3 *rowCounts, uint32_t ch, uint32_t zFirst, uint32_t z0,
                                                            uint2 *histogram)
 {
@@ -1732,6 +1731,7 @@ std::vector<uint16_t> makeEdgeLut16()
     return out;
 }
 
+/* device words the host waits for; it reads them from the mailbox, except shipOutSorted's two through hReadback */
 struct Readback
 {
     U3 totals;              /* occupied cells, vertices, indices of the (sub-)swathe */
@@ -1771,7 +1771,7 @@ struct mlsgpu_marching
     uint64_t *dWeldedKeys = nullptr;
     uint32_t *dHist = nullptr, *dTileSums = nullptr;
     Readback *dReadback = nullptr;          /* device words */
-    Readback *hReadback = nullptr;          /* pinned */
+    Readback *hReadback = nullptr;          /* pinned: numWelded / firstExternal of shipOutSorted */
     HostMailbox box;                        /* the totals a host decision waits for (swathe totals, welded counts) */
     uint2 *hHistogram = nullptr;            /* pinned, maxDepth entries (viReadback in the reference) */
 
@@ -1791,9 +1791,12 @@ struct mlsgpu_marching
     bool direct = false;                    /* this generate() call uses the lattice weld */
     uint32_t codeZ0 = 0;                    /* first cell slice held in dCellCode */
     uint32_t bufferedCells = 0;             /* occupied cells accounted since the last ship-out (direct mode) */
-    const mlsgpu_generator *generator = nullptr;
-    mlsgpu_output_fn output = nullptr;
+    uint32_t offsets[2] = {0, 0};           /* vertices / indices accounted since the last ship-out */
+    uint32_t zTop = 0;                      /* first cell slice of what is buffered */
+    uint64_t shipOutsBefore = 0;            /* counters[1] when the call began */
+    mlsgpu_batch_output_fn output = nullptr;
     void *outputUser = nullptr;
+    uint32_t outputIndex = 0;               /* the bucket's index in the call */
     uint32_t keyOffset[3] = {0, 0, 0};
     KeyLayout layout = {1, 1, 1};
 
@@ -1810,11 +1813,13 @@ struct mlsgpu_marching
     int generateCells(const mlsgpu_swathe &sw, U3 *totals);
     int sliceHistogram(const mlsgpu_swathe &sw);
     int computeCodes(const mlsgpu_swathe &sw);
-    int shipOut(const mlsgpu_swathe &sw, const uint32_t sizes[2], uint32_t zTop, uint32_t zMax);
-    int shipOutSorted(const uint32_t sizes[2], uint32_t zMax, mlsgpu_mesh *mesh);
-    int shipOutDone(const uint32_t sizes[2], const mlsgpu_mesh &mesh);
+    int shipOut(const mlsgpu_swathe &sw, uint32_t zMax);
+    int shipOutSorted(uint32_t zMax, mlsgpu_mesh *mesh);
+    int shipOutDone(const mlsgpu_mesh &mesh);
     CellCodeArgs cellCodeArgs(const mlsgpu_swathe &sw);
-    int addSlices(const mlsgpu_swathe &sw, uint32_t offsets[2], uint32_t &zTop, uint32_t *shipOuts);
+    bool overflows(const U3 &totals) const { return totals.b > vertexSpace || totals.c > indexSpace; }
+    int addSlices(const mlsgpu_swathe &sw, const U3 &totals);
+    int endGenerate(const mlsgpu_swathe &sw);
     template<typename K> int weld(uint32_t nv, uint32_t zMax);
 };
 
@@ -2021,33 +2026,45 @@ MLSGPU_API void mlsgpu_hip_marching_destroy(mlsgpu_marching *m)
     delete m;
 }
 
-/* generateCells, src/marching.cpp:500-551: classify the cells of the swathe and return the totals.
- * Leaves the scanned tile sums in dTileSums3 for the compaction pass. */
+/* The lattice weld's generateCells (src/marching.cpp:500-551) for the buckets of a batch, one launch and one read-back:
+ * totals[k] = the sum of the row totals of (sub-)swathe sws[k] of ms[k]; a single bucket is a batch of one */
+static int rowTotalsLanes(mlsgpu_marching *const *ms, const mlsgpu_swathe *sws, uint32_t count, U3 *totals)
+{
+    mlsgpu_marching *m0 = ms[0];
+    const auto rt = packLanes<RowTotalsArgs>(count, [&](uint32_t k) {
+        const mlsgpu_swathe &sw = sws[k];
+        const uint32_t cw = sw.width - 1, ch = sw.height - 1;
+        const uint64_t rows = cw > 0 ? (uint64_t) ch * (sw.zLast - sw.zFirst) : 0;
+        return RowTotalsArgs{ms[k]->dRowCounts + (uint64_t) (sw.zFirst - ms[k]->codeZ0) * ch, rows, &ms[k]->dReadback->totals};
+    });
+    uint32_t *const gate = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(m0->dReadback) + sizeof(Readback) + 64);
+    const uint32_t seq = m0->box.reserve();
+    LAUNCH(m0->ctx, "kernel.marching.genOccupied.time", rowTotalsKernel, dim3(count), dim3(1024), rt, count, gate, m0->box.dev, seq);
+    PROPAGATE(m0->box.wait(m0->ctx->stream));                /* the reference's queue.finish(), :548 */
+    std::memcpy(totals, m0->box.payload(), count * sizeof(U3));
+    return MLSGPU_OK;
+}
+
+/* generateCells, src/marching.cpp:500-551: the totals of the (sub-)swathe.  Lattice weld: from the row totals that
+ * computeCodes left.  Sort weld: classifies the cells and leaves the scanned tile sums in dTileSums3 for the compaction pass. */
 int mlsgpu_marching::generateCells(const mlsgpu_swathe &sw, U3 *totals)
 {
-    const CellRange R{sw.width - 1, sw.height - 1, sw.zFirst};
     if (direct)
     {
-        /* lattice weld: only the totals are needed now -- reduce the row totals of the (sub-)swathe */
-        const uint64_t rows = (uint64_t) R.ch * (sw.zLast - sw.zFirst);
-        const U3 *first = dRowCounts + (uint64_t) (sw.zFirst - codeZ0) * R.ch;
-        PROPAGATE((scanPhase1<U3, ArrayIn<U3> >(ctx, "kernel.marching.genOccupied.time", ArrayIn<U3>{first},
-                                                 R.cw > 0 ? rows : 0, U3{0, 0, 0}, dTileSums3, &dReadback->totals)));
+        mlsgpu_marching *self = this;
+        return rowTotalsLanes(&self, &sw, 1, totals);
     }
-    else
-    {
-        const uint64_t n = (uint64_t) R.cw * R.ch * (sw.zLast - sw.zFirst);
-        ClassifyIn in{codeView(sw), R, dCount};
-        PROPAGATE((scanPhase1<U3, ClassifyIn>(ctx, "kernel.marching.genOccupied.time", in, n, U3{0, 0, 0},
-                                              dTileSums3, &dReadback->totals)));
-    }
+    const CellRange R{sw.width - 1, sw.height - 1, sw.zFirst};
+    const uint64_t n = (uint64_t) R.cw * R.ch * (sw.zLast - sw.zFirst);
+    ClassifyIn in{codeView(sw), R, dCount};
+    PROPAGATE((scanPhase1<U3, ClassifyIn>(ctx, "kernel.marching.genOccupied.time", in, n, U3{0, 0, 0},
+                                          dTileSums3, &dReadback->totals)));
     int pend = -1;
     if (ctx->timing) pend = ctx->beginTiming(ctx->statId("kernel.marching.readback.time"));
     PROPAGATE(box.publish(ctx->stream, &dReadback->totals, 3));
     if (pend >= 0) ctx->endTiming(pend);
     PROPAGATE(box.wait(ctx->stream));                    /* the reference's queue.finish(), :548 */
-    std::memcpy(&hReadback->totals, box.payload(), sizeof(U3));
-    *totals = hReadback->totals;
+    std::memcpy(totals, box.payload(), sizeof(U3));
     return MLSGPU_OK;
 }
 
@@ -2109,9 +2126,9 @@ int mlsgpu_marching::computeCodes(const mlsgpu_swathe &sw)
 }
 
 /* shipOut, src/marching.cpp:553-625, sort-based: works on the unwelded buffers filled by generateElements */
-int mlsgpu_marching::shipOutSorted(const uint32_t sizes[2], uint32_t zMax, mlsgpu_mesh *mesh)
+int mlsgpu_marching::shipOutSorted(uint32_t zMax, mlsgpu_mesh *mesh)
 {
-    const uint32_t nv = sizes[0], ni = sizes[1];
+    const uint32_t nv = offsets[0], ni = offsets[1];
     if (wideKeys)
         PROPAGATE(weld<uint64_t>(nv, zMax));
     else
@@ -2320,8 +2337,9 @@ static int shipOutLatticeLanes(ShipLane *lanes, uint32_t count)
     for (uint32_t k = 0; k < count; k++)
     {
         mlsgpu_marching *m = lanes[k].m;
-        std::memcpy(&m->hReadback->classTotals, box.payload() + 6 * k, 2 * sizeof(U3));
-        const U3 ct = m->hReadback->classTotals, bt = m->hReadback->batchTotals;
+        U3 both[2];
+        std::memcpy(both, box.payload() + 6 * k, sizeof(both));
+        const U3 ct = both[0], bt = both[1];
         if (bt.a != m->bufferedCells || bt.b != lanes[k].sizes[0] || bt.c != lanes[k].sizes[1])
             return setError(MLSGPU_ERR_INVALID, "lattice weld: batch accounting mismatch (%u/%u cells, %u/%u vertices, %u/%u indices)",
                             bt.a, m->bufferedCells, bt.b, lanes[k].sizes[0], bt.c, lanes[k].sizes[1]);
@@ -2337,52 +2355,50 @@ static int shipOutLatticeLanes(ShipLane *lanes, uint32_t count)
 }
 
 /* the tail of shipOut (src/marching.cpp:619-624): counters, then the output functor */
-int mlsgpu_marching::shipOutDone(const uint32_t sizes[2], const mlsgpu_mesh &mesh)
+int mlsgpu_marching::shipOutDone(const mlsgpu_mesh &mesh)
 {
-    bufferedCells = 0;
     counters[1]++;
-    counters[4] += sizes[0];
-    counters[5] += sizes[1];
+    counters[4] += offsets[0];
+    counters[5] += offsets[1];
     counters[6] += mesh.numVertices;
     counters[7] += mesh.numVertices - mesh.numInternalVertices;
+    bufferedCells = 0;
+    offsets[0] = offsets[1] = 0;
     if (output != nullptr)
     {
-        const int rc = output(outputUser, ctx->stream, &mesh);
+        const int rc = output(outputUser, outputIndex, ctx->stream, &mesh);
         if (rc != 0)
             return setError(MLSGPU_ERR_CALLBACK, "output functor failed with %d", rc);
     }
     return MLSGPU_OK;
 }
 
-/* shipOut, src/marching.cpp:553-625 */
-int mlsgpu_marching::shipOut(const mlsgpu_swathe &sw, const uint32_t sizes[2], uint32_t zTop, uint32_t zMax)
+/* shipOut, src/marching.cpp:553-625: what is buffered, cells z in [zTop, zMax) */
+int mlsgpu_marching::shipOut(const mlsgpu_swathe &sw, uint32_t zMax)
 {
     if (direct)
     {
-        ShipLane lane{this, sw, {sizes[0], sizes[1]}, zTop, zMax, mlsgpu_mesh()};
+        ShipLane lane{this, sw, {offsets[0], offsets[1]}, zTop, zMax, mlsgpu_mesh()};
         PROPAGATE(shipOutLatticeLanes(&lane, 1));
-        return shipOutDone(sizes, lane.mesh);
+        return shipOutDone(lane.mesh);
     }
     mlsgpu_mesh mesh;
     mesh.dVertices = dWelded;
     mesh.dTriangles = dIndices;
     mesh.dVertexKeys = dWeldedKeys;
-    mesh.numTriangles = sizes[1] / 3;
-    PROPAGATE(shipOutSorted(sizes, zMax, &mesh));
-    return shipOutDone(sizes, mesh);
+    mesh.numTriangles = offsets[1] / 3;
+    PROPAGATE(shipOutSorted(zMax, &mesh));
+    return shipOutDone(mesh);
 }
 
-/* addSlices, src/marching.cpp:627-743 */
-int mlsgpu_marching::addSlices(const mlsgpu_swathe &swathe, uint32_t offsets[2], uint32_t &zTop, uint32_t *shipOuts)
+/* addSlices, src/marching.cpp:627-743; `totals` are generateCells' of the (sub-)swathe */
+int mlsgpu_marching::addSlices(const mlsgpu_swathe &swathe, const U3 &totals)
 {
-    uint32_t top[3] = {2 * (swathe.width - 1), 2 * (swathe.height - 1), 2 * zTop};
-    U3 totals;
-    PROPAGATE(generateCells(swathe, &totals));
     const uint32_t compacted = totals.a;
     if (compacted > 0)
     {
         uint32_t counts[2] = {totals.b, totals.c};
-        if (counts[0] > vertexSpace || counts[1] > indexSpace)
+        if (overflows(totals))
         {
             counters[0]++;
             ctx->addValue("marching.overflow", 1.0);                /* overflowStat, src/marching.cpp:655 */
@@ -2420,7 +2436,9 @@ int mlsgpu_marching::addSlices(const mlsgpu_swathe &swathe, uint32_t offsets[2],
                 mlsgpu_swathe sub = swathe;
                 sub.zFirst = subFirst;
                 sub.zLast = subLast;
-                PROPAGATE(addSlices(sub, offsets, zTop, shipOuts));
+                U3 subTotals;
+                PROPAGATE(generateCells(sub, &subTotals));
+                PROPAGATE(addSlices(sub, subTotals));
                 subFirst = subLast;
             }
         }
@@ -2429,11 +2447,8 @@ int mlsgpu_marching::addSlices(const mlsgpu_swathe &swathe, uint32_t offsets[2],
             if ((uint64_t) offsets[0] + counts[0] > vertexSpace || (uint64_t) offsets[1] + counts[1] > indexSpace)
             {
                 /* fits, but only after flushing what is buffered (:705-719) */
-                PROPAGATE(shipOut(swathe, offsets, zTop, swathe.zFirst));
-                (*shipOuts)++;
-                offsets[0] = offsets[1] = 0;
+                PROPAGATE(shipOut(swathe, swathe.zFirst));
                 zTop = swathe.zFirst;
-                top[2] = 2 * swathe.zFirst;
             }
             if (direct)
             {
@@ -2443,6 +2458,7 @@ int mlsgpu_marching::addSlices(const mlsgpu_swathe &swathe, uint32_t offsets[2],
             else
             {
                 /* scanElements + generateElements (:721-731): compaction pass, then one thread per cell */
+                const uint32_t top[3] = {2 * (swathe.width - 1), 2 * (swathe.height - 1), 2 * zTop};
                 const CellRange R{swathe.width - 1, swathe.height - 1, swathe.zFirst};
                 const uint64_t n = (uint64_t) R.cw * R.ch * (swathe.zLast - swathe.zFirst);
                 ClassifyIn in{codeView(swathe), R, dCount};
@@ -2471,9 +2487,18 @@ int mlsgpu_marching::addSlices(const mlsgpu_swathe &swathe, uint32_t offsets[2],
     return MLSGPU_OK;
 }
 
-/* the argument checks and per-call state of Marching::generate (src/marching.cpp:745-786) */
-static int beginGenerate(mlsgpu_marching *m, const mlsgpu_generator *generator, mlsgpu_output_fn output, void *outputUser,
-                         const uint32_t size[3], const uint32_t keyOffset[3], mlsgpu_swathe *swathe)
+/* the end of Marching::generate (src/marching.cpp:815-822): what is still buffered goes out, up to the swathe's last slice */
+int mlsgpu_marching::endGenerate(const mlsgpu_swathe &sw)
+{
+    if (offsets[0] > 0)
+        PROPAGATE(shipOut(sw, sw.zLast));
+    ctx->addValue("marching.shipouts", (double) (counters[1] - shipOutsBefore));        /* shipoutsStat, src/marching.cpp:822 */
+    return MLSGPU_OK;
+}
+
+/* the argument checks and per-call state of Marching::generate (src/marching.cpp:745-786) for bucket `index` of a call */
+static int beginGenerate(mlsgpu_marching *m, const mlsgpu_generator *generator, mlsgpu_batch_output_fn output, void *outputUser,
+                         uint32_t index, const uint32_t size[3], const uint32_t keyOffset[3], mlsgpu_swathe *swathe)
 {
     REQUIRE(m != nullptr && generator != nullptr && generator->enqueue != nullptr, MLSGPU_ERR_INVALID);
     REQUIRE(size != nullptr && keyOffset != nullptr, MLSGPU_ERR_INVALID);
@@ -2487,9 +2512,9 @@ static int beginGenerate(mlsgpu_marching *m, const mlsgpu_generator *generator, 
     /* global coordinates must fit the 20.1 key fields (MAX_GLOBAL_DIMENSION, src/marching.h:145-150) */
     for (int i = 0; i < 3; i++)
         REQUIRE((uint64_t) keyOffset[i] + size[i] <= (1u << 20) - 1, MLSGPU_ERR_LENGTH);
-    m->generator = generator;
     m->output = output;
     m->outputUser = outputUser;
+    m->outputIndex = index;
     for (int i = 0; i < 3; i++)
         m->keyOffset[i] = keyOffset[i];
     /* the generate-time key layout: only as many bits as this bucket's doubled local coordinates need */
@@ -2508,6 +2533,9 @@ static int beginGenerate(mlsgpu_marching *m, const mlsgpu_generator *generator, 
     if (!m->direct && !m->legacyBuffers)
         return setError(MLSGPU_ERR_LENGTH, "Marching: depth %u needs several swathes but was created for one", depth);
     m->bufferedCells = 0;
+    m->offsets[0] = m->offsets[1] = 0;
+    m->zTop = 0;
+    m->shipOutsBefore = m->counters[1];
     return MLSGPU_OK;
 }
 
@@ -2519,21 +2547,10 @@ static int callGenerator(const mlsgpu_generator *generator, mlsgpu_marching *m, 
     return MLSGPU_OK;
 }
 
-/* Marching::generate, src/marching.cpp:745-824 */
-MLSGPU_API int mlsgpu_hip_marching_generate(mlsgpu_marching *m, const mlsgpu_generator *generator,
-                                            mlsgpu_output_fn output, void *outputUser,
-                                            const uint32_t size[3], const uint32_t keyOffset[3])
+/* The swathe loop of Marching::generate (src/marching.cpp:787-824) for one bucket after beginGenerate: what a bucket of
+ * several swathes, or one that takes the sort weld, goes through */
+static int generateSwathes(mlsgpu_marching *m, const mlsgpu_generator *generator, mlsgpu_swathe swathe, uint32_t depth)
 {
-    mlsgpu_swathe swathe;
-    PROPAGATE(beginGenerate(m, generator, output, outputUser, size, keyOffset, &swathe));
-    const uint32_t depth = size[2];
-    mlsgpu_ctx *ctx = m->ctx;
-    HIP_CHECK(hipSetDevice(ctx->device));
-
-    uint32_t offsets[2] = {0, 0};
-    uint32_t zTop = 0;
-    uint32_t shipOuts = 0;
-    const uint64_t shipOutsBefore = m->counters[1];
     for (uint32_t z = 0; z < depth; z += m->maxSwathe)
     {
         swathe.zFirst = z;
@@ -2546,75 +2563,55 @@ MLSGPU_API int mlsgpu_hip_marching_generate(mlsgpu_marching *m, const mlsgpu_gen
         if (z > 0)
             swathe.zFirst--;
         PROPAGATE(m->computeCodes(swathe));
-        PROPAGATE(m->addSlices(swathe, offsets, zTop, &shipOuts));
+        U3 totals;
+        PROPAGATE(m->generateCells(swathe, &totals));
+        PROPAGATE(m->addSlices(swathe, totals));
     }
-    if (offsets[0] > 0)
-    {
-        PROPAGATE(m->shipOut(swathe, offsets, zTop, depth - 1));
-        shipOuts++;
-    }
-    ctx->addValue("marching.shipouts", (double) (m->counters[1] - shipOutsBefore));     /* shipoutsStat, src/marching.cpp:822 */
-    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MLSGPU_OK;
+    return m->endGenerate(swathe);
 }
-
-/*
- * Marching::generate for the buckets of a batch (the SubItems of one WorkItem, which the reference's worker walks one by
- * one, src/workers.cpp:232-286), in lock-step: one Marching object per bucket (own field, lattice and mesh arena), every
- * kernel launched once for the whole batch, the swathe totals and the welded counts of all buckets read back together --
- * three host decisions per BATCH.  Per bucket the results are those of mlsgpu_hip_marching_generate, bit for bit: the same
- * kernels run on the same data, only the launch is shared.  Meshes are handed to `output` bucket by bucket, in order.
- *
- * The shared launches cover buckets that take the lattice weld (one swathe spans the bucket) and whose swathe fits the mesh
- * memory; a bucket that overflows is finished by the sequential path behind the batch (the reference's slice splitting),
- * and when any bucket needs several swathes the whole batch is processed one bucket at a time.
- */
-namespace
-{
-struct BatchThunk
-{
-    mlsgpu_batch_output_fn fn;
-    void *user;
-    uint32_t index;
-};
-int batchThunkOutput(void *user, void *stream, const mlsgpu_mesh *mesh)
-{
-    const BatchThunk *t = static_cast<const BatchThunk *>(user);
-    return t->fn != nullptr ? t->fn(t->user, t->index, stream, mesh) : 0;
-}
-} // namespace
 
 extern "C" mlsgpu_mls *mlsgpu_hip_mls_of_generator(const mlsgpu_generator *gen);
 
+/*
+ * Marching::generate (src/marching.cpp:745-824) for the buckets of a batch (the SubItems of one WorkItem, which the
+ * reference's worker walks one by one, src/workers.cpp:232-286); one bucket is a batch of one.  Every bucket has its own
+ * Marching object (own field, lattice and mesh arena).  Meshes are handed to `output` bucket by bucket, in order.
+ *
+ * When every bucket takes the lattice weld (one swathe spans it) the batch runs in lock-step: every kernel launched once
+ * with a bucket dimension, the swathe totals and the welded counts of all buckets read back together -- three host decisions
+ * per BATCH.  Per bucket the results do not depend on its neighbours: the same kernels run on the same data, only the launch
+ * is shared.  A bucket whose swathe overflows the mesh memory is split and shipped by addSlices when its turn comes (the
+ * reference's slice splitting).  Otherwise -- a bucket needs several swathes, or MLSGPU_HIP_WELD=sort -- the buckets go
+ * through generateSwathes one at a time.
+ */
 MLSGPU_API int mlsgpu_hip_marching_generate_batch(mlsgpu_marching *const *ms, const mlsgpu_generator *generators, uint32_t count,
                                                   mlsgpu_batch_output_fn output, void *outputUser,
                                                   const uint32_t *sizes, const uint32_t *keyOffsets)
 {
     REQUIRE(ms != nullptr && generators != nullptr && sizes != nullptr && keyOffsets != nullptr, MLSGPU_ERR_INVALID);
     REQUIRE(count >= 1 && count <= MLSGPU_MAX_BATCH, MLSGPU_ERR_LENGTH);
-    BatchThunk thunks[MAX_LANES];
     mlsgpu_swathe sws[MAX_LANES];
     for (uint32_t k = 0; k < count; k++)
     {
         REQUIRE(ms[k] != nullptr && ms[k]->ctx == ms[0]->ctx, MLSGPU_ERR_INVALID);
         for (uint32_t j = 0; j < k; j++)
             REQUIRE(ms[j] != ms[k], MLSGPU_ERR_INVALID);
-        thunks[k] = BatchThunk{output, outputUser, k};
     }
     mlsgpu_ctx *ctx = ms[0]->ctx;
-    bool lockStep = count > 1;
+    bool lockStep = true;
     for (uint32_t k = 0; k < count; k++)
     {
-        PROPAGATE(beginGenerate(ms[k], &generators[k], batchThunkOutput, &thunks[k], sizes + 3 * k, keyOffsets + 3 * k, &sws[k]));
+        PROPAGATE(beginGenerate(ms[k], &generators[k], output, outputUser, k, sizes + 3 * k, keyOffsets + 3 * k, &sws[k]));
         lockStep = lockStep && ms[k]->direct;
     }
+    HIP_CHECK(hipSetDevice(ctx->device));
     if (!lockStep)
     {
         for (uint32_t k = 0; k < count; k++)
-            PROPAGATE(mlsgpu_hip_marching_generate(ms[k], &generators[k], batchThunkOutput, &thunks[k], sizes + 3 * k, keyOffsets + 3 * k));
+            PROPAGATE(generateSwathes(ms[k], &generators[k], sws[k], sizes[3 * k + 2]));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
         return MLSGPU_OK;
     }
-    HIP_CHECK(hipSetDevice(ctx->device));
     /* every bucket is one swathe: slices [0, depth - 1], stored from row block 1 (src/marching.cpp:787-802) */
     mlsgpu_mls *functors[MAX_LANES];
     float *fields[MAX_LANES];
@@ -2641,70 +2638,58 @@ MLSGPU_API int mlsgpu_hip_marching_generate_batch(mlsgpu_marching *const *ms, co
         for (uint32_t k = 0; k < count; k++)
             PROPAGATE(callGenerator(&generators[k], ms[k], &sws[k]));
     PROPAGATE(computeCodesLanes(ms, sws, count));
-    /* generateCells (src/marching.cpp:500-551): the swathe totals of every bucket, one read-back */
-    {
-        const auto rt = packLanes<RowTotalsArgs>(count, [&](uint32_t k) {
-            const mlsgpu_swathe &sw = sws[k];
-            const uint32_t cw = sw.width - 1, ch = sw.height - 1;
-            const uint64_t rows = cw > 0 ? (uint64_t) ch * (sw.zLast - sw.zFirst) : 0;
-            return RowTotalsArgs{ms[k]->dRowCounts, rows, &ms[k]->dReadback->totals};
-        });
-        uint32_t *const gate = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(ms[0]->dReadback) + sizeof(Readback) + 64);
-        const uint32_t seq = ms[0]->box.reserve();
-        LAUNCH(ctx, "kernel.marching.genOccupied.time", rowTotalsKernel, dim3(count), dim3(1024), rt, count, gate, ms[0]->box.dev, seq);
-        PROPAGATE(ms[0]->box.wait(ctx->stream));                 /* the reference's queue.finish(), :548 */
-    }
-    /* addSlices (src/marching.cpp:627-743) for a bucket that is one swathe with nothing buffered: it either fits the mesh
-     * memory and waits for the ship-out at the end of the bucket, or it has to be split */
+    U3 totals[MAX_LANES];
+    PROPAGATE(rowTotalsLanes(ms, sws, count, totals));
+    /* The buckets whose swathe fits the mesh memory first: with nothing buffered addSlices only accounts for them on the
+     * host, and their ship-outs at the end of the bucket share one set of launches. */
     ShipLane ship[MAX_LANES];
-    uint32_t shipOf[MAX_LANES], numShip = 0;
-    bool split[MAX_LANES];
-    uint64_t shipOutsBefore[MAX_LANES];
-    for (uint32_t k = 0; k < count; k++)
-        shipOutsBefore[k] = ms[k]->counters[1];
+    uint32_t numShip = 0;
     for (uint32_t k = 0; k < count; k++)
     {
         mlsgpu_marching *m = ms[k];
-        std::memcpy(&m->hReadback->totals, ms[0]->box.payload() + 3 * k, sizeof(U3));
-        const U3 totals = m->hReadback->totals;
-        split[k] = false;
-        shipOf[k] = MAX_LANES;
-        if (totals.a == 0)
-        {
-            ctx->addValue("marching.slices.nonempty", 0.0);
+        if (m->overflows(totals[k]))
             continue;
-        }
-        if (totals.b > m->vertexSpace || totals.c > m->indexSpace)
-        {
-            split[k] = true;            /* (addSlices below accounts for it) */
-            continue;
-        }
-        m->bufferedCells += totals.a;
-        m->counters[3] += totals.a;
-        m->counters[2] += 1;
-        ctx->addValue("marching.slices.nonempty", 1.0);
-        shipOf[k] = numShip;
-        ship[numShip++] = ShipLane{m, sws[k], {totals.b, totals.c}, 0u, sizes[3 * k + 2] - 1, mlsgpu_mesh()};
+        PROPAGATE(m->addSlices(sws[k], totals[k]));
+        if (m->offsets[0] > 0)
+            ship[numShip++] = ShipLane{m, sws[k], {m->offsets[0], m->offsets[1]}, 0u, sws[k].zLast, mlsgpu_mesh()};
     }
     if (numShip > 0)
         PROPAGATE(shipOutLatticeLanes(ship, numShip));
-    /* results bucket by bucket, in order; a bucket that has to be split goes through the sequential path here */
-    for (uint32_t k = 0; k < count; k++)
+    /* results bucket by bucket, in order; a bucket that has to be split is split and shipped here */
+    for (uint32_t k = 0, next = 0; k < count; k++)
     {
         mlsgpu_marching *m = ms[k];
-        if (shipOf[k] != MAX_LANES)
-            PROPAGATE(m->shipOutDone(ship[shipOf[k]].sizes, ship[shipOf[k]].mesh));
-        else if (split[k])
-        {
-            uint32_t offsets[2] = {0, 0}, zTop = 0, shipOuts = 0;
-            PROPAGATE(m->addSlices(sws[k], offsets, zTop, &shipOuts));
-            if (offsets[0] > 0)
-                PROPAGATE(m->shipOut(sws[k], offsets, zTop, sizes[3 * k + 2] - 1));
-        }
-        ctx->addValue("marching.shipouts", (double) (m->counters[1] - shipOutsBefore[k]));
+        if (next < numShip && ship[next].m == m)
+            PROPAGATE(m->shipOutDone(ship[next++].mesh));
+        else if (m->overflows(totals[k]))
+            PROPAGATE(m->addSlices(sws[k], totals[k]));
+        PROPAGATE(m->endGenerate(sws[k]));
     }
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return MLSGPU_OK;
+}
+
+/* Marching::generate, src/marching.cpp:745-824: a batch of one bucket */
+namespace
+{
+struct SingleOutput
+{
+    mlsgpu_output_fn fn;
+    void *user;
+};
+int singleOutput(void *user, uint32_t, void *stream, const mlsgpu_mesh *mesh)
+{
+    const SingleOutput *s = static_cast<const SingleOutput *>(user);
+    return s->fn != nullptr ? s->fn(s->user, stream, mesh) : 0;
+}
+} // namespace
+
+MLSGPU_API int mlsgpu_hip_marching_generate(mlsgpu_marching *m, const mlsgpu_generator *generator,
+                                            mlsgpu_output_fn output, void *outputUser,
+                                            const uint32_t size[3], const uint32_t keyOffset[3])
+{
+    SingleOutput single{output, outputUser};
+    return mlsgpu_hip_marching_generate_batch(&m, generator, 1, singleOutput, &single, size, keyOffset);
 }
 
 MLSGPU_API int mlsgpu_hip_marching_set_vertex_transform(mlsgpu_marching *m, int enabled, float scale,

@@ -411,3 +411,31 @@ def test_process_batch_failure_in_the_middle(ctx):
     for b, batches in zip(some, got):
         exp, _ = _oracle_bucket(ref, b)
         assert_batches_equal(batches, exp)
+
+
+def test_process_is_a_batch_of_one(ctx):
+    """Worker.process is process_batch with one item: the same batches, the same marching counters and the same
+    launches, kernel name by kernel name."""
+    import mlsgpu_amd as m
+    from mlsgpu_amd import synth
+    cloud, g = synth.make_cloud("cfg1")
+    w = m.Worker(ctx, len(cloud), max_cells=63)
+    item = (0, len(cloud), (0, 0, 0), (g, g, g))
+    runs = []
+    ctx.set_timing(True)
+    try:
+        for call in (lambda buf: w.process(buf, *item), lambda buf: w.process_batch(buf, [item])[0]):
+            buf = m.DeviceBuffer(ctx, array=cloud)          # a fresh copy: the build replaces the radii
+            before = w.marching_counters()
+            ctx.reset_stats()
+            got = call(buf)
+            launches = {name: n for name, (_, n) in ctx.stats().items() if name.startswith("kernel.") and n != 0}
+            after = w.marching_counters()
+            runs.append((got, {k: after[k] - before[k] for k in after}, launches))
+    finally:
+        ctx.set_timing(False)
+    (got, counters, launches), (got_b, counters_b, launches_b) = runs
+    assert len(got) >= 1 and counters["shipouts"] == len(got)
+    assert_batches_equal(got_b, got)
+    assert counters_b == counters
+    assert launches and launches_b == launches

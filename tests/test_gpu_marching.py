@@ -278,3 +278,46 @@ def test_generate_batch_with_host_generators(ctx, mem_slices):
     # a batch of one is the one-bucket entry point
     one = m.Marching.generate_batch(marchings[:1], gens[:1], sizes[:1], offsets[:1])
     assert_batches_equal(one[0], got[0])
+
+
+def marching_launches(ctx):
+    """Launch count of every kernel.marching.* name in the context's registry (a name that never ran counts as 0)."""
+    return {name: n for name, (_, n) in ctx.stats().items() if name.startswith("kernel.marching.") and n != 0}
+
+
+@pytest.mark.parametrize("mem_slices", [300, 2])
+def test_one_bucket_launches_as_a_batch(ctx, mem_slices):
+    """A bucket on its own IS a batch of one: Marching.generate, generate_batch of that one object and generate_batch of
+    three objects with the same field launch the same kernels the same number of times (the bucket dimension is
+    blockIdx.y) and deliver the same batches.  With two slices' worth of mesh memory (the setting at which buckets
+    overflow and are split) generate is compared with the batch of one."""
+    import mlsgpu_amd as m
+    alignment = (8, 8, 8)
+    (_, _, _), size, fn = GENERATE_CASES["tsphere"]
+    dims = (88, 80, 72)
+    mesh_memory = (dims[0] - 1) * (dims[1] - 1) * 872 * mem_slices
+    lanes = 3 if mem_slices == 300 else 1
+    marchings = [m.Marching(ctx, dims[0], dims[1], dims[2], 72, mesh_memory, alignment) for _ in range(lanes)]
+    gens = [m.binding.HostGenerator(ctx, fn, alignment) for _ in range(lanes)]
+    offset = (3, 100, 7)
+    ctx.set_timing(True)
+    try:
+        ctx.reset_stats()
+        single = marchings[0].generate(gens[0], size, offset)
+        launches = marching_launches(ctx)
+        ctx.reset_stats()
+        one = m.Marching.generate_batch(marchings[:1], gens[:1], [size], [offset])
+        launches_one = marching_launches(ctx)
+        if lanes > 1:
+            ctx.reset_stats()
+            many = m.Marching.generate_batch(marchings, gens, [size] * lanes, [offset] * lanes)
+            launches_many = marching_launches(ctx)
+    finally:
+        ctx.set_timing(False)
+    assert len(single) >= 1
+    assert launches and launches_one == launches
+    assert_batches_equal(one[0], single)
+    if lanes > 1:
+        assert launches_many == launches
+        for got in many:
+            assert_batches_equal(got, single)
