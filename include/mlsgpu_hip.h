@@ -224,6 +224,7 @@ int mlsgpu_hip_marching_create(mlsgpu_ctx *ctx, uint32_t maxWidth, uint32_t maxH
                                uint32_t maxSwathe, uint64_t meshMemory, const uint32_t alignment[3],
                                mlsgpu_marching **out);
 void mlsgpu_hip_marching_destroy(mlsgpu_marching *m);
+/* Marching::resourceUsage: device bytes a Marching of this capacity allocates. */
 uint64_t mlsgpu_hip_marching_resource_usage(uint32_t maxWidth, uint32_t maxHeight, uint32_t maxDepth,
                                             uint32_t maxSwathe, uint64_t meshMemory, const uint32_t alignment[3]);
 /* Marching::generate, src/marching.cpp:745-824: mlsgpu_hip_marching_generate_batch (below) with one bucket.  Blocks until

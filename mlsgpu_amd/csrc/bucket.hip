@@ -649,28 +649,36 @@ struct GridBox
 /* device scratch of one recursion depth; a level's sorted member lists must outlive the recursion below it */
 struct DepthBuffers
 {
-    uint32_t *keysA = nullptr, *valsA = nullptr, *keysB = nullptr, *valsB = nullptr;
-    uint32_t *hist = nullptr, *tileSums = nullptr;
-    uint64_t pairCap = 0, keysBCap = 0;
-    uint32_t *counts = nullptr, *table = nullptr, *starts = nullptr;
-    uint32_t nodeCap = 0, regionCap = 0;
-    uint32_t *total = nullptr;
-    uint32_t *scanSums = nullptr;
-    uint64_t scanCap = 0;
-    uint2 *notes = nullptr;             /* RegionView::packNote of every element of the level being split */
-    uint64_t noteCap = 0;
-    uint32_t *slices = nullptr;         /* bucketCountPrivateKernel's per-workgroup counters */
-    uint64_t sliceCap = 0;
+    DeviceArray<uint32_t> keysA, valsA, keysB, valsB, hist, tileSums;
+    uint64_t pairCap = 0;               /* pairs that keysA, valsA, valsB, hist and tileSums are ALL good for */
+    DeviceArray<uint32_t> counts, table, starts, total, scanSums;
+    DeviceArray<uint2> notes;           /* RegionView::packNote of every element of the level being split */
+    DeviceArray<uint32_t> slices;       /* bucketCountPrivateKernel's per-workgroup counters */
     /* events of callbacks that still read member lists of this level (mlsgpu_bucket::consumed): whatever overwrites the
      * level's buffers is ordered behind them on the GPU */
     std::vector<hipEvent_t> readers;
-    ~DepthBuffers()
+
+    /* the dense counters and the region table of a level of `nodes` microblock-octree nodes */
+    int reserveNodes(uint64_t nodes)
     {
-        hipFree(scanSums);
-        hipFree(notes);
-        hipFree(slices);
-        hipFree(keysA); hipFree(valsA); hipFree(keysB); hipFree(valsB); hipFree(hist); hipFree(tileSums);
-        hipFree(counts); hipFree(table); hipFree(starts); hipFree(total);
+        PROPAGATE(total.reserve(2));
+        PROPAGATE(counts.reserve(nodes));
+        return table.reserve(nodes);
+    }
+    /* what the member lists of `pairs` (region, id) pairs and their sort need, an eighth of headroom when they grow */
+    int reservePairs(uint64_t pairs)
+    {
+        if (pairs <= pairCap)
+            return MLSGPU_OK;
+        const uint64_t cap = pairs + pairs / 8 + 1024;
+        pairCap = 0;
+        PROPAGATE(keysA.reserve(cap));
+        PROPAGATE(valsA.reserve(cap));
+        PROPAGATE(valsB.reserve(cap));
+        PROPAGATE(hist.reserve(sortHistElems(cap)));
+        PROPAGATE(tileSums.reserve(scanTiles(std::max<uint64_t>(sortHistElems(cap), cap))));
+        pairCap = cap;
+        return MLSGPU_OK;
     }
 };
 
@@ -697,13 +705,6 @@ struct Bucketer
                 (void) hipStreamWaitEvent(ctx->stream, ev, 0);
             level->readers.clear();
         }
-    }
-    int ensure(uint32_t **p, size_t elems)
-    {
-        hipFree(*p);
-        *p = nullptr;
-        HIP_CHECK(hipMalloc((void **) p, std::max<size_t>(elems, 1) * sizeof(uint32_t)));
-        return MLSGPU_OK;
     }
 
     int recurse(const uint32_t *dIds, uint64_t n, bool isSubset, const GridBox &grid, uint32_t chunkCells, uint32_t microCells,
@@ -786,8 +787,6 @@ int Bucketer::recurse(const uint32_t *dIds, uint64_t n, bool isSubset, const Gri
     while (depthList->size() <= depth)
         depthList->emplace_back(new DepthBuffers);
     DepthBuffers &B = *(*depthList)[depth];
-    if (B.total == nullptr)
-        PROPAGATE(ensure(&B.total, 2));
 
     /* chunks x-major as the callbacks of bucket_impl.h:548-553; the chunks' states are independent */
     for (uint32_t cx = 0; cx < chunks[0]; cx++)
@@ -831,12 +830,7 @@ int Bucketer::recurse(const uint32_t *dIds, uint64_t n, bool isSubset, const Gri
                 }
                 L.offset[macroLevels] = (uint32_t) totalNodes;
                 const uint32_t n0 = V.dims[0] * V.dims[1] * V.dims[2];
-                if (B.nodeCap < totalNodes)
-                {
-                    PROPAGATE(ensure(&B.counts, totalNodes));
-                    PROPAGATE(ensure(&B.table, totalNodes));
-                    B.nodeCap = (uint32_t) totalNodes;
-                }
+                PROPAGATE(B.reserveNodes(totalNodes));
                 /* the level's buffers are about to be overwritten: behind the callbacks that still read its lists */
                 for (hipEvent_t ev : B.readers)
                     HIP_CHECK(hipStreamWaitEvent(ctx->stream, ev, 0));
@@ -854,16 +848,8 @@ int Bucketer::recurse(const uint32_t *dIds, uint64_t n, bool isSubset, const Gri
                     uint2 *notes = nullptr;
                     if (n >= notesFrom() && std::max(std::max(V.dims[0], V.dims[1]), V.dims[2]) <= 65536u)
                     {
-                        if (B.noteCap < n)
-                        {
-                            hipFree(B.notes);
-                            B.notes = nullptr;
-                            B.noteCap = 0;
-                            if (hipMalloc((void **) &B.notes, n * sizeof(uint2)) == hipSuccess)
-                                B.noteCap = n;
-                            else
-                                (void) hipGetLastError();       /* without them the passes read the splats again */
-                        }
+                        if (B.notes.reserve(n) != MLSGPU_OK)
+                            (void) hipGetLastError();           /* without them the passes read the splats again */
                         notes = B.notes;
                     }
                     /* private counters (bucketCountPrivateKernel): a big level whose finest counters miss the LDS table */
@@ -871,18 +857,10 @@ int Bucketer::recurse(const uint32_t *dIds, uint64_t n, bool isSubset, const Gri
                     const uint64_t numSlices = divUp(n, (uint64_t) PRIV_SPAN);
                     bool privateCounters = (ldsFrom > 0 || privateFrom() == 0) && macroLevels >= 2 && n >= privateFrom()
                         && (uint64_t) imageWords * 4 <= PRIV_LDS_BYTES && numSlices < (1u << 24);
-                    if (privateCounters && B.sliceCap < numSlices * imageWords)
+                    if (privateCounters && B.slices.reserve(numSlices * imageWords) != MLSGPU_OK)
                     {
-                        hipFree(B.slices);
-                        B.slices = nullptr;
-                        B.sliceCap = 0;
-                        if (hipMalloc((void **) &B.slices, numSlices * imageWords * 4) == hipSuccess)
-                            B.sliceCap = numSlices * imageWords;
-                        else
-                        {
-                            (void) hipGetLastError();
-                            privateCounters = false;
-                        }
+                        (void) hipGetLastError();
+                        privateCounters = false;
                     }
                     if (privateCounters)
                     {
@@ -962,23 +940,9 @@ int Bucketer::recurse(const uint32_t *dIds, uint64_t n, bool isSubset, const Gri
 
                 /* 3. member lists */
                 const RegionCountIn in{V, B.table};
-                if (B.scanCap < scanTiles(n))
-                {
-                    PROPAGATE(ensure(&B.scanSums, scanTiles(n)));
-                    B.scanCap = scanTiles(n);
-                }
+                PROPAGATE(B.scanSums.reserve(scanTiles(n)));
                 uint32_t *tileSums = B.scanSums;
-                if (B.pairCap < totalPairs)
-                {
-                    const uint64_t cap = (uint64_t) totalPairs + totalPairs / 8 + 1024;
-                    B.pairCap = 0;
-                    PROPAGATE(ensure(&B.keysA, cap));
-                    PROPAGATE(ensure(&B.valsA, cap));
-                    PROPAGATE(ensure(&B.valsB, cap));
-                    PROPAGATE(ensure(&B.hist, sortHistElems(cap)));
-                    PROPAGATE(ensure(&B.tileSums, scanTiles(std::max<uint64_t>(sortHistElems(cap), cap))));
-                    B.pairCap = cap;
-                }
+                PROPAGATE(B.reservePairs(totalPairs));
                 PROPAGATE((scanPhase1<uint32_t, RegionCountIn>(ctx, "bucket.members.time", in, n, 0u, tileSums, B.total)));
                 PROPAGATE((scanPhase2<uint32_t, RegionCountIn, RegionEmitOut>(ctx, "bucket.members.time", in,
                                                                             RegionEmitOut{V, B.table, B.keysA, B.valsA}, n,
@@ -988,12 +952,8 @@ int Bucketer::recurse(const uint32_t *dIds, uint64_t n, bool isSubset, const Gri
                  * more digits ping-pong the keys, so both key buffers exist then */
                 const uint32_t regionBits = bitsForCount(numRegions);
                 const bool oneDigit = regionBits <= SortCaps<uint32_t>::MAX_DIGIT_BITS && getenv("MLSGPU_HIP_SORT_DIGIT_BITS") == nullptr;
-                if (!oneDigit && B.keysBCap < B.pairCap)
-                {
-                    B.keysBCap = 0;
-                    PROPAGATE(ensure(&B.keysB, B.pairCap));
-                    B.keysBCap = B.pairCap;
-                }
+                if (!oneDigit)
+                    PROPAGATE(B.keysB.reserve(B.pairCap));
                 PROPAGATE(radixSort<uint32_t>(ctx, "bucket.members.time", B.keysA, B.valsA, B.keysB, B.valsB, totalPairs,
                                               regionBits, false, B.hist, B.tileSums, &sorted, nullptr, 0, false));
                 /* the callbacks may read the lists from any stream */
@@ -1082,25 +1042,16 @@ int Bucketer::recurseStream(mlsgpu_fileset *files, uint64_t n, const GridBox &gr
     while (depthList->size() <= 0)
         depthList->emplace_back(new DepthBuffers);
     DepthBuffers &B = *(*depthList)[0];
-    if (B.total == nullptr)
-        PROPAGATE(ensure(&B.total, 2));
 
     /* the chunk in flight, the batch, and two words: splats of the batch so far, splats the last chunk added */
-    mlsgpu_splat *dChunk = nullptr, *dBatch = nullptr;
-    uint32_t *dWords = nullptr, *dScanSums = nullptr;
-    uint8_t *dFlags = nullptr;
-    struct Free
-    {
-        mlsgpu_splat *&a, *&b;
-        uint32_t *&c, *&d;
-        uint8_t *&e;
-        ~Free() { hipFree(a); hipFree(b); hipFree(c); hipFree(d); hipFree(e); }
-    } release{dChunk, dBatch, dWords, dScanSums, dFlags};
-    HIP_CHECK(hipMalloc((void **) &dChunk, chunkSplats * sizeof(mlsgpu_splat)));
-    HIP_CHECK(hipMalloc((void **) &dBatch, budget * sizeof(mlsgpu_splat)));
-    HIP_CHECK(hipMalloc((void **) &dWords, 2 * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc((void **) &dScanSums, ((size_t) scanTiles(chunkSplats) + 1) * sizeof(uint32_t)));
-    HIP_CHECK(hipMalloc((void **) &dFlags, chunkSplats));
+    DeviceArray<mlsgpu_splat> dChunk, dBatch;
+    DeviceArray<uint32_t> dWords, dScanSums;
+    DeviceArray<uint8_t> dFlags;
+    PROPAGATE(dChunk.alloc(chunkSplats));
+    PROPAGATE(dBatch.alloc(budget));
+    PROPAGATE(dWords.alloc(2));
+    PROPAGATE(dScanSums.alloc((uint64_t) scanTiles(chunkSplats) + 1));
+    PROPAGATE(dFlags.alloc(chunkSplats));
 
     /* The bounding box of every file chunk's splats (with their radii), noted in the first pass: a later pass skips the chunks
      * that cannot reach the regions it is collecting -- what the reference's blob index buys on inputs whose files are
@@ -1186,12 +1137,7 @@ int Bucketer::recurseStream(mlsgpu_fileset *files, uint64_t n, const GridBox &gr
                 }
                 L.offset[macroLevels] = (uint32_t) totalNodes;
                 const uint32_t n0 = V.dims[0] * V.dims[1] * V.dims[2];
-                if (B.nodeCap < totalNodes)
-                {
-                    PROPAGATE(ensure(&B.counts, totalNodes));
-                    PROPAGATE(ensure(&B.table, totalNodes));
-                    B.nodeCap = (uint32_t) totalNodes;
-                }
+                PROPAGATE(B.reserveNodes(totalNodes));
                 /* pass 1: the counters of the whole set, chunk after chunk */
                 HIP_CHECK(hipMemsetAsync(B.counts, 0, totalNodes * 4, ctx->stream));
                 uint32_t ldsFrom = L.levels;
@@ -1299,37 +1245,15 @@ int Bucketer::recurseStream(mlsgpu_fileset *files, uint64_t n, const GridBox &gr
                     RegionView VB = V;
                     VB.splats = dBatch;
                     const uint32_t nr = r1 - r0;
-                    if (B.regionCap < nr + 1)
-                    {
-                        PROPAGATE(ensure(&B.starts, nr + 1));
-                        B.regionCap = nr + 1;
-                    }
+                    PROPAGATE(B.starts.reserve(nr + 1));
                     const RegionCountIn in{VB, B.table, r0, r1};
-                    if (B.scanCap < scanTiles(nb))
-                    {
-                        PROPAGATE(ensure(&B.scanSums, scanTiles(nb)));
-                        B.scanCap = scanTiles(nb);
-                    }
+                    PROPAGATE(B.scanSums.reserve(scanTiles(nb)));
                     PROPAGATE((scanPhase1<uint32_t, RegionCountIn>(ctx, "bucket.members.time", in, nb, 0u, B.scanSums, B.total)));
                     uint32_t totalPairs = 0;
                     HIP_CHECK(hipMemcpyAsync(&totalPairs, B.total, 4, hipMemcpyDeviceToHost, ctx->stream));
                     HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                    if (B.pairCap < totalPairs)
-                    {
-                        const uint64_t cap = (uint64_t) totalPairs + totalPairs / 8 + 1024;
-                        PROPAGATE(ensure(&B.keysA, cap));
-                        PROPAGATE(ensure(&B.valsA, cap));
-                        PROPAGATE(ensure(&B.valsB, cap));
-                        PROPAGATE(ensure(&B.hist, sortHistElems(cap)));
-                        PROPAGATE(ensure(&B.tileSums, scanTiles(std::max<uint64_t>(sortHistElems(cap), cap))));
-                        B.pairCap = cap;
-                    }
-                    if (B.keysBCap < B.pairCap)
-                    {
-                        B.keysBCap = 0;
-                        PROPAGATE(ensure(&B.keysB, B.pairCap));
-                        B.keysBCap = B.pairCap;
-                    }
+                    PROPAGATE(B.reservePairs(totalPairs));
+                    PROPAGATE(B.keysB.reserve(B.pairCap));
                     PROPAGATE((scanPhase2<uint32_t, RegionCountIn, RegionEmitOut>(ctx, "bucket.members.time", in,
                                                                                    RegionEmitOut{VB, B.table, B.keysA, B.valsA, r0, r1}, nb,
                                                                                    (const uint32_t *) B.scanSums)));
@@ -1419,14 +1343,13 @@ MLSGPU_API int mlsgpu_hip_bucket(mlsgpu_ctx *ctx, const mlsgpu_splat *dSplats, u
 static int foldBbox(mlsgpu_ctx *ctx, const mlsgpu_splat *dSplats, uint64_t numSplats, float lo[3], float hi[3])
 {
     const uint32_t blocks = (uint32_t) std::max<uint64_t>(1, std::min<uint64_t>(divUp(numSplats, 256), 2048));
-    float *dPartial = nullptr;
-    HIP_CHECK(hipMalloc((void **) &dPartial, (size_t) blocks * 6 * sizeof(float)));
+    DeviceArray<float> dPartial;
+    PROPAGATE(dPartial.alloc((uint64_t) blocks * 6));
     std::vector<float> partial((size_t) blocks * 6);
-    hipLaunchKernelGGL(bboxKernel, dim3(blocks), dim3(256), 0, ctx->stream, dSplats, numSplats, dPartial);
+    hipLaunchKernelGGL(bboxKernel, dim3(blocks), dim3(256), 0, ctx->stream, dSplats, numSplats, dPartial.get());
     hipError_t e = hipMemcpyAsync(partial.data(), dPartial, partial.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess)
         e = hipStreamSynchronize(ctx->stream);
-    hipFree(dPartial);
     if (e != hipSuccess)
         return setError(MLSGPU_ERR_HIP, "bounding grid: %s", hipGetErrorString(e));
     for (uint32_t b = 0; b < blocks; b++)
@@ -1461,8 +1384,8 @@ MLSGPU_API int mlsgpu_hip_fileset_bounding_grid(mlsgpu_fileset *files, mlsgpu_ct
     REQUIRE(spacing > 0.0f && bucketSize >= 1 && chunkSplats >= 1, MLSGPU_ERR_INVALID);
     HIP_CHECK(hipSetDevice(ctx->device));
     const uint64_t n = mlsgpu_hip_fileset_num_splats(files);
-    mlsgpu_splat *dChunk = nullptr;
-    HIP_CHECK(hipMalloc((void **) &dChunk, std::min<uint64_t>(chunkSplats, std::max<uint64_t>(n, 1)) * sizeof(mlsgpu_splat)));
+    DeviceArray<mlsgpu_splat> dChunk;
+    PROPAGATE(dChunk.alloc(std::min<uint64_t>(chunkSplats, std::max<uint64_t>(n, 1))));
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     int rc = MLSGPU_OK;
     for (uint64_t first = 0; first < n && rc == MLSGPU_OK; first += chunkSplats)
@@ -1472,7 +1395,6 @@ MLSGPU_API int mlsgpu_hip_fileset_bounding_grid(mlsgpu_fileset *files, mlsgpu_ct
         if (rc == MLSGPU_OK)
             rc = foldBbox(ctx, dChunk, cnt, lo, hi);
     }
-    hipFree(dChunk);
     PROPAGATE(rc);
     return gridFromBbox(lo, hi, spacing, bucketSize, out);
 }

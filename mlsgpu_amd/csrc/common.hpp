@@ -11,6 +11,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/mlsgpu_hip.h"
@@ -75,6 +76,104 @@ static inline void enablePeerAccess(int a, int b)
         (void) hipGetLastError();       /* "already enabled" is not an error */
     }
 }
+
+/* ---------------------------------------------------------------- owned memory */
+
+/*
+ * Device memory that belongs to one object or one call: the pointer and the element capacity it was allocated with live
+ * together, and the destructor frees.  The owner's device must be current.  alloc() and reserve() return the library's status
+ * (and set its error text); a caller that can do without the buffer clears the sticky HIP error itself.
+ */
+template<typename T>
+class DeviceArray
+{
+    T *p = nullptr;
+    uint64_t cap = 0;
+
+public:
+    DeviceArray() = default;
+    DeviceArray(DeviceArray &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DeviceArray &operator=(DeviceArray &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DeviceArray() { release(); }
+
+    /* what alloc(n) takes from the device (never a zero-byte allocation) */
+    static uint64_t bytes(uint64_t n) { return n ? n * sizeof(T) : 4; }
+    /* exactly n elements, whatever was held before */
+    int alloc(uint64_t n)
+    {
+        release();
+        const hipError_t e = hipMalloc((void **) &p, bytes(n));
+        if (e != hipSuccess)
+        {
+            p = nullptr;
+            return setError(e == hipErrorOutOfMemory ? MLSGPU_ERR_NOMEM : MLSGPU_ERR_HIP, "cannot allocate %llu bytes of device memory: %s",
+                            (unsigned long long) bytes(n), hipGetErrorString(e));
+        }
+        cap = n;
+        return MLSGPU_OK;
+    }
+    /* at least n elements; grows only, and growing DISCARDS the contents.  A failure leaves the array empty, capacity 0 */
+    int reserve(uint64_t n) { return p != nullptr && n <= cap ? MLSGPU_OK : alloc(n); }
+    void release()
+    {
+        if (p) (void) hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    uint64_t capacity() const { return cap; }
+    T *get() const { return p; }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+};
+
+/* The pinned-memory sibling, with a length n <= capacity: what a device -> host copy of n elements lands in */
+template<typename T>
+class PinnedArray
+{
+    T *p = nullptr;
+    size_t n = 0, cap = 0;
+
+public:
+    PinnedArray() = default;
+    PinnedArray(const PinnedArray &) = delete;
+    PinnedArray &operator=(const PinnedArray &) = delete;
+    ~PinnedArray() { release(); }
+
+    /* exactly `count` elements (hipHostMalloc's flags), whatever was held before; a failure leaves the array empty */
+    int alloc(size_t count, unsigned int flags = hipHostMallocDefault)
+    {
+        release();
+        if (hipHostMalloc((void **) &p, count * sizeof(T), flags) != hipSuccess)
+        {
+            p = nullptr;
+            return setError(MLSGPU_ERR_NOMEM, "cannot allocate %zu bytes of pinned memory", count * sizeof(T));
+        }
+        n = cap = count;
+        return MLSGPU_OK;
+    }
+    /* `count` elements, contents undefined: grows with a quarter of headroom, never shrinks */
+    int resize(size_t count, unsigned int flags = hipHostMallocDefault)
+    {
+        if (count > cap)
+            PROPAGATE(alloc(count + count / 4 + 1024, flags));
+        n = count;
+        return MLSGPU_OK;
+    }
+    void release()
+    {
+        if (p) (void) hipHostFree(p);
+        p = nullptr;
+        n = cap = 0;
+    }
+    void clear() { n = 0; }
+    size_t size() const { return n; }
+    bool empty() const { return n == 0; }
+    T *data() const { return p; }
+    const T *begin() const { return p; }
+    const T *end() const { return p + n; }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+};
 
 /* ---------------------------------------------------------------- context */
 

@@ -1741,6 +1741,14 @@ struct Readback
     U3 batchTotals;         /* lattice weld: occupied cells / vertices / indices of the batch */
 };
 
+/* ... as they lie in device memory, with the two words behind them that are no read-back */
+struct ReadbackWords : Readback
+{
+    uint32_t idle[16];      /* [0]: the word latticeTrianglesRowKernel's idle stores hit */
+    uint32_t gate[16];      /* [0]: the gate of rowTotalsKernel (zero between launches) */
+};
+static_assert(sizeof(ReadbackWords) == sizeof(Readback) + 128, "the words lie right behind the read-back");
+
 } // namespace
 
 struct mlsgpu_marching
@@ -1753,33 +1761,33 @@ struct mlsgpu_marching
     bool wideKeys = false;
     HostTables tables;
 
-    float *dField = nullptr;
-    uchar2 *dCount = nullptr;
-    ushort2 *dStart = nullptr;
-    uint8_t *dData = nullptr;
-    uint32_t *dKey = nullptr;
-    uint32_t *dCodeRec = nullptr;
-    uint64_t *dEdgeLut = nullptr;           /* latticeMaskKernel: per code byte, the lattice points a cell gives a corner */
-    uint16_t *dEdgeLut16 = nullptr;         /* latticeMaskWordKernel: the same, per (dy, dz) */
-    uint2 *dCells = nullptr, *dViStart = nullptr, *dHistogram = nullptr;
-    U3 *dTileSums3 = nullptr;
-    float4 *dVertices = nullptr;
-    void *dKeysA = nullptr, *dKeysB = nullptr;
-    uint32_t *dValsA = nullptr, *dValsB = nullptr;
-    uint32_t *dIndices = nullptr, *dIndexRemap = nullptr;
-    float *dWelded = nullptr;
-    uint64_t *dWeldedKeys = nullptr;
-    uint32_t *dHist = nullptr, *dTileSums = nullptr;
-    Readback *dReadback = nullptr;          /* device words */
-    Readback *hReadback = nullptr;          /* pinned: numWelded / firstExternal of shipOutSorted */
+    DeviceArray<float> dField;
+    DeviceArray<uchar2> dCount;
+    DeviceArray<ushort2> dStart;
+    DeviceArray<uint8_t> dData;
+    DeviceArray<uint32_t> dKey;
+    DeviceArray<uint32_t> dCodeRec;
+    DeviceArray<uint64_t> dEdgeLut;         /* latticeMaskKernel: per code byte, the lattice points a cell gives a corner */
+    DeviceArray<uint16_t> dEdgeLut16;       /* latticeMaskWordKernel: the same, per (dy, dz) */
+    DeviceArray<uint2> dCells, dViStart, dHistogram;
+    DeviceArray<U3> dTileSums3;
+    DeviceArray<float4> dVertices;
+    DeviceArray<uint64_t> dKeysA, dKeysB;   /* 32-bit keys when !wideKeys */
+    DeviceArray<uint32_t> dValsA, dValsB;
+    DeviceArray<uint32_t> dIndices, dIndexRemap;
+    DeviceArray<float> dWelded;             /* 3 per vertex */
+    DeviceArray<uint64_t> dWeldedKeys;
+    DeviceArray<uint32_t> dHist, dTileSums;
+    DeviceArray<ReadbackWords> dReadback;   /* device words */
+    PinnedArray<Readback> hReadback;        /* numWelded / firstExternal of shipOutSorted */
     HostMailbox box;                        /* the totals a host decision waits for (swathe totals, welded counts) */
-    uint2 *hHistogram = nullptr;            /* pinned, maxDepth entries (viReadback in the reference) */
+    PinnedArray<uint2> hHistogram;          /* maxDepth entries (viReadback in the reference) */
 
     /* lattice weld (single-swathe buckets) */
-    uint8_t *dCellCode = nullptr;
-    U3 *dRowCounts = nullptr, *dRowStarts = nullptr;   /* per row of cells of the swathe: (occupied, vertices, indices) */
-    LatWord *dLatWords = nullptr;
-    U3 *dLatRows = nullptr;
+    DeviceArray<uint8_t> dCellCode;
+    DeviceArray<U3> dRowCounts, dRowStarts; /* per row of cells of the swathe: (occupied, vertices, indices) */
+    DeviceArray<LatWord> dLatWords;
+    DeviceArray<U3> dLatRows;
     uint64_t latRowsMax = 0;
     uint32_t latWords = 0;
     bool legacyBuffers = true;              /* false: every bucket fits one swathe, sort path never needed */
@@ -1799,6 +1807,68 @@ struct mlsgpu_marching
     uint32_t outputIndex = 0;               /* the bucket's index in the call */
     uint32_t keyOffset[3] = {0, 0, 0};
     KeyLayout layout = {1, 1, 1};
+
+    mlsgpu_marching(uint32_t maxWidth, uint32_t maxHeight, uint32_t maxDepth, uint32_t swatheLimit, uint64_t meshMemory,
+                    const uint32_t alignment[3])
+        : maxWidth(maxWidth), maxHeight(maxHeight), maxDepth(maxDepth)
+    {
+        /* src/marching.cpp:273-284 */
+        imageWidth = roundUp(maxWidth, alignment[0]);
+        imageHeight = zStride = roundUp(maxHeight, alignment[1]);
+        maxSwathe = std::min(swatheLimit, maxDepth) / alignment[2] * alignment[2];
+        swatheCells = (uint64_t) (maxWidth - 1) * (maxHeight - 1) * maxSwathe;
+        const uint64_t meshCells = meshMemory / MLSGPU_MARCHING_MAX_CELL_BYTES;
+        vertexSpace = meshCells * MAX_CELL_VERTICES;
+        indexSpace = meshCells * MAX_CELL_INDICES;
+        /* image height imageHeight * (maxSwathe + 1) (src/marching.cpp:380-381), plus the slack a
+         * generator may write when the last swathe is padded up to its Z alignment (src/marching.h:236-237) */
+        fieldRows = (uint64_t) imageHeight * (maxSwathe + 1 + alignment[2]);
+        legacyBuffers = maxSwathe < maxDepth;           /* some bucket may need more than one swathe */
+        latRowsMax = (uint64_t) (2 * maxSwathe + 1) * (2 * maxHeight - 1);
+        latWords = (2 * maxWidth - 1 + 63) / 64;
+    }
+    ~mlsgpu_marching() { box.destroy(); }
+
+    /* Every device buffer with its element count, once: each(array, elements) until one fails.
+     * mlsgpu_hip_marching_create allocates them, mlsgpu_hip_marching_resource_usage adds them up. */
+    template<typename Each>
+    int buffers(Each each)
+    {
+        const uint64_t vs = vertexSpace, sc = swatheCells, cellRows = (uint64_t) maxSwathe * (maxHeight - 1);
+        PROPAGATE(each(dField, fieldRows * imageWidth));
+        PROPAGATE(each(dCount, 256));
+        PROPAGATE(each(dStart, 257));
+        PROPAGATE(each(dData, 8192));
+        PROPAGATE(each(dKey, 2432));
+        PROPAGATE(each(dCodeRec, 256 * 16));
+        PROPAGATE(each(dEdgeLut, 256));
+        PROPAGATE(each(dEdgeLut16, 4 * 256));
+        PROPAGATE(each(dCells, sc));
+        PROPAGATE(each(dViStart, sc));
+        PROPAGATE(each(dHistogram, maxDepth));
+        PROPAGATE(each(dTileSums3, (uint64_t) scanTiles(std::max(sc, latRowsMax)) + 1));
+        PROPAGATE(each(dCellCode, sc + 64));        /* latticeMaskWordKernel reads whole 32-byte words: up to 31 bytes behind the last row */
+        PROPAGATE(each(dRowCounts, cellRows + 1));
+        PROPAGATE(each(dRowStarts, cellRows + 1));
+        PROPAGATE(each(dLatWords, latRowsMax * latWords));
+        PROPAGATE(each(dLatRows, latRowsMax));
+        if (legacyBuffers)
+        {
+            PROPAGATE(each(dVertices, vs));         /* unwelded */
+            PROPAGATE(each(dKeysA, vs + 1));        /* sort keys and values, ping-pong */
+            PROPAGATE(each(dKeysB, vs + 1));
+            PROPAGATE(each(dValsA, vs + 1));
+            PROPAGATE(each(dValsB, vs + 1));
+            PROPAGATE(each(dIndexRemap, vs));
+            PROPAGATE(each(dHist, sortHistElems(vs) + 1));
+            PROPAGATE(each(dTileSums, (uint64_t) scanTiles(std::max<uint64_t>(sortHistElems(vs), vs)) + 1));
+        }
+        PROPAGATE(each(dIndices, indexSpace));
+        PROPAGATE(each(dWelded, vs * 3));
+        PROPAGATE(each(dWeldedKeys, vs));
+        PROPAGATE(each(dReadback, 1));
+        return MLSGPU_OK;
+    }
 
     FieldView view(const mlsgpu_swathe &sw) const { return FieldView{dField, imageWidth, sw.zStride, sw.zBias}; }
     CodeView codeView(const mlsgpu_swathe &sw) const { return CodeView{dCellCode, sw.width - 1, sw.height - 1, codeZ0}; }
@@ -1823,56 +1893,16 @@ struct mlsgpu_marching
     template<typename K> int weld(uint32_t nv, uint32_t zMax);
 };
 
-namespace
-{
-
-uint64_t marchingSizes(uint32_t maxWidth, uint32_t maxHeight, uint32_t maxDepth, uint32_t maxSwathe,
-                       uint64_t meshMemory, const uint32_t alignment[3],
-                       uint32_t *imageWidth, uint32_t *imageHeight, uint32_t *swathe,
-                       uint64_t *vertexSpace, uint64_t *indexSpace, uint64_t *swatheCells, uint64_t *fieldRows)
-{
-    /* src/marching.cpp:273-284 */
-    *imageWidth = roundUp(maxWidth, alignment[0]);
-    *imageHeight = roundUp(maxHeight, alignment[1]);
-    *swathe = std::min(maxSwathe, maxDepth) / alignment[2] * alignment[2];
-    const uint64_t sliceCells = (uint64_t) (maxWidth - 1) * (maxHeight - 1);
-    *swatheCells = sliceCells * *swathe;
-    const uint64_t meshCells = meshMemory / MLSGPU_MARCHING_MAX_CELL_BYTES;
-    *vertexSpace = meshCells * MAX_CELL_VERTICES;
-    *indexSpace = meshCells * MAX_CELL_INDICES;
-    /* image height imageHeight * (maxSwathe + 1) (src/marching.cpp:380-381), plus the slack a
-     * generator may write when the last swathe is padded up to its Z alignment (src/marching.h:236-237) */
-    *fieldRows = (uint64_t) *imageHeight * (*swathe + 1 + alignment[2]);
-    const uint64_t vs = *vertexSpace, is = *indexSpace, sc = *swatheCells;
-    const bool legacy = *swathe < maxDepth;         /* some bucket may need more than one swathe */
-    const uint64_t latRows = (uint64_t) (2 * *swathe + 1) * (2 * maxHeight - 1);
-    const uint64_t latWords = (2 * maxWidth - 1 + 63) / 64;
-    uint64_t bytes = *fieldRows * *imageWidth * 4;
-    bytes += sc * 16 + sc;                          /* cells + viStart + cell codes */
-    bytes += (uint64_t) scanTiles(std::max(sc, latRows)) * 12 + 12;    /* tile sums (U3) */
-    bytes += latRows * latWords * 16 + latRows * 28;                   /* lattice words, row counts, row info */
-    bytes += (uint64_t) *swathe * (maxHeight - 1) * 24;                /* per cell-row counts and starts */
-    if (legacy)
-    {
-        bytes += vs * 16;                           /* unwelded vertices */
-        bytes += vs * 8 * 2 + vs * 4 * 2;           /* sort keys + values, ping-pong */
-        bytes += vs * 4;                            /* indexRemap */
-        bytes += sortHistElems(vs) * 4 + (uint64_t) scanTiles(std::max(sortHistElems(vs), vs)) * 4;
-    }
-    bytes += is * 4;                                /* indices */
-    bytes += vs * 12 + vs * 8;                      /* welded vertices + keys */
-    bytes += (uint64_t) maxDepth * 8 + 512 + 1028 + 8192 + 2432 * 4;
-    return bytes;
-}
-
-} // namespace
-
 MLSGPU_API uint64_t mlsgpu_hip_marching_resource_usage(uint32_t maxWidth, uint32_t maxHeight, uint32_t maxDepth,
                                                        uint32_t maxSwathe, uint64_t meshMemory, const uint32_t alignment[3])
 {
-    uint32_t iw, ih, sw;
-    uint64_t vs, is, sc, fr;
-    return marchingSizes(maxWidth, maxHeight, maxDepth, maxSwathe, meshMemory, alignment, &iw, &ih, &sw, &vs, &is, &sc, &fr);
+    /* device memory only: the pinned read-backs and the mailbox are host memory */
+    uint64_t bytes = 0;
+    mlsgpu_marching(maxWidth, maxHeight, maxDepth, maxSwathe, meshMemory, alignment).buffers([&](auto &array, uint64_t n) {
+        bytes += array.bytes(n);
+        return MLSGPU_OK;
+    });
+    return bytes;
 }
 
 MLSGPU_API int mlsgpu_hip_marching_create(mlsgpu_ctx *ctx, uint32_t maxWidth, uint32_t maxHeight, uint32_t maxDepth,
@@ -1889,80 +1919,20 @@ MLSGPU_API int mlsgpu_hip_marching_create(mlsgpu_ctx *ctx, uint32_t maxWidth, ui
     REQUIRE(meshMemory >= (uint64_t) (maxWidth - 1) * (maxHeight - 1) * MLSGPU_MARCHING_MAX_CELL_BYTES, MLSGPU_ERR_INVALID);
     HIP_CHECK(hipSetDevice(ctx->device));
 
-    mlsgpu_marching *m = new mlsgpu_marching;
+    std::unique_ptr<mlsgpu_marching> m(new mlsgpu_marching(maxWidth, maxHeight, maxDepth, maxSwathe, meshMemory, alignment));
     m->ctx = ctx;
-    m->maxWidth = maxWidth; m->maxHeight = maxHeight; m->maxDepth = maxDepth;
-    marchingSizes(maxWidth, maxHeight, maxDepth, maxSwathe, meshMemory, alignment, &m->imageWidth, &m->imageHeight,
-                  &m->maxSwathe, &m->vertexSpace, &m->indexSpace, &m->swatheCells, &m->fieldRows);
-    m->zStride = m->imageHeight;
     if (m->vertexSpace >= (uint64_t(1) << 32) || m->indexSpace >= (uint64_t(1) << 32))
-    {
-        delete m;
         return setError(MLSGPU_ERR_LENGTH, "Marching: meshMemory gives more than 2^32 vertices or indices");
-    }
     if (m->swatheCells >= (uint64_t(1) << 32))
-    {
-        delete m;
         return setError(MLSGPU_ERR_LENGTH, "Marching: more than 2^32 cells per swathe");
-    }
     makeTables(m->tables);
     assert(m->tables.data.size() == 8192 && m->tables.key.size() == 2432 * 3);    /* src/marching.cpp:248-251 */
 
-    int rc = MLSGPU_OK;
-    auto alloc = [&](void **p, uint64_t bytes) {
-        if (rc == MLSGPU_OK && hipMalloc(p, bytes ? bytes : 4) != hipSuccess)
-            rc = setError(MLSGPU_ERR_NOMEM, "Marching: cannot allocate %llu bytes", (unsigned long long) bytes);
-    };
-    const uint64_t vs = m->vertexSpace, is = m->indexSpace, sc = m->swatheCells;
-    alloc((void **) &m->dField, m->fieldRows * m->imageWidth * 4);
-    alloc((void **) &m->dCount, 512);
-    alloc((void **) &m->dStart, 257 * 4);
-    alloc((void **) &m->dData, 8192);
-    alloc((void **) &m->dKey, 2432 * 4);
-    alloc((void **) &m->dCodeRec, 256 * 16 * 4);
-    alloc((void **) &m->dEdgeLut, 256 * 8);
-    alloc((void **) &m->dEdgeLut16, 4 * 256 * 2);
-    alloc((void **) &m->dCells, sc * 8);
-    alloc((void **) &m->dViStart, sc * 8);
-    alloc((void **) &m->dHistogram, (uint64_t) maxDepth * 8);
-    m->legacyBuffers = m->maxSwathe < maxDepth;
-    m->latRowsMax = (uint64_t) (2 * m->maxSwathe + 1) * (2 * maxHeight - 1);
-    m->latWords = (2 * maxWidth - 1 + 63) / 64;
-    alloc((void **) &m->dTileSums3, ((uint64_t) scanTiles(std::max(sc, m->latRowsMax)) + 1) * sizeof(U3));
-    alloc((void **) &m->dCellCode, sc + 64);        /* latticeMaskWordKernel reads whole 32-byte words: up to 31 bytes behind the last row */
-    alloc((void **) &m->dRowCounts, ((uint64_t) m->maxSwathe * (maxHeight - 1) + 1) * sizeof(U3));
-    alloc((void **) &m->dRowStarts, ((uint64_t) m->maxSwathe * (maxHeight - 1) + 1) * sizeof(U3));
-    alloc((void **) &m->dLatWords, m->latRowsMax * m->latWords * sizeof(LatWord));
-    alloc((void **) &m->dLatRows, m->latRowsMax * sizeof(U3));
-    if (m->legacyBuffers)
-    {
-        alloc((void **) &m->dVertices, vs * 16);
-        alloc(&m->dKeysA, (vs + 1) * 8);
-        alloc(&m->dKeysB, (vs + 1) * 8);
-        alloc((void **) &m->dValsA, (vs + 1) * 4);
-        alloc((void **) &m->dValsB, (vs + 1) * 4);
-        alloc((void **) &m->dIndexRemap, vs * 4);
-        alloc((void **) &m->dHist, (sortHistElems(vs) + 1) * 4);
-        alloc((void **) &m->dTileSums, ((uint64_t) scanTiles(std::max(sortHistElems(vs), vs)) + 1) * 4);
-    }
-    alloc((void **) &m->dIndices, is * 4);
-    alloc((void **) &m->dWelded, vs * 12);
-    alloc((void **) &m->dWeldedKeys, vs * 8);
-    /* + the word latticeTrianglesRowKernel's idle stores hit, + the gate of rowTotalsKernel (zero between launches) */
-    alloc((void **) &m->dReadback, sizeof(Readback) + 128);
-    if (rc == MLSGPU_OK && hipMemset(m->dReadback, 0, sizeof(Readback) + 128) != hipSuccess)
-        rc = setError(MLSGPU_ERR_HIP, "Marching: cannot clear the read-back words");
-    if (rc == MLSGPU_OK && hipHostMalloc((void **) &m->hReadback, sizeof(Readback)) != hipSuccess)
-        rc = setError(MLSGPU_ERR_NOMEM, "Marching: cannot allocate pinned readback");
-    if (rc == MLSGPU_OK && hipHostMalloc((void **) &m->hHistogram, (uint64_t) maxDepth * 8) != hipSuccess)
-        rc = setError(MLSGPU_ERR_NOMEM, "Marching: cannot allocate pinned histogram");
-    if (rc == MLSGPU_OK)
-        rc = m->box.create();
-    if (rc != MLSGPU_OK)
-    {
-        mlsgpu_hip_marching_destroy(m);
-        return rc;
-    }
+    PROPAGATE(m->buffers([](auto &array, uint64_t n) { return array.alloc(n); }));
+    HIP_CHECK(hipMemset(m->dReadback, 0, sizeof(ReadbackWords)));
+    PROPAGATE(m->hReadback.alloc(1));
+    PROPAGATE(m->hHistogram.alloc(maxDepth));
+    PROPAGATE(m->box.create());
     /* upload the tables */
     std::vector<uint32_t> packedKey(2432);
     for (int i = 0; i < 2432; i++)
@@ -2000,11 +1970,8 @@ MLSGPU_API int mlsgpu_hip_marching_create(mlsgpu_ctx *ctx, uint32_t maxWidth, ui
     if (e == hipSuccess) e = hipMemcpy(m->dData, m->tables.data.data(), 8192, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(m->dKey, packedKey.data(), 2432 * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess)
-    {
-        mlsgpu_hip_marching_destroy(m);
         return setError(MLSGPU_ERR_HIP, "Marching: table upload failed: %s", hipGetErrorString(e));
-    }
-    *out = m;
+    *out = m.release();
     return MLSGPU_OK;
 }
 
@@ -2013,16 +1980,6 @@ MLSGPU_API void mlsgpu_hip_marching_destroy(mlsgpu_marching *m)
     if (!m)
         return;
     hipSetDevice(m->ctx->device);
-    hipFree(m->dField); hipFree(m->dCount); hipFree(m->dStart); hipFree(m->dData); hipFree(m->dKey); hipFree(m->dCodeRec); hipFree(m->dEdgeLut); hipFree(m->dEdgeLut16);
-    hipFree(m->dCells); hipFree(m->dViStart); hipFree(m->dHistogram); hipFree(m->dTileSums3);
-    hipFree(m->dVertices); hipFree(m->dKeysA); hipFree(m->dKeysB); hipFree(m->dValsA); hipFree(m->dValsB);
-    hipFree(m->dIndices); hipFree(m->dIndexRemap); hipFree(m->dWelded); hipFree(m->dWeldedKeys);
-    hipFree(m->dHist); hipFree(m->dTileSums); hipFree(m->dReadback);
-    hipFree(m->dCellCode); hipFree(m->dRowCounts); hipFree(m->dRowStarts);
-    hipFree(m->dLatWords); hipFree(m->dLatRows);
-    if (m->hReadback) hipHostFree(m->hReadback);
-    if (m->hHistogram) hipHostFree(m->hHistogram);
-    m->box.destroy();
     delete m;
 }
 
@@ -2037,7 +1994,7 @@ static int rowTotalsLanes(mlsgpu_marching *const *ms, const mlsgpu_swathe *sws, 
         const uint64_t rows = cw > 0 ? (uint64_t) ch * (sw.zLast - sw.zFirst) : 0;
         return RowTotalsArgs{ms[k]->dRowCounts + (uint64_t) (sw.zFirst - ms[k]->codeZ0) * ch, rows, &ms[k]->dReadback->totals};
     });
-    uint32_t *const gate = reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(m0->dReadback) + sizeof(Readback) + 64);
+    uint32_t *const gate = m0->dReadback->gate;
     const uint32_t seq = m0->box.reserve();
     LAUNCH(m0->ctx, "kernel.marching.genOccupied.time", rowTotalsKernel, dim3(count), dim3(1024), rt, count, gate, m0->box.dev, seq);
     PROPAGATE(m0->box.wait(m0->ctx->stream));                /* the reference's queue.finish(), :548 */
@@ -2082,7 +2039,7 @@ int mlsgpu_marching::sliceHistogram(const mlsgpu_swathe &sw)
 template<typename K>
 int mlsgpu_marching::weld(uint32_t nv, uint32_t zMax)
 {
-    K *keysA = static_cast<K *>(dKeysA), *keysB = static_cast<K *>(dKeysB);
+    K *keysA = reinterpret_cast<K *>(dKeysA.get()), *keysB = reinterpret_cast<K *>(dKeysB.get());
     SortResult<K> sorted;
     PROPAGATE(radixSort<K>(ctx, "kernel.marching.sortVertices.time", keysA, dValsA, keysB, dValsB, nv, layout.bits(),
                            true, dHist, dTileSums, &sorted));
@@ -2318,7 +2275,7 @@ static int shipOutLatticeLanes(ShipLane *lanes, uint32_t count)
             const auto A = packLanes<LatticeTrianglesRowArgs>(nr, [&](uint32_t j) {
                 const Rec &r = *byRows[j];
                 return LatticeTrianglesRowArgs{r.L, r.C, r.m->devTables(), r.firstRow, (const U3 *) r.m->dRowStarts, r.ship->zTop,
-                                               r.m->dIndices, r.cellRows, (uint32_t *) (r.m->dReadback + 1)};
+                                               r.m->dIndices, r.cellRows, r.m->dReadback->idle};
             });
             const uint32_t most = mostOfLanes(nr, [&](uint32_t j) { return byRows[j]->cellRows; });
             const uint32_t nwMax = mostOfLanes(nr, [&](uint32_t j) { return byRows[j]->L.nw; });
@@ -2468,12 +2425,12 @@ int mlsgpu_marching::addSlices(const mlsgpu_swathe &swathe, const U3 &totals)
                 const dim3 grid(divUp(compacted, 256)), block(256);
                 if (wideKeys)
                     LAUNCH(ctx, "kernel.marching.generateElements.time", (generateElementsKernel<uint64_t>), grid, block,
-                           dVertices, static_cast<uint64_t *>(dKeysA), dIndices, (const uint2 *) dViStart, (const uint2 *) dCells,
+                           dVertices, dKeysA.get(), dIndices, (const uint2 *) dViStart, (const uint2 *) dCells,
                            view(swathe), devTables(), keyOffset[0], keyOffset[1], keyOffset[2], top[0], top[1], top[2],
                            layout, compacted);
                 else
                     LAUNCH(ctx, "kernel.marching.generateElements.time", (generateElementsKernel<uint32_t>), grid, block,
-                           dVertices, static_cast<uint32_t *>(dKeysA), dIndices, (const uint2 *) dViStart, (const uint2 *) dCells,
+                           dVertices, reinterpret_cast<uint32_t *>(dKeysA.get()), dIndices, (const uint2 *) dViStart, (const uint2 *) dCells,
                            view(swathe), devTables(), keyOffset[0], keyOffset[1], keyOffset[2], top[0], top[1], top[2],
                            layout, compacted);
             }
@@ -2757,13 +2714,12 @@ MLSGPU_API int mlsgpu_hip_test_compute_key(mlsgpu_ctx *ctx, const uint32_t c[3],
 {
     REQUIRE(ctx != nullptr && out != nullptr, MLSGPU_ERR_INVALID);
     HIP_CHECK(hipSetDevice(ctx->device));
-    uint64_t *d = nullptr;
-    HIP_CHECK(hipMalloc(&d, 8));
-    hipLaunchKernelGGL(computeKeyTestKernel, dim3(1), dim3(1), 0, ctx->stream, c[0], c[1], c[2], top[0], top[1], top[2], d);
+    DeviceArray<uint64_t> d;
+    PROPAGATE(d.alloc(1));
+    hipLaunchKernelGGL(computeKeyTestKernel, dim3(1), dim3(1), 0, ctx->stream, c[0], c[1], c[2], top[0], top[1], top[2], d.get());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(out, d, 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    hipFree(d);
     return MLSGPU_OK;
 }
 

@@ -479,34 +479,28 @@ __global__ void applyVerdictKernel(const uint32_t *rootId, const uint8_t *keep, 
 template<typename T>
 struct Arena
 {
-    T *ptr = nullptr;
-    uint64_t used = 0, cap = 0;
+    DeviceArray<T> ptr;
+    uint64_t used = 0;
+    uint64_t cap() const { return ptr.capacity(); }
 
     /* the mesher's device must be current; `stream` is one of its streams */
     int reserve(hipStream_t stream, uint64_t need)
     {
-        if (need <= cap)
+        if (need <= cap())
             return MLSGPU_OK;
-        const uint64_t newCap = std::max<uint64_t>(need, cap + cap / 2 + 1024);
-        T *np = nullptr;
-        HIP_CHECK(hipMalloc((void **) &np, newCap * sizeof(T)));
+        DeviceArray<T> grown;
+        PROPAGATE(grown.alloc(std::max<uint64_t>(need, cap() + cap() / 2 + 1024)));
         if (used > 0)
         {
-            hipError_t e = hipMemcpyAsync(np, ptr, used * sizeof(T), hipMemcpyDeviceToDevice, stream);
+            hipError_t e = hipMemcpyAsync(grown, ptr, used * sizeof(T), hipMemcpyDeviceToDevice, stream);
             if (e == hipSuccess)
                 e = hipStreamSynchronize(stream);
             if (e != hipSuccess)
-            {
-                hipFree(np);
                 return setError(MLSGPU_ERR_HIP, "mesher: arena move failed: %s", hipGetErrorString(e));
-            }
         }
-        hipFree(ptr);
-        ptr = np;
-        cap = newCap;
+        ptr = std::move(grown);         /* the old buffer goes with `grown` */
         return MLSGPU_OK;
     }
-    ~Arena() { hipFree(ptr); }
 };
 
 } // namespace
@@ -572,8 +566,8 @@ struct mlsgpu_mesher
     uint64_t cacheDims[3] = {0, 0, 0};
     uint32_t cacheRootCount = 0;
     /* results */
-    float *outVertices = nullptr;
-    uint32_t *outTriangles = nullptr;
+    DeviceArray<float> outVertices;             /* 3 per vertex */
+    DeviceArray<uint32_t> outTriangles;         /* 3 per triangle */
     std::vector<uint64_t> chunkVStart, chunkTStart;     /* [chunks + 1] */
     std::vector<uint32_t> outChunks;                    /* dense chunk indices that have triangles */
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -581,74 +575,24 @@ struct mlsgpu_mesher
     bool analyzed = false;
     /* the export's keys and their roots land in PINNED memory (tens of MB: a copy into pageable memory goes through the
      * runtime's staging buffers and took anything from 5 to 80 ms) */
-    template<typename T>
-    struct PinnedArray
-    {
-        T *p = nullptr;
-        size_t n = 0, cap = 0;
-        ~PinnedArray() { if (p) hipHostFree(p); }
-        int resize(size_t count)
-        {
-            if (count > cap)
-            {
-                if (p) hipHostFree(p);
-                p = nullptr;
-                cap = 0;
-                const size_t want = count + count / 4 + 1024;
-                if (hipHostMalloc((void **) &p, want * sizeof(T)) != hipSuccess)
-                    return setError(MLSGPU_ERR_NOMEM, "mesher: cannot allocate %zu bytes of pinned export buffer", want * sizeof(T));
-                cap = want;
-            }
-            n = count;
-            return MLSGPU_OK;
-        }
-        void clear() { n = 0; }
-        size_t size() const { return n; }
-        bool empty() const { return n == 0; }
-        T *data() { return p; }
-        const T *begin() const { return p; }
-        const T *end() const { return p + n; }
-    };
     PinnedArray<uint64_t> bKeys;
     PinnedArray<uint32_t> bKeyRoot;
     std::vector<uint64_t> bRootVertices, bRootTriangles;
 
     /* kept between finalize calls; grown on demand (or up front by reserve) */
-    void *slab = nullptr;
-    uint64_t slabCap = 0;
-    uint64_t outVCap = 0, outTCap = 0;
+    DeviceArray<char> slab;
 
     int ensureSlab(uint64_t bytes)
     {
-        if (bytes <= slabCap)
+        if (bytes <= slab.capacity())
             return MLSGPU_OK;
         cacheKind = 0;          /* whatever an analysis left in the old slab is gone */
-        hipFree(slab);
-        slab = nullptr;
-        slabCap = 0;
-        HIP_CHECK(hipMalloc(&slab, bytes));
-        slabCap = bytes;
-        return MLSGPU_OK;
+        return slab.reserve(bytes);
     }
     int ensureOutputs(uint64_t nv, uint64_t nt)
     {
-        if (outVCap < nv)
-        {
-            hipFree(outVertices);
-            outVertices = nullptr;
-            outVCap = 0;
-            HIP_CHECK(hipMalloc((void **) &outVertices, std::max<uint64_t>(3 * nv, 1) * sizeof(float)));
-            outVCap = nv;
-        }
-        if (outTCap < nt)
-        {
-            hipFree(outTriangles);
-            outTriangles = nullptr;
-            outTCap = 0;
-            HIP_CHECK(hipMalloc((void **) &outTriangles, std::max<uint64_t>(3 * nt, 1) * sizeof(uint32_t)));
-            outTCap = nt;
-        }
-        return MLSGPU_OK;
+        PROPAGATE(outVertices.reserve(std::max<uint64_t>(3 * nv, 1)));
+        return outTriangles.reserve(std::max<uint64_t>(3 * nt, 1));
     }
     /* a stream of the mesher's own: add() is called from worker threads whose contexts (and devices) differ, and the
      * mesher's context belongs to the thread that finalizes; everything on it runs under the mutex */
@@ -697,9 +641,6 @@ struct mlsgpu_mesher
     int finalizeImpl(uint32_t *numChunks, bool analyzeOnly, const uint8_t *keepRoots, uint64_t numRoots);
     ~mlsgpu_mesher()
     {
-        hipFree(outVertices);
-        hipFree(outTriangles);
-        hipFree(slab);
         if (addStream) hipStreamDestroy(addStream);
         drainPending();
         for (auto &e : eventPool)
@@ -745,8 +686,8 @@ MLSGPU_API int mlsgpu_hip_mesher_reserve(mlsgpu_mesher *m, uint64_t numVertices,
     PROPAGATE(m->ensureAddStream());
     /* an arena that grows moves (copy on addStream, old buffer freed): same-device appends may still be running on their
      * producers' streams, so they must have landed first -- the rule mlsgpu_hip_mesher_add follows before it grows one */
-    if (3 * numVertices > m->vertices.cap || 3 * numTriangles > m->triangles.cap || numExternal > m->extKeys.cap
-        || numExternal > m->extGid.cap || numExternal > m->extChunk.cap)
+    if (3 * numVertices > m->vertices.cap() || 3 * numTriangles > m->triangles.cap() || numExternal > m->extKeys.cap()
+        || numExternal > m->extGid.cap() || numExternal > m->extChunk.cap())
         PROPAGATE(m->drainPending());
     PROPAGATE(m->vertices.reserve(m->addStream, 3 * numVertices));
     PROPAGATE(m->triangles.reserve(m->addStream, 3 * numTriangles));
@@ -790,8 +731,8 @@ MLSGPU_API int mlsgpu_hip_mesher_add(mlsgpu_mesher *m, mlsgpu_ctx *from, uint64_
     const uint64_t nv = mesh->numVertices, nt = mesh->numTriangles, ne = nv - mesh->numInternalVertices;
     REQUIRE(m->vertices.used / 3 + nv < (uint64_t(1) << 32), MLSGPU_ERR_LENGTH);
     /* an arena that has to grow moves: every earlier append must have landed first (reserve() up front avoids both) */
-    if (m->vertices.used + 3 * nv > m->vertices.cap || m->triangles.used + 3 * nt > m->triangles.cap
-        || m->extKeys.used + ne > m->extKeys.cap || m->extGid.used + ne > m->extGid.cap || m->extChunk.used + ne > m->extChunk.cap)
+    if (m->vertices.used + 3 * nv > m->vertices.cap() || m->triangles.used + 3 * nt > m->triangles.cap()
+        || m->extKeys.used + ne > m->extKeys.cap() || m->extGid.used + ne > m->extGid.cap() || m->extChunk.used + ne > m->extChunk.cap())
         PROPAGATE(m->drainPending());
     PROPAGATE(m->vertices.reserve(m->addStream, m->vertices.used + 3 * nv));
     PROPAGATE(m->triangles.reserve(m->addStream, m->triangles.used + 3 * nt));
@@ -933,11 +874,11 @@ int mlsgpu_mesher::regroupByChunk()
     Arena<float> nVertices;
     Arena<uint32_t> nTriangles, nGid, nChunk;
     Arena<uint64_t> nKeys;
-    PROPAGATE(nVertices.reserve(addStream, std::max<uint64_t>(vertices.cap, 1)));
-    PROPAGATE(nTriangles.reserve(addStream, std::max<uint64_t>(triangles.cap, 1)));
-    PROPAGATE(nKeys.reserve(addStream, std::max<uint64_t>(extKeys.cap, 1)));
-    PROPAGATE(nGid.reserve(addStream, std::max<uint64_t>(extGid.cap, 1)));
-    PROPAGATE(nChunk.reserve(addStream, std::max<uint64_t>(extChunk.cap, 1)));
+    PROPAGATE(nVertices.reserve(addStream, std::max<uint64_t>(vertices.cap(), 1)));
+    PROPAGATE(nTriangles.reserve(addStream, std::max<uint64_t>(triangles.cap(), 1)));
+    PROPAGATE(nKeys.reserve(addStream, std::max<uint64_t>(extKeys.cap(), 1)));
+    PROPAGATE(nGid.reserve(addStream, std::max<uint64_t>(extGid.cap(), 1)));
+    PROPAGATE(nChunk.reserve(addStream, std::max<uint64_t>(extChunk.cap(), 1)));
     std::vector<MeshRecord> moved;
     for (uint32_t idx : order)
     {
@@ -973,11 +914,11 @@ int mlsgpu_mesher::regroupByChunk()
     }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(addStream));
-    std::swap(vertices.ptr, nVertices.ptr);   std::swap(vertices.cap, nVertices.cap);
-    std::swap(triangles.ptr, nTriangles.ptr); std::swap(triangles.cap, nTriangles.cap);
-    std::swap(extKeys.ptr, nKeys.ptr);        std::swap(extKeys.cap, nKeys.cap);
-    std::swap(extGid.ptr, nGid.ptr);          std::swap(extGid.cap, nGid.cap);
-    std::swap(extChunk.ptr, nChunk.ptr);      std::swap(extChunk.cap, nChunk.cap);
+    std::swap(vertices.ptr, nVertices.ptr);
+    std::swap(triangles.ptr, nTriangles.ptr);
+    std::swap(extKeys.ptr, nKeys.ptr);
+    std::swap(extGid.ptr, nGid.ptr);
+    std::swap(extChunk.ptr, nChunk.ptr);
     blocks.swap(moved);
     return MLSGPU_OK;
 }
@@ -1031,13 +972,13 @@ int mlsgpu_mesher::finalizeImpl(uint32_t *numChunks, bool analyzeOnly, const uin
         return MLSGPU_OK;
     }
     {
-        const void *const slabBefore = m->slab;
+        const uint64_t slabBefore = m->slab.capacity();
         PROPAGATE(m->ensureSlab(scratchBytes(nv, nt, ne, nb, nc)));
-        if (m->slab != slabBefore)
+        if (m->slab.capacity() != slabBefore)
             reuse = reuseDense = false;         /* (cannot happen for unchanged arenas; the cached analysis lived there) */
     }
     PROPAGATE(m->ensureOutputs(nv, nt));
-    Scratch S(m->slab, m->slabCap);
+    Scratch S(m->slab, m->slab.capacity());
     uint32_t *compRep, *outRep, *parent, *root, *size, *vIndex;
     PROPAGATE(S.get(&compRep, nv));
     PROPAGATE(S.get(&outRep, nv));
@@ -1428,26 +1369,23 @@ MLSGPU_API int mlsgpu_hip_mesher_write_ply(mlsgpu_mesher *m, uint32_t i, const c
         bufferBytes = uint64_t(64) << 20;
     /* a piece holds whole 12-byte vertices and whole 13-byte faces */
     const uint64_t piece = std::max<uint64_t>(bufferBytes / 2 / 156, 1) * 156;
-    uint8_t *pinned[2] = {nullptr, nullptr}, *dPack = nullptr;
+    PinnedArray<uint8_t> pinned[2];
+    DeviceArray<uint8_t> dPack;
     hipEvent_t done[2] = {nullptr, nullptr};
     FILE *f = nullptr;
     int rc = MLSGPU_OK;
     auto cleanup = [&]()
     {
         for (int k = 0; k < 2; k++)
-        {
-            if (pinned[k]) hipHostFree(pinned[k]);
             if (done[k]) hipEventDestroy(done[k]);
-        }
-        hipFree(dPack);
         if (f != nullptr)
             std::fclose(f);
     };
     for (int k = 0; k < 2 && rc == MLSGPU_OK; k++)
-        if (hipHostMalloc((void **) &pinned[k], piece) != hipSuccess || hipEventCreateWithFlags(&done[k], hipEventDisableTiming) != hipSuccess)
-            rc = setError(MLSGPU_ERR_NOMEM, "mesher: cannot allocate %llu bytes of pinned write buffer", (unsigned long long) piece);
-    if (rc == MLSGPU_OK && hipMalloc((void **) &dPack, 2 * piece) != hipSuccess)
-        rc = setError(MLSGPU_ERR_NOMEM, "mesher: cannot allocate the face packing buffer");
+        if ((rc = pinned[k].alloc(piece)) == MLSGPU_OK && hipEventCreateWithFlags(&done[k], hipEventDisableTiming) != hipSuccess)
+            rc = setError(MLSGPU_ERR_HIP, "mesher: cannot create an event");
+    if (rc == MLSGPU_OK)
+        rc = dPack.alloc(2 * piece);
     if (rc == MLSGPU_OK && (f = std::fopen(path, "wb")) == nullptr)
         rc = setError(MLSGPU_ERR_INVALID, "cannot open %s for writing", path);
     if (rc != MLSGPU_OK)

@@ -1487,16 +1487,15 @@ __global__ void testMlsKernel(int op, const float *in, uint32_t n, float *out)
 
 int runMlsTest(mlsgpu_ctx *ctx, int op, const float *in, size_t inFloats, uint32_t n, float *out, int outFloats)
 {
-    float *dIn = nullptr, *dOut = nullptr;
+    DeviceArray<float> dIn, dOut;
     HIP_CHECK(hipSetDevice(ctx->device));
-    HIP_CHECK(hipMalloc(&dIn, inFloats * 4 + 4));
-    HIP_CHECK(hipMalloc(&dOut, 32));
+    PROPAGATE(dIn.alloc(inFloats + 1));
+    PROPAGATE(dOut.alloc(8));
     HIP_CHECK(hipMemcpyAsync(dIn, in, inFloats * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(testMlsKernel, dim3(1), dim3(1), 0, ctx->stream, op, (const float *) dIn, n, dOut);
+    hipLaunchKernelGGL(testMlsKernel, dim3(1), dim3(1), 0, ctx->stream, op, (const float *) dIn, n, dOut.get());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(out, dOut, outFloats * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    hipFree(dIn); hipFree(dOut);
     return MLSGPU_OK;
 }
 } // namespace

@@ -31,17 +31,51 @@ struct mlsgpu_tree
     uint64_t maxLevels = 0, maxSplats = 0;
     uint64_t maxStart = 0, commandsSize = 0;
     uint32_t numLevels = 0;
-    int32_t *dStart = nullptr, *dJumpPos = nullptr, *dCommands = nullptr;
-    uint32_t *dKeysA = nullptr, *dKeysB = nullptr, *dValsA = nullptr, *dValsB = nullptr;
-    uint32_t *dHist = nullptr, *dTileSums = nullptr, *dNumEntries = nullptr;
-    uint32_t *dNodeCounts = nullptr, *dNodeBase = nullptr;     /* per node: entries, and twice the non-empty nodes before it */
-    uint32_t *dDigitBase = nullptr;     /* 257 words: where the groups of the fused first pass begin (packed entries) */
-    U3 *dNodeTiles = nullptr;           /* tile sums of the scan over the nodes */
+    DeviceArray<int32_t> dStart, dJumpPos, dCommands;
+    DeviceArray<uint32_t> dKeysA, dKeysB, dValsA, dValsB;
+    DeviceArray<uint32_t> dHist, dTileSums, dNumEntries;
+    DeviceArray<uint32_t> dNodeCounts, dNodeBase;   /* per node: entries, and twice the non-empty nodes before it */
+    DeviceArray<uint32_t> dDigitBase;   /* 257 words: where the groups of the fused first pass begin (packed entries) */
+    DeviceArray<U3> dNodeTiles;         /* tile sums of the scan over the nodes */
     HostMailbox entryBox;               /* the entry count comes back to the host once per build */
-    uint8_t *dSlotMasks = nullptr;      /* per splat: which of its 8 candidate slots are real entries */
-    uint64_t *dEntryNotes = nullptr;    /* per splat, the fused front end: slot mask, level, node coordinates (packNote) */
+    DeviceArray<uint8_t> dSlotMasks;    /* per splat: which of its 8 candidate slots are real entries */
+    DeviceArray<uint64_t> dEntryNotes;  /* per splat, the fused front end: slot mask, level, node coordinates (packNote) */
     mlsgpu_splat *dSplats = nullptr;   /* borrowed between build and clear_splats */
     bool mutate = true;                 /* radius -> 1/radius^2 in place (the reference); false: the splats stay as they came */
+
+    mlsgpu_tree(uint64_t maxLevels, uint64_t maxSplats) : maxLevels(maxLevels), maxSplats(maxSplats)
+    {
+        /* src/splat_tree_cl.cpp:112-123 */
+        maxStart = (uint64_t(1) << (3 * maxLevels)) / 7;
+        commandsSize = maxSplats * 8 + std::min(maxStart, 8 * maxSplats) * 2;
+    }
+    ~mlsgpu_tree() { entryBox.destroy(); }
+
+    /* Every device buffer of the tree with its element count, once: each(array, elements) until one fails.
+     * mlsgpu_hip_tree_create allocates them, mlsgpu_hip_tree_resource_usage adds them up. */
+    template<typename Each>
+    int buffers(Each each)
+    {
+        const uint64_t entries = maxSplats * 8;
+        const uint64_t histElems = sortHistElems(entries);
+        PROPAGATE(each(dStart, maxStart));
+        PROPAGATE(each(dJumpPos, maxStart));
+        PROPAGATE(each(dCommands, commandsSize));
+        PROPAGATE(each(dKeysA, entries));
+        PROPAGATE(each(dKeysB, entries));
+        PROPAGATE(each(dValsA, entries));
+        PROPAGATE(each(dValsB, entries));
+        PROPAGATE(each(dHist, histElems));
+        PROPAGATE(each(dTileSums, (uint64_t) scanTiles(std::max(histElems, entries)) + 1));
+        PROPAGATE(each(dNumEntries, 1));
+        PROPAGATE(each(dSlotMasks, maxSplats));
+        PROPAGATE(each(dEntryNotes, maxSplats));
+        PROPAGATE(each(dNodeCounts, maxStart));
+        PROPAGATE(each(dNodeBase, maxStart));
+        PROPAGATE(each(dDigitBase, 257));
+        PROPAGATE(each(dNodeTiles, (uint64_t) scanTiles(maxStart) + 1));
+        return MLSGPU_OK;
+    }
 };
 
 namespace
@@ -704,20 +738,19 @@ __global__ void testHelpersKernel(int op, const int32_t *iargs, const float *far
 
 int runTestHelper(mlsgpu_ctx *ctx, int op, const int32_t *iargs, int ni, const float *fargs, int nf, uint32_t *out)
 {
-    int32_t *dI = nullptr;
-    float *dF = nullptr;
-    uint32_t *dO = nullptr;
+    DeviceArray<int32_t> dI;
+    DeviceArray<float> dF;
+    DeviceArray<uint32_t> dO;
     HIP_CHECK(hipSetDevice(ctx->device));
-    HIP_CHECK(hipMalloc(&dI, 64));
-    HIP_CHECK(hipMalloc(&dF, 64));
-    HIP_CHECK(hipMalloc(&dO, 16));
+    PROPAGATE(dI.alloc(16));
+    PROPAGATE(dF.alloc(16));
+    PROPAGATE(dO.alloc(4));
     if (ni) HIP_CHECK(hipMemcpyAsync(dI, iargs, ni * 4, hipMemcpyHostToDevice, ctx->stream));
     if (nf) HIP_CHECK(hipMemcpyAsync(dF, fargs, nf * 4, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(testHelpersKernel, dim3(1), dim3(1), 0, ctx->stream, op, (const int32_t *) dI, (const float *) dF, dO);
+    hipLaunchKernelGGL(testHelpersKernel, dim3(1), dim3(1), 0, ctx->stream, op, (const int32_t *) dI, (const float *) dF, dO.get());
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(out, dO, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    hipFree(dI); hipFree(dF); hipFree(dO);
     return MLSGPU_OK;
 }
 
@@ -725,23 +758,15 @@ int runTestHelper(mlsgpu_ctx *ctx, int op, const int32_t *iargs, int ni, const f
 
 /* ------------------------------------------------------------------ C-ABI */
 
-static void treeSizes(uint64_t maxLevels, uint64_t maxSplats, uint64_t *maxStart, uint64_t *commandsSize)
-{
-    /* src/splat_tree_cl.cpp:112-123 */
-    *maxStart = (uint64_t(1) << (3 * maxLevels)) / 7;
-    const uint64_t maxRanges = *maxStart < 8 * maxSplats ? *maxStart : 8 * maxSplats;
-    *commandsSize = maxSplats * 8 + maxRanges * 2;
-}
-
+/* device memory only: the entry mailbox is pinned host memory */
 MLSGPU_API uint64_t mlsgpu_hip_tree_resource_usage(uint64_t maxLevels, uint64_t maxSplats)
 {
-    uint64_t maxStart, commandsSize;
-    treeSizes(maxLevels, maxSplats, &maxStart, &commandsSize);
-    const uint64_t entries = maxSplats * 8;
-    /* start, jumpPos, node counts and bases; commands; keys and values x2; histogram, tile sums; slot masks; node tiles */
-    return maxStart * 4 * 4 + commandsSize * 4 + entries * 4 * 4
-        + sortHistElems(entries) * 4 + ((uint64_t) scanTiles(sortHistElems(entries) > entries ? sortHistElems(entries) : entries) + 1) * 4
-        + 4 + maxSplats * 9 + ((uint64_t) scanTiles(maxStart) + 1) * sizeof(U3);
+    uint64_t bytes = 0;
+    mlsgpu_tree(maxLevels, maxSplats).buffers([&](auto &array, uint64_t n) {
+        bytes += array.bytes(n);
+        return MLSGPU_OK;
+    });
+    return bytes;
 }
 
 MLSGPU_API int mlsgpu_hip_tree_create(mlsgpu_ctx *ctx, uint64_t maxLevels, uint64_t maxSplats, mlsgpu_tree **out)
@@ -750,43 +775,11 @@ MLSGPU_API int mlsgpu_hip_tree_create(mlsgpu_ctx *ctx, uint64_t maxLevels, uint6
     REQUIRE(1 <= maxSplats && maxSplats <= MLSGPU_TREE_MAX_SPLATS, MLSGPU_ERR_LENGTH);   /* src/splat_tree_cl.cpp:106 */
     REQUIRE(1 <= maxLevels && maxLevels <= MLSGPU_TREE_MAX_LEVELS, MLSGPU_ERR_LENGTH);   /* :107 */
     HIP_CHECK(hipSetDevice(ctx->device));
-    mlsgpu_tree *t = new mlsgpu_tree;
+    std::unique_ptr<mlsgpu_tree> t(new mlsgpu_tree(maxLevels, maxSplats));
     t->ctx = ctx;
-    t->maxLevels = maxLevels;
-    t->maxSplats = maxSplats;
-    treeSizes(maxLevels, maxSplats, &t->maxStart, &t->commandsSize);
-    const uint64_t entries = maxSplats * 8;
-    const uint64_t histElems = sortHistElems(entries);
-    const uint64_t tileSums = scanTiles(histElems > entries ? histElems : entries) + 1;
-    int rc = MLSGPU_OK;
-    auto alloc = [&](void **p, uint64_t bytes) {
-        if (rc == MLSGPU_OK && hipMalloc(p, bytes ? bytes : 4) != hipSuccess)
-            rc = setError(MLSGPU_ERR_NOMEM, "SplatTreeCL: cannot allocate %llu bytes", (unsigned long long) bytes);
-    };
-    alloc((void **) &t->dStart, t->maxStart * 4);
-    alloc((void **) &t->dJumpPos, t->maxStart * 4);
-    alloc((void **) &t->dCommands, t->commandsSize * 4);
-    alloc((void **) &t->dKeysA, entries * 4);
-    alloc((void **) &t->dKeysB, entries * 4);
-    alloc((void **) &t->dValsA, entries * 4);
-    alloc((void **) &t->dValsB, entries * 4);
-    alloc((void **) &t->dHist, histElems * 4);
-    alloc((void **) &t->dTileSums, tileSums * 4);
-    alloc((void **) &t->dNumEntries, 4);
-    alloc((void **) &t->dSlotMasks, maxSplats);
-    alloc((void **) &t->dEntryNotes, maxSplats * 8);
-    alloc((void **) &t->dNodeCounts, t->maxStart * 4);
-    alloc((void **) &t->dNodeBase, t->maxStart * 4);
-    alloc((void **) &t->dDigitBase, 257 * 4);
-    alloc((void **) &t->dNodeTiles, ((uint64_t) scanTiles(t->maxStart) + 1) * sizeof(U3));
-    if (rc == MLSGPU_OK)
-        rc = t->entryBox.create();
-    if (rc != MLSGPU_OK)
-    {
-        mlsgpu_hip_tree_destroy(t);
-        return rc;
-    }
-    *out = t;
+    PROPAGATE(t->buffers([](auto &array, uint64_t n) { return array.alloc(n); }));
+    PROPAGATE(t->entryBox.create());
+    *out = t.release();
     return MLSGPU_OK;
 }
 
@@ -795,11 +788,6 @@ MLSGPU_API void mlsgpu_hip_tree_destroy(mlsgpu_tree *t)
     if (!t)
         return;
     hipSetDevice(t->ctx->device);
-    hipFree(t->dStart); hipFree(t->dJumpPos); hipFree(t->dCommands);
-    hipFree(t->dKeysA); hipFree(t->dKeysB); hipFree(t->dValsA); hipFree(t->dValsB);
-    hipFree(t->dHist); hipFree(t->dTileSums); hipFree(t->dNumEntries); hipFree(t->dSlotMasks); hipFree(t->dEntryNotes);
-    hipFree(t->dNodeCounts); hipFree(t->dNodeBase); hipFree(t->dNodeTiles); hipFree(t->dDigitBase);
-    t->entryBox.destroy();
     delete t;
 }
 
@@ -874,7 +862,7 @@ static int treeBuildBatch(mlsgpu_tree *const *trees, const mlsgpu_tree_build *re
     }
     /* fill(jumpPos, -1), kernels/octree.cl:346 -- or, on the direct route, the node counters (NodeOut writes jumpPos) */
     const auto jump = packLanes<int32_t *>(count, [&](uint32_t k) {
-        return direct ? reinterpret_cast<int32_t *>(trees[k]->dNodeCounts) : trees[k]->dJumpPos;
+        return direct ? reinterpret_cast<int32_t *>(trees[k]->dNodeCounts.get()) : trees[k]->dJumpPos.get();
     });
     LAUNCH(ctx, "kernel.octree.fill.time", fillKernel, dim3(divUp(numStart, 256), count), dim3(256), jump, numStart,
            (int32_t) (direct ? 0 : -1));
@@ -1018,7 +1006,7 @@ static int treeBuildBatch(mlsgpu_tree *const *trees, const mlsgpu_tree_build *re
             const auto sc = packLanes<SortScatterArgs<uint32_t> >(na, [&](uint32_t a) {
                 const SortJob<uint32_t> &j = sortJobs[a];
                 mlsgpu_tree *t = trees[act[a]];
-                return SortScatterArgs<uint32_t>{j.keysA, j.valsA, (uint32_t *) nullptr, reinterpret_cast<uint32_t *>(t->dCommands), j.dHist,
+                return SortScatterArgs<uint32_t>{j.keysA, j.valsA, (uint32_t *) nullptr, reinterpret_cast<uint32_t *>(t->dCommands.get()), j.dHist,
                                                  sortDigitTotals(j), j.n, j.nDev, sortTiles(j.n), t->dNodeBase, t->dDigitBase, idBits,
                                                  (uint32_t) reqs[act[a]].firstSplat};
             });
@@ -1128,12 +1116,11 @@ MLSGPU_API int mlsgpu_hip_test_scan_u32(mlsgpu_ctx *ctx, uint32_t *dData, uint64
 {
     REQUIRE(ctx != nullptr, MLSGPU_ERR_INVALID);
     HIP_CHECK(hipSetDevice(ctx->device));
-    uint32_t *dTiles = nullptr;
-    HIP_CHECK(hipMalloc(&dTiles, ((uint64_t) scanTiles(n) + 1) * 4));
+    DeviceArray<uint32_t> dTiles;
+    PROPAGATE(dTiles.alloc((uint64_t) scanTiles(n) + 1));
     int rc = exclusiveScan<uint32_t>(ctx, "test.scan", ArrayIn<uint32_t>{dData}, ArrayOut<uint32_t>{dData}, n, seed,
-                                     dTiles, (uint32_t *) nullptr);
+                                     dTiles.get(), (uint32_t *) nullptr);
     hipStreamSynchronize(ctx->stream);
-    hipFree(dTiles);
     return rc;
 }
 
@@ -1145,22 +1132,19 @@ MLSGPU_API int mlsgpu_hip_test_scan_u32_batch(mlsgpu_ctx *ctx, const uint32_t *c
     REQUIRE(ctx != nullptr && dIn != nullptr && dOut != nullptr && n != nullptr && seeds != nullptr, MLSGPU_ERR_INVALID);
     REQUIRE(count >= 1 && count <= MAX_LANES, MLSGPU_ERR_LENGTH);
     HIP_CHECK(hipSetDevice(ctx->device));
-    uint32_t *dTiles[MAX_LANES] = {};
+    DeviceArray<uint32_t> dTiles[MAX_LANES];
     typedef ScanJob<uint32_t, ArrayIn<uint32_t>, ArrayIn<uint32_t>, ArrayOut<uint32_t> > Job;
     Job jobs[MAX_LANES];
     int rc = MLSGPU_OK;
     for (uint32_t k = 0; k < count && rc == MLSGPU_OK; k++)
     {
-        if (hipMalloc(&dTiles[k], ((uint64_t) scanTiles(n[k]) + 1) * 4) != hipSuccess)
-            rc = setError(MLSGPU_ERR_NOMEM, "hipMalloc failed");
+        rc = dTiles[k].alloc((uint64_t) scanTiles(n[k]) + 1);
         jobs[k] = Job{ArrayIn<uint32_t>{dIn[k]}, ArrayIn<uint32_t>{dIn[k]}, ArrayOut<uint32_t>{dOut[k]}, n[k], seeds[k], dTiles[k],
                       (uint32_t *) nullptr, (const uint32_t *) nullptr};
     }
     for (uint32_t r = 0; r < repeats && rc == MLSGPU_OK; r++)
         rc = exclusiveScanBatch<uint32_t>(ctx, "test.scan", jobs, count);
     hipStreamSynchronize(ctx->stream);
-    for (uint32_t k = 0; k < count; k++)
-        hipFree(dTiles[k]);
     return rc;
 }
 
@@ -1168,12 +1152,12 @@ template<typename K>
 static int testSort(mlsgpu_ctx *ctx, K *dKeys, uint32_t *dValues, uint64_t n, uint32_t bits)
 {
     HIP_CHECK(hipSetDevice(ctx->device));
-    K *kb = nullptr;
-    uint32_t *vb = nullptr, *hist = nullptr, *tiles = nullptr;
-    HIP_CHECK(hipMalloc(&kb, (n + 1) * sizeof(K)));
-    HIP_CHECK(hipMalloc(&vb, (n + 1) * 4));
-    HIP_CHECK(hipMalloc(&hist, (sortHistElems(n) + 1) * 4));
-    HIP_CHECK(hipMalloc(&tiles, ((uint64_t) scanTiles(sortHistElems(n)) + 1) * 4));
+    DeviceArray<K> kb;
+    DeviceArray<uint32_t> vb, hist, tiles;
+    PROPAGATE(kb.alloc(n + 1));
+    PROPAGATE(vb.alloc(n + 1));
+    PROPAGATE(hist.alloc(sortHistElems(n) + 1));
+    PROPAGATE(tiles.alloc((uint64_t) scanTiles(sortHistElems(n)) + 1));
     SortResult<K> res;
     int rc = radixSort<K>(ctx, "test.sort", dKeys, dValues, kb, vb, n, bits, false, hist, tiles, &res);
     if (rc == MLSGPU_OK && res.keys != dKeys && n > 0)
@@ -1182,7 +1166,6 @@ static int testSort(mlsgpu_ctx *ctx, K *dKeys, uint32_t *dValues, uint64_t n, ui
         hipMemcpyAsync(dValues, res.vals, n * 4, hipMemcpyDeviceToDevice, ctx->stream);
     }
     hipStreamSynchronize(ctx->stream);
-    hipFree(kb); hipFree(vb); hipFree(hist); hipFree(tiles);
     return rc;
 }
 

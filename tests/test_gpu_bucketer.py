@@ -10,10 +10,14 @@ from test_oracle_bucket import GRID
 pytestmark = pytest.mark.gpu
 
 
-def both(splats, grid, max_splats, max_cells, chunk_cells, micro_cells, max_split):
+def both(splats, grid, max_splats, max_cells, chunk_cells, micro_cells, max_split, ctx=None):
+    """Leaves of the HIP bucketer and of the oracle, equal; on `ctx` (whose bucketer scratch then lives on) or a context of
+    the call's own."""
     import mlsgpu_amd as m
     from mlsgpu_amd import binding as b
-    ctx = m.Context(0)
+    own = ctx is None
+    if own:
+        ctx = m.Context(0)
     dev = m.DeviceBuffer(ctx, array=splats) if len(splats) else None
     try:
         try:
@@ -30,7 +34,8 @@ def both(splats, grid, max_splats, max_cells, chunk_cells, micro_cells, max_spli
     finally:
         if dev is not None:
             dev.free()
-        ctx.close()
+        if own:
+            ctx.close()
     assert len(got) == len(exp)
     for g, e in zip(got, exp):
         assert g["extents"] == e["extents"] and g["chunk"] == e["chunk"] and g["depth"] == e["depth"]
@@ -78,6 +83,31 @@ def test_random_with_kept_ranges_and_private_counters(seed, private, monkeypatch
     both(create_splats(), GRID, 5, 8, 0, 8, 1000000)
     both(create_splats(), GRID, 5, 8, 0, 0, 64)
     both(create_splats(), GRID, 20, 2 ** 31 - 1, 14, 8, 1000000)
+
+
+@pytest.mark.parametrize("forced", [False, True])
+def test_scratch_regrows_on_one_context(forced, monkeypatch):
+    """The bucketer's lists and counters stay with the context and grow on demand: a small cloud, one with many times the
+    splats (every buffer is reallocated while the small one's is held), then the small one again in the larger buffers --
+    the leaves are the oracle's each time.  `forced`: the kept ranges and the private counters from the first splat on, so
+    that their buffers regrow too."""
+    import mlsgpu_amd as m
+    if forced:
+        monkeypatch.setenv("MLSGPU_HIP_BUCKET_NOTES_FROM", "0")
+        monkeypatch.setenv("MLSGPU_HIP_BUCKET_PRIVATE_FROM", "0")
+    small = create_splats()
+    splats, grid, p = random_case(1)
+    assert len(splats) >= 4 * len(small)
+    ctx = m.Context(0)
+    try:
+        got, _ = both(small, GRID, 5, 8, 0, 8, 1000000, ctx=ctx)
+        assert len(got) == 11
+        got, _ = both(splats, grid, p["max_splats"], p["max_cells"], p["chunk_cells"], p["micro_cells"], p["max_split"], ctx=ctx)
+        assert got is not None and len(got) > 11
+        got, _ = both(small, GRID, 5, 8, 0, 8, 1000000, ctx=ctx)
+        assert len(got) == 11
+    finally:
+        ctx.close()
 
 
 def test_big_level_takes_the_private_counters():

@@ -102,6 +102,33 @@ def test_generate_manifold_and_parity(ctx, name):
     assert_batches_equal(again, exp)
 
 
+# (max dims, swathe, mesh memory, alignment): one swathe holds the volume (lattice weld only); several swathes (sort-weld buffers too)
+SMALL_SHAPES = [((33, 33, 32), 32, 32 * 32 * 2 * 872, (8, 8, 8)), ((20, 18, 24), 8, 19 * 17 * 3 * 872, (1, 1, 1))]
+
+
+def test_create_and_destroy_many_then_generate(ctx):
+    """Sixteen objects made and destroyed, alternately with and without the sort-weld buffers; one of each made behind them
+    still gives the oracle's batches."""
+    import mlsgpu_amd as m
+    from test_oracle_marching import sphere_fn
+    for i in range(16):
+        dims, swathe, mesh_memory, alignment = SMALL_SHAPES[i % 2]
+        mc = m.Marching(ctx, *dims, swathe, mesh_memory, alignment)
+        del mc
+    for (dims, swathe, mesh_memory, alignment), fn in zip(SMALL_SHAPES, [sphere_fn(16.3, 15.7, 15.2, 11.4),
+                                                                         sphere_fn(9.6, 8.7, 11.8, 7.3)]):
+        mc = m.Marching(ctx, *dims, swathe, mesh_memory, alignment)
+        got = mc.generate(m.binding.HostGenerator(ctx, fn, alignment), dims)
+        oracle = ob.MarchingOracle(*dims, swathe, mesh_memory, alignment)
+        exp = oracle.generate(host_generator(fn), dims)
+        assert sum(len(b["triangles"]) for b in exp) > 100
+        assert_batches_equal(got, exp)
+        st, cnt = oracle.stats(), mc.counters()
+        for k in ("shipouts", "overflows", "occupied", "unwelded", "indices", "welded", "external"):
+            assert st[k] == cnt[k], k
+        del mc
+
+
 @pytest.mark.parametrize("swathe,mem_slices,alignment,key_offset", [
     (8, 1, (8, 8, 8), (0, 0, 0)), (64, 300, (8, 8, 8), (100, 200, 300)), (24, 3, (8, 8, 8), (5, 6, 7)),
     # one swathe for the whole volume: the sort-free lattice weld, incl. overflow splitting and mid-bucket ship-outs

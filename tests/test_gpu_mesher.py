@@ -282,3 +282,48 @@ def test_boundary_after_finalize_reuses_the_analysis(seed, prune):
     fresh.close()
     sink.close()
     ctx.close()
+
+
+def test_one_sink_regrows_between_jobs():
+    """Jobs of very different sizes through ONE sink, reset() in between: a small one, one large enough that the slab, both
+    outputs and the arenas are reallocated while the sink holds the small job's buffers, and the small one again in the
+    larger buffers.  Every result is what a fresh sink gives.
+    An arena grows to max(need, 1.5 x capacity + 1024) elements, so its capacity stays below 1.5 x (the most it has held)
+    + 1024: a job that holds more than that in an arena moves it.  random_meshes(2) does so for vertices and triangles but
+    has 937 external keys, fewer than the 1039 that would move the key arenas behind CASES["weld"]'s 10; the 40-block job
+    behind it moves all of them (asserted on the input counts, on the CPU)."""
+    import mlsgpu_amd as m
+    jobs = [(CASES["weld"]["meshes"], 0.0), (random_meshes(2), 0.01), (CASES["weld"]["meshes"], 0.0),
+            (random_meshes(2, blocks=40), 0.01), (CASES["weld"]["meshes"], 0.0)]
+
+    def held(meshes):       # elements in the vertex, triangle and external-key arenas
+        return (3 * sum(len(x["vertices"]) for x in meshes), 3 * sum(len(x["triangles"]) for x in meshes),
+                sum(len(x["vertices"]) - x["num_internal"] for x in meshes))
+    small, large, larger = held(jobs[0][0]), held(jobs[1][0]), held(jobs[3][0])
+    assert all(b > 1.5 * a + 1024 for a, b in zip(small[:2], large[:2]))
+    assert all(b > 1.5 * a + 1024 for a, b in zip(large, larger))
+    for meshes, prune in jobs[:4]:
+        exp_stats = mo.mesh_sink(meshes, prune)[1]
+        assert exp_stats["kept_triangles"] > 0
+
+    ctx = m.Context(0)
+    sink = m.Mesher(ctx)
+    fresh = {}
+    for meshes, prune in jobs:
+        if id(meshes) not in fresh:
+            fresh[id(meshes)] = run_hip(meshes, prune)
+        exp, exp_stats = fresh[id(meshes)]
+        sink.set_prune_threshold(prune)
+        seen = {}
+        for mesh in meshes:
+            sink.add(chunk_number(mesh["chunk"], seen), mesh["vertices"], mesh["num_internal"], mesh["keys"], mesh["triangles"])
+        n = sink.finalize()
+        out = [sink.chunk(i) for i in range(n)]
+        assert sink.stats() == exp_stats
+        back = {v: k for k, v in seen.items()}
+        assert [back[c["chunk"]] for c in out] == [c for c, _, _ in exp]
+        for c, (_, ev, et) in zip(out, exp):
+            assert mo.isomorphic(c["vertices"], c["triangles"], ev, et)
+        sink.reset()
+    sink.close()
+    ctx.close()
