@@ -181,7 +181,11 @@ uint64_t mlsgpu_hip_tree_commands_size(const mlsgpu_tree *tree);       /* elemen
 uint64_t mlsgpu_hip_tree_start_size(const mlsgpu_tree *tree);
 uint32_t mlsgpu_hip_tree_num_levels(const mlsgpu_tree *tree);          /* getNumLevels */
 
-/* ---- MlsFunctor (src/mls.h:79-170) ---- */
+/* ---- MlsFunctor (src/mls.h:79-170) ----
+ * The functor owns one device allocation, which no resource_usage figure counts (the reference's functor has none): the table
+ * of block descriptors its default kernel reads, 64 bytes per 8x8x8 block of the largest launch so far (of all its buckets,
+ * for the first functor of mlsgpu_hip_mls_enqueue_batch): 2 MB for a 256^3 bucket.  It is allocated by the first enqueue, only
+ * grows, and goes with mlsgpu_hip_mls_destroy. */
 int mlsgpu_hip_mls_create(mlsgpu_ctx *ctx, int shape, mlsgpu_mls **out);
 void mlsgpu_hip_mls_destroy(mlsgpu_mls *mls);
 /* MlsFunctor::set(offset, tree, subsamplingShift), src/mls.cpp:91-94 */

@@ -36,8 +36,31 @@ extern "C" const int32_t *mlsgpu_hip_tree_commands(const mlsgpu_tree *);
 extern "C" const int32_t *mlsgpu_hip_tree_start(const mlsgpu_tree *);
 extern "C" int mlsgpu_hip_tree_mutates(const mlsgpu_tree *);
 
+/* What a workgroup of variant 5 is told about its block (blockTableKernel makes it, processCornersMatrixKernel reads it with one
+ * scalar load of 16 words): 0 the list position of the block's first splat id, negative for a block without a list; 1 the end
+ * of the list's first run; 2-3 the block's grid coordinates (gx | gy << 21 | gz << 42: none reaches 2^17, mlsLaneArgs);
+ * 4 + 4 a ..: the bounds of the block's two rows of sub-blocks along axis a, (float) o, o + 3, o + 4, o + 7 with o the block's
+ * first corner in splat coordinates. */
+struct alignas(64) BlockDesc
+{
+    uint32_t w[16];
+};
+
 struct mlsgpu_mls
 {
+    /* a table that a launch may still read: kept until `done`, recorded behind that launch, has passed */
+    struct RetiredBlocks
+    {
+        DeviceArray<BlockDesc> blocks;
+        hipEvent_t done;
+    };
+
+    ~mlsgpu_mls()
+    {
+        for (RetiredBlocks &r : retired)
+            (void) hipEventDestroy(r.done);
+    }
+
     mlsgpu_ctx *ctx = nullptr;
     int shape = MLSGPU_SHAPE_SPHERE;
     int variant = 5;             /* sub-block culling + matrix-core prefilter; 4 = culled + cube streams (round 5's default); 1 = the reference's loop structure (variants 0, 2, 3 were removed in round 4) */
@@ -50,6 +73,10 @@ struct mlsgpu_mls
     bool isSet = false;
     bool rawRadius = false;      /* the splats still hold the radius (a tree built without mutation): 1/r^2 is taken at staging */
     unsigned long long *dStats = nullptr;   /* optional work counters, see mlsgpu_hip_mls_set_stats */
+    /* variant 5: one BlockDesc per workgroup of the launch (of all its lanes, when this is the first functor of a batch), rewritten
+     * in front of every launch.  Allocated on first use, grows only; not part of any buffer list (see mlsgpu_hip.h) */
+    DeviceArray<BlockDesc> dBlocks;
+    std::vector<RetiredBlocks> retired;
 };
 
 namespace
@@ -281,11 +308,12 @@ struct MlsArgs
     uint32_t numBlocks;          /* blocksX * blocksY * blocksZ: workgroups of this lane; the grid covers the largest lane */
     float boundaryFactor;
     uint32_t xcdChunk;           /* see xcdRemap */
-    /* the block's place without a division (processCornersMatrixKernel): a workgroup's first ~100 instructions were four
-     * 32-bit divisions.  superShift = log2(8 * xcdChunk) when xcdChunk is a power of two, full = numBlocks rounded down to
-     * a multiple of 8 * xcdChunk, magicX / magicY = ceil(2^32 / blocksX), ceil(2^32 / blocksY), exact for every dividend the
-     * lane has (checked where they are made: mlsLaneArgs); superShift = 0: none of this holds, the kernel divides. */
+    /* a block's place without a division, for blockTableKernel (variants 1 and 4 divide: xcdRemap): superShift =
+     * log2(8 * xcdChunk) when xcdChunk is a power of two, full = numBlocks rounded down to a multiple of 8 * xcdChunk, magicX /
+     * magicY = ceil(2^32 / blocksX), ceil(2^32 / blocksY), exact for every dividend the lane has (checked where they are made:
+     * mlsLaneArgs); superShift = 0: none of this holds, the table kernel divides too. */
     uint32_t superShift, full, magicX, magicY;
+    BlockDesc *blocks;           /* variant 5: the lane's descriptors, entry i for workgroup blockIdx.x == i */
     uint32_t rawRadius;          /* splat.w is the radius, not 1/radius^2 */
     unsigned long long *stats;   /* MLSGPU_MLS_STATS_WORDS counters, see mlsgpu_hip_mls_set_stats */
 };
@@ -785,9 +813,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
  * instructions and 25 % fewer LDS instructions (profiles/r06_cfg3_processCorners_sq_counters.csv), the matrix pipe is 4 %
  * busy.  The drain requests the next candidate's records before it works on this one's (-1.5 %).
  *
- * Where a wave's time goes (s_memtime at the phase boundaries, -DMLSGPU_MLS5_CLOCK, tools/mls_clock.sh; cfg3 uniform): 15 %
- * before its first round (kernel arguments, start[], the list head, the ids: four dependent loads), 12 % staging, 6 % at the
- * barrier behind it, 9 % compaction, 43 % tiles and drains, 10 % at the round's last barrier.  Two things follow from it:
+ * What a workgroup knows about its block -- its place in the grid, where its list begins, the sub-block bounds the staging
+ * compares with -- is the same for its eight waves and a pure function of the launch and blockIdx.x: blockTableKernel works it
+ * out once per block, in front of the launch, and a wave begins with ONE scalar load of its block's 64-byte descriptor
+ * (BlockDesc).  Each wave used to spend ~150 of its ~2 300 instructions on the XCD map, the Morton code, start[], the list's
+ * head and twelve int -> float conversions carried into scalar registers through v_readfirstlane, behind two dependent scalar
+ * loads.  The ids and then the first round's records are requested straight away; the lane's own constants are made under
+ * those loads, the B operands come from a constant table (kBFrag: they depend on the thread, never on the block), and the
+ * lane's place in the field is worked out again at the final store instead of living through the rounds (the sphere fit
+ * spilled it: 12 bytes of scratch, now none).  Head 243 -> 140 instructions; cfg3 uniform 489 -> 466 us per launch of two
+ * buckets, + 4.9 us for the table kernel (profiles/NOTES_processCorners_head.md).
+ *
+ * Where a wave's time went before that (s_memtime at the phase boundaries, -DMLSGPU_MLS5_CLOCK, tools/mls_clock.sh; cfg3
+ * uniform): 12-15 % before its first round (kernel arguments, start[], the list head, the ids: four dependent loads), 12-14 %
+ * staging, 6 % at the barrier behind it, 9 % compaction, 43 % tiles and drains, 6-10 % at the round's last barrier.  Two things
+ * follow from it:
  * a round's records are requested BEFORE the wave waits for the others to leave the round before (the barrier that guards
  * the staged arrays sits between the loads and the LDS writes, and waits for LDS operations only), and a lane's eight
  * sub-block masks lie side by side so that the compaction reads them once (together -1.8 %).  -DMLSGPU_MLS5_DUMP leaves
@@ -819,6 +859,101 @@ __device__ __forceinline__ uint32_t packHi(uint32_t e0, uint32_t e1)
 #define MLSGPU_MLS5_WAVES 8
 #endif
 
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+
+/* the B operands of the two MFMAs for thread tid of a workgroup (see the kernel): the same for every block */
+struct BFragTable
+{
+    alignas(16) uint32_t w[512][2][4];
+};
+
+constexpr uint32_t smallIntAsFloatBits(uint32_t v)
+{
+    if (v == 0)
+        return 0;
+    uint32_t e = 0;
+    while ((2u << e) <= v)
+        e++;
+    return ((127u + e) << 23) | ((v - (1u << e)) << (23u - e));
+}
+
+constexpr uint32_t packHiConst(uint32_t e0, uint32_t e1) { return (e1 & 0xFFFF0000u) | (e0 >> 16); }
+
+constexpr BFragTable makeBFragTable()
+{
+    BFragTable t{};
+    for (uint32_t tid = 0; tid < 512; tid++)
+    {
+        const uint32_t wave = tid >> 6, lane = tid & 63u;
+        const uint32_t n = lane & 31u, h = lane >> 5;
+        for (uint32_t j = 0; j < 2; j++)
+        {
+            const uint32_t q = n + 32u * j;
+            const uint32_t qx = (wave & 1u) * 4u + (q & 3u), qy = ((wave >> 1) & 1u) * 4u + ((q >> 2) & 3u), qz = (wave >> 2) * 4u + (q >> 4);
+            const uint32_t u = h ? qz : qx, v = h ? qx * qx + qy * qy + qz * qz : qy;
+            const uint32_t ub = smallIntAsFloatBits(u), vb = smallIntAsFloatBits(v);     /* exact in bf16 */
+            t.w[tid][j][0] = packHiConst(ub, ub);
+            t.w[tid][j][1] = packHiConst(ub, vb);
+            t.w[tid][j][2] = packHiConst(vb, vb);
+            t.w[tid][j][3] = 0x3F803F80u;
+        }
+    }
+    return t;
+}
+
+__device__ const BFragTable kBFrag = makeBFragTable();
+
+/* The descriptors of a launch, one thread per workgroup of processCornersMatrixKernel: where workgroup `id` of the lane works
+ * (xcdRemap, and the three coordinates by shifts and two multiplications where MlsArgs has the constants), where its list
+ * begins, and the sub-block bounds as the floats the staging compares with -- everything about a block that is the same for
+ * its eight waves.  The workgroups then start with one scalar load instead of ~150 instructions and two dependent loads. */
+__global__ __launch_bounds__(256) void blockTableKernel(Lanes<MlsArgs> lanes)
+{
+    const MlsArgs A = lanes.a[blockIdx.y];
+    const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= A.numBlocks)
+        return;
+    uint32_t gx, gy, gz;
+    if (A.superShift != 0)
+    {
+        const uint32_t sh = A.superShift;
+        const uint32_t j = id & ((1u << sh) - 1u);
+        const uint32_t bid = id >= A.full ? id : (id >> sh << sh) + ((j & 7u) << (sh - 3u)) + (j >> 3);
+        const uint32_t t = __umulhi(bid, A.magicX);
+        gx = bid - t * A.blocksX;
+        gz = __umulhi(t, A.magicY);
+        gy = t - gz * A.blocksY;
+    }
+    else
+    {
+        const uint32_t bid = xcdRemap(id, A.numBlocks, A.xcdChunk);
+        gx = bid % A.blocksX;
+        gy = (bid / A.blocksX) % A.blocksY;
+        gz = bid / (A.blocksX * A.blocksY);
+    }
+    const int w[3] = {(int) (gx * 8), (int) (gy * 8), (int) (gz * 8 + A.zFirst)};
+    const int o[3] = {w[0] + A.ox, w[1] + A.oy, w[2] + A.oz};
+    /* makeCode(wid) >> startShift (kernels/mls.cl:318) == makeCode(wid >> subsampling): Morton digits are independent */
+    const uint32_t sub = A.startShift / 3;
+    const uint32_t code = spread3((uint32_t) w[0] >> sub) | (spread3((uint32_t) w[1] >> sub) << 1) | (spread3((uint32_t) w[2] >> sub) << 2);
+    const int32_t pos = A.start[code];
+    const uint64_t g = (uint64_t) gx | ((uint64_t) gy << 21) | ((uint64_t) gz << 42);
+    u32x16 d;
+    d[0] = pos >= 0 ? (uint32_t) (pos + 1) : 0xFFFFFFFFu;
+    d[1] = pos >= 0 ? (uint32_t) A.commands[pos] : 0u;
+    d[2] = (uint32_t) g;
+    d[3] = (uint32_t) (g >> 32);
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+    {
+        d[4 + 4 * a] = __float_as_uint((float) o[a]);
+        d[5 + 4 * a] = __float_as_uint((float) (o[a] + 3));
+        d[6 + 4 * a] = __float_as_uint((float) (o[a] + 4));
+        d[7 + 4 * a] = __float_as_uint((float) (o[a] + 7));
+    }
+    *reinterpret_cast<u32x16 *>(A.blocks + id) = d;
+}
+
 
 template<int SHAPE, bool STATS>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MLSGPU_MLS5_WAVES, MLSGPU_MLS5_WAVES)))
@@ -841,10 +976,11 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
 #ifdef MLSGPU_MLS5_CLOCK
     /* where a wave's time goes (an instrumented build for profiles/NOTES only: tools/mls_clock.sh); s_memtime at the points
      * where the wave waits for its LDS operations anyway */
-    uint64_t clkMark = __builtin_amdgcn_s_memtime();
-    const uint64_t clkStart = clkMark;
-    uint64_t clkHead = 0, clkStage = 0, clkBar1 = 0, clkCompact = 0, clkTiles = 0, clkBar2 = 0;
-#define MLS5_CLOCK(sum) do { uint64_t now_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_) : : "memory"); sum += now_ - clkMark; clkMark = now_; } while (0)
+    /* (32-bit marks and sums: a wave lives ~50 000 cycles, and seven 64-bit values more in scalar registers spill) */
+    uint32_t clkMark = (uint32_t) __builtin_amdgcn_s_memtime();
+    const uint32_t clkStart = clkMark;
+    uint32_t clkHead = 0, clkStage = 0, clkBar1 = 0, clkCompact = 0, clkTiles = 0, clkBar2 = 0;
+#define MLS5_CLOCK(sum) do { uint64_t now_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_) : : "memory"); sum += (uint32_t) now_ - clkMark; clkMark = (uint32_t) now_; } while (0)
 #else
 #define MLS5_CLOCK(sum) do { } while (0)
 #endif
@@ -854,87 +990,41 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
             sHist[threadIdx.x] = 0;
         __syncthreads();
     }
-    uint32_t gx, gy, gz;
-    if (A.superShift != 0)
-    {
-        /* xcdRemap and the three coordinates by shifts and two multiplications (see MlsArgs) */
-        const uint32_t id = blockIdx.x, sh = A.superShift;
-        const uint32_t j = id & ((1u << sh) - 1u);
-        const uint32_t bid = id >= A.full ? id : (id >> sh << sh) + ((j & 7u) << (sh - 3u)) + (j >> 3);
-        const uint32_t t = __umulhi(bid, A.magicX);
-        gx = bid - t * A.blocksX;
-        gz = __umulhi(t, A.magicY);
-        gy = t - gz * A.blocksY;
-    }
-    else
-    {
-        const uint32_t bid = xcdRemap(blockIdx.x, A.numBlocks, A.xcdChunk);
-        gx = bid % A.blocksX;
-        gy = (bid / A.blocksX) % A.blocksY;
-        gz = bid / (A.blocksX * A.blocksY);
-    }
+    /* the block: one scalar load (blockTableKernel).  Read as constant memory, which the table is while this kernel runs: a
+     * plain global load stays a scalar one only as long as nothing in front of it may write memory (the instrumented builds'
+     * barrier and clock reads do) */
+    typedef const __attribute__((address_space(4))) u32x16 ConstDesc;
+    const u32x16 D = *(ConstDesc *) reinterpret_cast<const u32x16 *>(A.blocks + blockIdx.x);
+    const uint32_t gx = D[2] & 0x1FFFFFu, gy = (uint32_t) ((((uint64_t) D[3] << 32) | D[2]) >> 21) & 0x1FFFFFu, gz = D[3] >> 10;
     const int wx = (int) (gx * 8), wy = (int) (gy * 8), wz = (int) (gz * 8 + A.zFirst);
-    const uint32_t sub = A.startShift / 3;
-    const uint32_t code = spread3((uint32_t) wx >> sub) | (spread3((uint32_t) wy >> sub) << 1) | (spread3((uint32_t) wz >> sub) << 2);
-    int32_t pos = A.start[code];
+    /* this thread's corner gets f.  Its place is worked out from threadIdx.x where the store is, behind the rounds: kept from
+     * the head, it would occupy two of the kernel's 64 vector registers throughout (the sphere fit spilled them) */
+    auto storeCorner = [&](const float f)
+    {
+        uint32_t t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        const uint32_t w = t >> 6, l = t & 63;
+        const int x = wx + (int) ((w & 1) * 4 + (l & 3));
+        const int y = wy + (int) (((w >> 1) & 1) * 4 + ((l >> 2) & 3));
+        const int z = wz + (int) ((w >> 2) * 4 + (l >> 4));
+        const int64_t row = (int64_t) y + (int64_t) z * A.zStride + A.zBias;
+        A.field[row * (int64_t) A.pitch + x] = f;
+    };
+    int32_t pos = (int32_t) D[0], end = (int32_t) D[1];
 
     const uint32_t tid = threadIdx.x;
     const uint32_t wave = tid >> 6, lane = tid & 63;
-    const int lx = (int) ((wave & 1) * 4 + (lane & 3));
-    const int ly = (int) (((wave >> 1) & 1) * 4 + ((lane >> 2) & 3));
-    const int lz = (int) ((wave >> 2) * 4 + (lane >> 4));
-
     float f = __int_as_float(0x7FC00000);
-    if (pos >= 0)       /* uniform over the workgroup */
+    if (pos >= 0)       /* uniform over the workgroup; a block without a list goes straight to its store */
     {
-        const float cx = (float) (wx + lx + A.ox), cy = (float) (wy + ly + A.oy), cz = (float) (wz + lz + A.oz);
-
-        /* wave-uniform floats live in scalar registers (a float made by a vector instruction would be hoisted out of the
-         * loops into a vector register each: twelve of the kernel's 64) */
-        /* (the builtin is folded away for a value the compiler knows to be uniform.)  The wait states are part of the
-         * statement: the compiler's hazard recogniser does not look into inline assembly, and a v_readfirstlane issued
-         * right behind the conversion that writes its source READ THE OLD REGISTER on gfx950 -- one block of one test case,
-         * found when a rearrangement of this kernel put the two back to back (profiles/NOTES_r06.md, section 1).  Four bounds
-         * of an axis per statement: one pair of wait states for the four. */
-        float bx0, by0, bz0;
-        float boxLo[3][2], boxHi[3][2];
-        auto axisBounds = [](int o, float &lo0, float &hi0, float &lo1, float &hi1)
-        {
-            asm("s_nop 3\n\tv_readfirstlane_b32 %0, %4\n\tv_readfirstlane_b32 %1, %5\n\tv_readfirstlane_b32 %2, %6\n\t"
-                "v_readfirstlane_b32 %3, %7\n\ts_nop 1"
-                : "=s"(lo0), "=s"(hi0), "=s"(lo1), "=s"(hi1)
-                : "v"((float) o), "v"((float) (o + 3)), "v"((float) (o + 4)), "v"((float) (o + 7)));
-        };
-        axisBounds(wx + A.ox, boxLo[0][0], boxHi[0][0], boxLo[0][1], boxHi[0][1]);
-        axisBounds(wy + A.oy, boxLo[1][0], boxHi[1][0], boxLo[1][1], boxHi[1][1]);
-        axisBounds(wz + A.oz, boxLo[2][0], boxHi[2][0], boxLo[2][1], boxHi[2][1]);
-        bx0 = boxLo[0][0];
-        by0 = boxLo[1][0];
-        bz0 = boxLo[2][0];
-        Fit fit;
-        fitInit(fit);
-        unsigned long long nListed = 0, nTests = 0, nCand = 0, nMissed = 0;
-        uint32_t drainCalls = 0, sumMost = 0, sumMostRound = 0, roundCnt = 0;
-        typedef __attribute__((address_space(3))) uint16_t LdsSlot;
-        LdsSlot *const mySlots = (LdsSlot *) sSlot[wave] + 4;
-        f32x2 sWpxy = {0.0f, 0.0f}, sWnxy = {0.0f, 0.0f};
-        const f32x2 cxy = {cx, cy};
-
+        /* the first round's splat ids and then its records are requested first: the lane's constants are made under the loads.
+         * (Later on a round's ids are requested while the round before it is processed.) */
+        int32_t idAhead = listedId(A, pos, end, tid);
         /* B operands: lane l = column n = l & 31 of both MFMAs, k = 8 (l >> 5) + j.  MFMA j covers the corners
          * n + 32 j of the sub-block (z layers 2 j, 2 j + 1); coordinates relative to the block origin */
         uint4 bFrag[2];
-        {
-            const uint32_t n = lane & 31u, h = lane >> 5;
-#pragma unroll
-            for (uint32_t j = 0; j < 2; j++)
-            {
-                const uint32_t q = n + 32u * j;
-                const uint32_t qx = (wave & 1u) * 4u + (q & 3u), qy = ((wave >> 1) & 1u) * 4u + ((q >> 2) & 3u), qz = (wave >> 2) * 4u + (q >> 4);
-                const uint32_t u = h ? qz : qx, v = h ? qx * qx + qy * qy + qz * qz : qy;
-                const uint32_t ub = __float_as_uint((float) u), vb = __float_as_uint((float) v);     /* exact in bf16 */
-                bFrag[j] = make_uint4(packHi(ub, ub), packHi(ub, vb), packHi(vb, vb), 0x3F803F80u);
-            }
-        }
+        bFrag[0] = *reinterpret_cast<const uint4 *>(kBFrag.w[tid][0]);
+        bFrag[1] = *reinterpret_cast<const uint4 *>(kBFrag.w[tid][1]);
         /* A operand: lane l holds row m = l & 31, which carries splat s(m) of the tile so that the sign bits line up in
          * list order: row 8 (r >> 2) + 4 half + (r & 3) <-> splat 16 half + r */
         const uint32_t rowM = lane & 31u;
@@ -945,6 +1035,39 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
         static_assert((MATRIX_SLOTS + 40) * sizeof(uint16_t) % 16 == 0 && (MATRIX_SLOTS + 40) * sizeof(uint16_t) <= 64 * 16, "one store per lane");
         if (lane < (MATRIX_SLOTS + 40) * sizeof(uint16_t) / 16)
             reinterpret_cast<uint4 *>(sSlot[wave])[lane] = make_uint4(0u, 0u, 0u, 0u);
+
+        float4 pr = {0.0f, 0.0f, 0.0f, 0.0f}, nq = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (idAhead >= 0)
+        {
+            pr = A.splats[2 * (int64_t) idAhead];
+            nq = A.splats[2 * (int64_t) idAhead + 1];
+        }
+
+        const int lx = (int) ((wave & 1) * 4 + (lane & 3));
+        const int ly = (int) (((wave >> 1) & 1) * 4 + ((lane >> 2) & 3));
+        const int lz = (int) ((wave >> 2) * 4 + (lane >> 4));
+        const float cx = (float) (wx + lx + A.ox), cy = (float) (wy + ly + A.oy), cz = (float) (wz + lz + A.oz);
+
+        /* wave-uniform floats live in scalar registers, which is where the descriptor's load puts them (a float made by a
+         * vector instruction would be hoisted out of the loops into a vector register each: twelve of the kernel's 64) */
+        float boxLo[3][2], boxHi[3][2];
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+        {
+            boxLo[a][0] = __uint_as_float(D[4 + 4 * a]);
+            boxHi[a][0] = __uint_as_float(D[5 + 4 * a]);
+            boxLo[a][1] = __uint_as_float(D[6 + 4 * a]);
+            boxHi[a][1] = __uint_as_float(D[7 + 4 * a]);
+        }
+        const float bx0 = boxLo[0][0], by0 = boxLo[1][0], bz0 = boxLo[2][0];
+        Fit fit;
+        fitInit(fit);
+        unsigned long long nListed = 0, nTests = 0, nCand = 0, nMissed = 0;
+        uint32_t drainCalls = 0, sumMost = 0, sumMostRound = 0, roundCnt = 0;
+        typedef __attribute__((address_space(3))) uint16_t LdsSlot;
+        LdsSlot *const mySlots = (LdsSlot *) sSlot[wave] + 4;
+        f32x2 sWpxy = {0.0f, 0.0f}, sWnxy = {0.0f, 0.0f};
+        const f32x2 cxy = {cx, cy};
 
         /* one candidate: the reference's test and sums (kernels/mls.cl:362-390) */
         auto accumulate = [&](const float4 pr, const float4 nq)
@@ -1008,30 +1131,12 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
             }
         };
 
-        int32_t end = A.commands[pos++];
-        /* a round's splat ids are requested while the round before it is processed */
-        int32_t idAhead = listedId(A, pos, end, tid);
         MLS5_CLOCK(clkHead);
-        bool laterRound = false;
         while (pos < end)
         {
             {
                 uint32_t mask = 0;
                 const int32_t mine = idAhead;
-                /* the round's records are requested BEFORE the wave waits for the others to be done with the round before:
-                 * the barrier only guards the staged arrays */
-                float4 pr = {0.0f, 0.0f, 0.0f, 0.0f}, nq = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (mine >= 0)
-                {
-                    pr = A.splats[2 * (int64_t) mine];
-                    nq = A.splats[2 * (int64_t) mine + 1];
-                }
-                if (laterRound)
-                {
-                    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : : : "memory");
-                    MLS5_CLOCK(clkBar2);
-                }
-                laterRound = true;
                 if (mine >= 0)
                 {
                     if (A.rawRadius)
@@ -1189,6 +1294,19 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
                 sumMostRound += waveMax(roundCnt);
                 roundCnt = 0;
             }
+            if (pos < end)
+            {
+                /* the next round's records are requested BEFORE the wave waits for the others to be done with this one: the
+                 * barrier only guards the staged arrays */
+                pr = nq = float4{0.0f, 0.0f, 0.0f, 0.0f};
+                if (idAhead >= 0)
+                {
+                    pr = A.splats[2 * (int64_t) idAhead];
+                    nq = A.splats[2 * (int64_t) idAhead + 1];
+                }
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" : : : "memory");
+                MLS5_CLOCK(clkBar2);
+            }
         }
         fitUnpack(fit, sWpxy, sWnxy);
         f = finishCorner<SHAPE>(fit, A.boundaryFactor);
@@ -1203,7 +1321,7 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
             atomicAdd(&A.stats[3], (unsigned long long) clkCompact);
             atomicAdd(&A.stats[4], (unsigned long long) clkTiles);
             atomicAdd(&A.stats[5], (unsigned long long) clkBar2);
-            atomicAdd(&A.stats[6], (unsigned long long) (__builtin_amdgcn_s_memtime() - clkStart));
+            atomicAdd(&A.stats[6], (unsigned long long) ((uint32_t) __builtin_amdgcn_s_memtime() - clkStart));
             atomicAdd(&A.stats[7], 1ull);
         }
 #endif
@@ -1217,8 +1335,7 @@ void processCornersMatrixKernel(Lanes<MlsArgs> lanes)
             addStats<true>(A, fit.hits, nListed, nTests, drainCalls, sumMost, sumMostRound, sHist);
         }
     }
-    const int64_t row = (int64_t) (wy + ly) + (int64_t) (wz + lz) * A.zStride + A.zBias;
-    A.field[row * (int64_t) A.pitch + (wx + lx)] = f;
+    storeCorner(f);
 }
 
 } // namespace
@@ -1236,7 +1353,13 @@ MLSGPU_API int mlsgpu_hip_mls_create(mlsgpu_ctx *ctx, int shape, mlsgpu_mls **ou
     return mlsgpu_hip_mls_set_boundary_limit(m, 1.0f);     /* src/mls.cpp:72 */
 }
 
-MLSGPU_API void mlsgpu_hip_mls_destroy(mlsgpu_mls *m) { delete m; }
+MLSGPU_API void mlsgpu_hip_mls_destroy(mlsgpu_mls *m)
+{
+    if (!m)
+        return;
+    hipSetDevice(m->ctx->device);       /* the descriptor tables go with it */
+    delete m;
+}
 
 MLSGPU_API int mlsgpu_hip_mls_set_buffers(mlsgpu_mls *m, const int32_t offset[3], const mlsgpu_splat *dSplats,
                                           const int32_t *dCommands, const int32_t *dStart, uint32_t subsamplingShift)
@@ -1359,10 +1482,39 @@ static int mlsLaneArgs(mlsgpu_mls *m, float *dField, uint64_t pitch, uint64_t fi
             A.magicY = (uint32_t) my;
         }
     }
+    A.blocks = nullptr;         /* mlsEnqueueLanes */
     A.rawRadius = m->rawRadius ? 1u : 0u;
     A.stats = m->dStats;
     *out = A;
     return MLSGPU_OK;
+}
+
+/* room for the `n` block descriptors of a launch in m's table.  A table that is outgrown may still be read by a launch in
+ * flight: it is put aside with an event behind that launch and freed by a later call that finds the event passed (or with m). */
+static int mlsReserveBlocks(mlsgpu_mls *m, uint64_t n)
+{
+    for (size_t i = m->retired.size(); i-- > 0;)
+        if (hipEventQuery(m->retired[i].done) == hipSuccess)
+        {
+            (void) hipEventDestroy(m->retired[i].done);
+            m->retired.erase(m->retired.begin() + (std::ptrdiff_t) i);
+        }
+    (void) hipGetLastError();       /* hipErrorNotReady is no error */
+    if (m->dBlocks.get() != nullptr && n <= m->dBlocks.capacity())
+        return MLSGPU_OK;
+    if (m->dBlocks.get() != nullptr)
+    {
+        hipEvent_t done;
+        HIP_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        const hipError_t e = hipEventRecord(done, m->ctx->stream);
+        if (e != hipSuccess)
+        {
+            (void) hipEventDestroy(done);
+            HIP_CHECK(e);
+        }
+        m->retired.push_back(mlsgpu_mls::RetiredBlocks{std::move(m->dBlocks), done});
+    }
+    return m->dBlocks.alloc(n);
 }
 
 /* MlsFunctor::enqueue for the buckets of a batch: one launch, blockIdx.y = bucket.  The functors share a context, the
@@ -1375,8 +1527,19 @@ static int mlsEnqueueLanes(mlsgpu_mls *const *ms, const MlsArgs *args, uint32_t 
         REQUIRE(ms[k]->ctx == ctx && ms[k]->shape == m->shape && ms[k]->variant == m->variant
                 && (ms[k]->dStats != nullptr) == (m->dStats != nullptr), MLSGPU_ERR_INVALID);
     HIP_CHECK(hipSetDevice(ctx->device));
-    const auto L = packLanes<MlsArgs>(count, [&](uint32_t k) { return args[k]; });
-    const dim3 grid(mostOfLanes(count, [&](uint32_t k) { return args[k].numBlocks; }), count), block(512);
+    const uint32_t mostBlocks = mostOfLanes(count, [&](uint32_t k) { return args[k].numBlocks; });
+    /* variant 5: the lanes' block descriptors lie one lane after the other in the first functor's table */
+    uint64_t blocksBefore[MAX_LANES + 1] = {0};
+    for (uint32_t k = 0; k < count; k++)
+        blocksBefore[k + 1] = blocksBefore[k] + args[k].numBlocks;
+    if (m->variant == 5)
+        PROPAGATE(mlsReserveBlocks(m, blocksBefore[count]));
+    const auto L = packLanes<MlsArgs>(count, [&](uint32_t k) {
+        MlsArgs A = args[k];
+        A.blocks = m->variant == 5 ? m->dBlocks.get() + blocksBefore[k] : nullptr;
+        return A;
+    });
+    const dim3 grid(mostBlocks, count), block(512);
     const char *stat = "kernel.mls.processCorners.time";      /* src/mls.cpp:57 */
     /* tuning aid: dynamic LDS that the kernel never touches lowers its occupancy (3 workgroups per CU from 8 KB, 2 from
      * 20 KB), leaving wave slots to the memory-bound kernels of the other device workers */
@@ -1393,18 +1556,28 @@ static int mlsEnqueueLanes(mlsgpu_mls *const *ms, const MlsArgs *args, uint32_t 
     const bool sphere = m->shape == MLSGPU_SHAPE_SPHERE, stats = m->dStats != nullptr;    /* stats: an instrumented build,
                                                                                             * never in a timed run */
 #endif
-#define MLS_LAUNCH(KERNEL, SHAPE, STATS) LAUNCH_LDS(ctx, stat, (KERNEL<SHAPE, STATS>), grid, block, ldsPad, L)
+    /* one timed interval per enqueue: variant 5's table kernel runs under processCorners' name and counts as part of it */
+    int pending = -1;
+    if (ctx->timing)
+        pending = ctx->beginTiming(ctx->statId(stat));
+#define MLS_LAUNCH(KERNEL, SHAPE, STATS) hipLaunchKernelGGL((KERNEL<SHAPE, STATS>), grid, block, ldsPad, ctx->stream, L)
 #define MLS_LAUNCH_ANY(KERNEL)                                                                                   \
     do {                                                                                                         \
         if (stats) { if (sphere) MLS_LAUNCH(KERNEL, MLSGPU_SHAPE_SPHERE, true); else MLS_LAUNCH(KERNEL, MLSGPU_SHAPE_PLANE, true); } \
         else { if (sphere) MLS_LAUNCH(KERNEL, MLSGPU_SHAPE_SPHERE, false); else MLS_LAUNCH(KERNEL, MLSGPU_SHAPE_PLANE, false); }     \
     } while (0)
     if (m->variant == 5)
+    {
+        hipLaunchKernelGGL(blockTableKernel, dim3(divUp(mostBlocks, 256), count), dim3(256), 0, ctx->stream, L);
         MLS_LAUNCH_ANY(processCornersMatrixKernel);
+    }
     else if (m->variant == 4)
         MLS_LAUNCH_ANY(processCornersCubeKernel);
     else
         MLS_LAUNCH_ANY(processCornersKernel);
+    if (pending >= 0)
+        ctx->endTiming(pending);
+    HIP_CHECK(hipGetLastError());
 #undef MLS_LAUNCH_ANY
 #undef MLS_LAUNCH
     return MLSGPU_OK;
