@@ -12,9 +12,10 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
+ * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
  */
 #include <cstdio>
 #include <cstdlib>
@@ -32,7 +33,7 @@ static bool isPly(const std::string &a) { return a.size() > 4 && a.compare(a.siz
 int main(int argc, char **argv)
 {
     std::vector<std::int32_t> devices(1, 0);
-    bool hostWeld = false;
+    bool hostWeld = false, checkTopology = false;
     std::uint64_t bufferBytes = 0, hbmSplats = 0;
     std::string tmpDir;
     std::vector<std::string> plys, rest;
@@ -49,6 +50,8 @@ int main(int argc, char **argv)
         }
         else if (a == "--weld" && i + 1 < argc)
             hostWeld = std::string(argv[++i]) == "host";
+        else if (a == "--check")
+            checkTopology = true;
         else if (a == "--buffer" && i + 1 < argc)
             bufferBytes = strtoull(argv[++i], NULL, 10);
         else if (a == "--tmp-dir" && i + 1 < argc)             // --weld host: the welder's blocks in temporary files there (src/mlsgpu_core.cpp --tmp-dir)
@@ -62,7 +65,7 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
         return 2;
     }
@@ -162,6 +165,18 @@ int main(int argc, char **argv)
                     grid.extents[3], grid.extents[4], grid.extents[5], bins, devices.size(), hostWeld ? "host" : "device",
                     written, (unsigned long long) st[4], (unsigned long long) st[5], (unsigned long long) st[2],
                     (unsigned long long) st[3]);
+        if (checkTopology && !hostWeld)
+            for (std::uint32_t i = 0; i < written; i++)
+            {
+                std::uint64_t id = 0;
+                check(mlsgpu_hip_mesher_chunk(deviceMesher.get(), i, &id, NULL, NULL, NULL, NULL));
+                const mlsgpu_topology t = deviceMesher.topology(i);
+                const std::string why = Manifold::reason(t);
+                std::printf("topology chunk %llu manifold %s components %llu boundaries %llu euler %lld boundary-edges %llu%s%s\n",
+                            (unsigned long long) id, t.manifold ? "yes" : "no", (unsigned long long) t.numComponents,
+                            (unsigned long long) t.numBoundaries, (long long) t.eulerCharacteristic,
+                            (unsigned long long) t.boundaryEdges, why.empty() ? "" : " ", why.c_str());
+            }
     }
     catch (std::exception &e)
     {

@@ -599,6 +599,58 @@ int mlsgpu_hip_mesher_chunk(mlsgpu_mesher *mesher, uint32_t i, uint64_t *chunkId
 /* getStatistics (src/mesher.cpp:491-536): out[0] welded vertices, [1] threshold, [2] components, [3] kept components,
  * [4] kept vertices (each welded vertex once), [5] kept triangles, [6] vertices added, [7] triangles added */
 int mlsgpu_hip_mesher_stats(mlsgpu_mesher *mesher, uint64_t out[8]);
+
+/* ---- topology report of a device-resident mesh: Manifold::isManifold (test/manifold.h:98-232) in its "count-all" form.
+ *      The reference returns at the first defect; here every triangle and vertex is classified and counted, and the lowest
+ *      index of each class is kept, from which the reference's verdict follows (firstKind / firstIndex).
+ *      A triangle (i0, i1, i2) takes the first check that fails of i0 >= V, i0 == i1, i1 >= V, i1 == i2, i2 >= V, i2 == i0:
+ *      a range failure is OUT_OF_RANGE, an equality DEGENERATE; such triangles take no further part.  The others give the
+ *      half-edges a -> b, b -> c, c -> a.  A vertex is ISOLATED if no good triangle uses it, else DUPLICATED if it is an end of
+ *      a half-edge that occurs more than once, else MIXED ("both in the interior and on the boundary") or TUNNEL ("tunnels
+ *      between interior regions") as in the reference.  The mesh is manifold if all six counts are zero; only then are
+ *      edges, numComponents, numBoundaries and eulerCharacteristic filled (0 otherwise, like the reference's Metadata). ---- */
+#define MLSGPU_TOPO_OUT_OF_RANGE 0
+#define MLSGPU_TOPO_DEGENERATE 1
+#define MLSGPU_TOPO_ISOLATED 2
+#define MLSGPU_TOPO_DUPLICATED 3
+#define MLSGPU_TOPO_MIXED 4
+#define MLSGPU_TOPO_TUNNEL 5
+#define MLSGPU_TOPO_NONE 6
+typedef struct mlsgpu_topology
+{
+    uint64_t numVertices, numTriangles;
+    uint64_t count[6];      /* triangles (the first two) and vertices per class, indexed by MLSGPU_TOPO_* */
+    uint64_t firstOf[6];    /* lowest triangle / vertex index of the class, UINT64_MAX if none */
+    uint64_t duplicateEdges;/* half-edge records equal to their predecessor in (from, to) order */
+    uint64_t boundaryEdges; /* distinct half-edges a -> b without b -> a */
+    uint64_t edges;         /* (3 T + boundaryEdges) / 2 */
+    uint64_t numComponents; /* connected components of the graph of vertices and edges */
+    uint64_t numBoundaries; /* connected components of the graph of boundary edges (a vertex on several boundary runs joins
+                             * them into one, test/manifold.h:84-87) */
+    int64_t eulerCharacteristic;    /* V - edges + T */
+    uint64_t firstIndex;    /* the reference's verdict: the lowest bad triangle if any, else the lowest classified vertex; */
+    uint32_t firstKind;     /* its class, MLSGPU_TOPO_NONE (and firstIndex UINT64_MAX) for a manifold mesh */
+    uint32_t manifold;      /* 1 or 0 */
+} mlsgpu_topology;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_topology) == 176, "mlsgpu_topology is part of the ABI");
+#else
+typedef char mlsgpu_topology_size_is_176[sizeof(mlsgpu_topology) == 176 ? 1 : -1];
+#endif
+/* numTriangles triangles of three uint32 indices on ctx's device, numVertices vertices (no positions are needed).
+ * MLSGPU_ERR_LENGTH if 3 * numTriangles or numVertices does not fit 32 bits.  No triangles: every vertex is isolated, and no
+ * vertices either is manifold.  Scratch is allocated for the call and freed on return: 24 bytes per half-edge (the sort's
+ * two sides), the sort's histogram, 18 bytes per vertex; MLSGPU_ERR_NOMEM if the device does not have it.  Blocks until the
+ * report is there. */
+int mlsgpu_hip_mesh_topology(mlsgpu_ctx *ctx, const uint32_t *dTriangles, uint64_t numTriangles, uint64_t numVertices,
+                             mlsgpu_topology *out);
+/* the same for output chunk i of a finalized device sink (the mesh of mlsgpu_hip_mesher_chunk), on the mesher's context */
+int mlsgpu_hip_mesher_chunk_topology(mlsgpu_mesher *mesher, uint32_t i, mlsgpu_topology *out);
+/* Host only: "" if the mesh is manifold, else one sentence for the first defect, in the reference's wording where the
+ * report carries what it names (a DUPLICATED vertex stands for the reference's edge, and the offending index of a bad
+ * triangle is not repeated).  At most len - 1 characters and a terminator are written to buf (which may be NULL); returns
+ * the length of the whole sentence. */
+uint64_t mlsgpu_hip_topology_reason(const mlsgpu_topology *t, char *buf, uint64_t len);
 /* ---- host mesh sink: OOCMesher's weld as the reference runs it, on the host (src/mesher.cpp:220-469, north_star:
  *      "welding stays on host").  add() is MesherBase::InputFunctor: local components of the block by union-find over
  *      two edges per triangle (computeLocalComponents, :220-236), clumps merged across blocks through the external

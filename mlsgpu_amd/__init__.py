@@ -6,7 +6,7 @@ a thin ctypes binding of the same C-ABI, used by the tests and by bench.py.  The
 fallback: importing :mod:`mlsgpu_amd.binding` without the built library raises.
 """
 from .binding import (BucketFarm, Context, DensityError, DeviceBuffer, FormatError, HipError, HostMesher, InvalidArgument, LengthError, Marching, Mesher, MlsError,
-                      MlsFunctor, SPLAT_DTYPE, SplatTree, Swathe, Worker, WorkerConfig, lib, library_path)
+                      MlsFunctor, SPLAT_DTYPE, SplatTree, Swathe, Topology, Worker, WorkerConfig, lib, library_path, mesh_topology)
 
 __all__ = ["BucketFarm", "Context", "DensityError", "DeviceBuffer", "FormatError", "HipError", "HostMesher", "InvalidArgument", "LengthError", "Marching", "Mesher", "MlsError",
-           "MlsFunctor", "SPLAT_DTYPE", "SplatTree", "Swathe", "Worker", "WorkerConfig", "lib", "library_path"]
+           "MlsFunctor", "SPLAT_DTYPE", "SplatTree", "Swathe", "Topology", "Worker", "WorkerConfig", "lib", "library_path", "mesh_topology"]

@@ -116,6 +116,20 @@ class FarmConfig(C.Structure):
                 ("spare", C.c_uint32), ("worker", WorkerConfig), ("copyThreads", C.c_uint32), ("stagingBuffers", C.c_uint32)]
 
 
+class Topology(C.Structure):
+    """mlsgpu_topology: the count-all form of Manifold::isManifold (test/manifold.h:98-232)."""
+    _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("count", C.c_uint64 * 6),
+                ("firstOf", C.c_uint64 * 6), ("duplicateEdges", C.c_uint64), ("boundaryEdges", C.c_uint64),
+                ("edges", C.c_uint64), ("numComponents", C.c_uint64), ("numBoundaries", C.c_uint64),
+                ("eulerCharacteristic", C.c_int64), ("firstIndex", C.c_uint64), ("firstKind", C.c_uint32),
+                ("manifold", C.c_uint32)]
+
+
+# MLSGPU_TOPO_*: the index into Topology.count / firstOf, and firstKind
+TOPO_OUT_OF_RANGE, TOPO_DEGENERATE, TOPO_ISOLATED, TOPO_DUPLICATED, TOPO_MIXED, TOPO_TUNNEL, TOPO_NONE = range(7)
+TOPO_NAMES = ("out_of_range", "degenerate", "isolated", "duplicated", "mixed", "tunnel", "none")
+
+
 FARM_OUTPUT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.POINTER(Mesh))
 FARM_HOST_OUTPUT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.POINTER(HostMesh))
 
@@ -300,6 +314,9 @@ def lib():
     sig("mlsgpu_hip_mesher_finalize", C.c_int, vp, P(u32))
     sig("mlsgpu_hip_mesher_chunk", C.c_int, vp, u32, P(u64), P(u64), P(u64), P(vp), P(vp))
     sig("mlsgpu_hip_mesher_stats", C.c_int, vp, vp)
+    sig("mlsgpu_hip_mesh_topology", C.c_int, vp, vp, u64, u64, P(Topology))
+    sig("mlsgpu_hip_mesher_chunk_topology", C.c_int, vp, u32, P(Topology))
+    sig("mlsgpu_hip_topology_reason", u64, P(Topology), C.c_char_p, u64)
     sig("mlsgpu_hip_write_ply", C.c_int, C.c_char_p, vp, u64, vp, u64, vp, u32)
     sig("mlsgpu_hip_bucket", C.c_int, vp, vp, u64, P(GridStruct), P(BucketParams), BUCKET_FN, vp, P(u64))
     sig("mlsgpu_hip_bucket_load", C.c_int, vp, vp, vp, u64, P(GridStruct), vp)
@@ -802,6 +819,12 @@ class Mesher:
             out["vertices"], out["triangles"] = v, t
         return out
 
+    def chunk_topology(self, i):
+        """The topology report (mesh_topology) of output chunk i, computed where the chunk lies."""
+        t = Topology()
+        check(lib().mlsgpu_hip_mesher_chunk_topology(self.h, i, C.byref(t)))
+        return t
+
     def write_ply(self, i, path, comments=(), buffer_bytes=0):
         """Output chunk i straight from HBM into FastPly::Writer's file through a bounded pinned buffer."""
         arr = (C.c_char_p * max(len(comments), 1))(*[c.encode("ascii") for c in comments])
@@ -825,6 +848,33 @@ class Mesher:
             self.close()
         except Exception:
             pass
+
+
+def mesh_topology(ctx, triangles, num_vertices, num_triangles=None):
+    """Manifold::isManifold (test/manifold.h:98-232) on the device, in its count-all form: a Topology.  `triangles` is a
+    numpy array of index triples (uploaded for the call) or a DeviceBuffer of uint32 triples; num_triangles defaults to
+    all of it."""
+    t = Topology()
+    if isinstance(triangles, DeviceBuffer):
+        n = triangles.nbytes // 12 if num_triangles is None else num_triangles
+        check(lib().mlsgpu_hip_mesh_topology(ctx.h, triangles.ptr, n, num_vertices, C.byref(t)))
+        return t
+    tri = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    n = len(tri) if num_triangles is None else num_triangles
+    buf = DeviceBuffer(ctx, array=tri) if tri.size else None
+    try:
+        check(lib().mlsgpu_hip_mesh_topology(ctx.h, buf.ptr if buf else None, n, num_vertices, C.byref(t)))
+    finally:
+        if buf is not None:
+            buf.free()
+    return t
+
+
+def reason(t):
+    """Manifold::isManifold's return value for a Topology: '' if manifold, else a sentence about the first defect."""
+    buf = C.create_string_buffer(128)
+    lib().mlsgpu_hip_topology_reason(C.byref(t), buf, len(buf))
+    return buf.value.decode("ascii")
 
 
 class MesherCollector:

@@ -22,6 +22,7 @@
  */
 #include "common.hpp"
 #include "primitives.hpp"
+#include "unionfind.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -120,49 +121,6 @@ __global__ void externalRepsKernel(const uint64_t *keys, const uint32_t *slots, 
     outRep[g] = extGid[slots[o]];
 }
 
-/* parent[] is read while other workgroups hook roots: the loads must come from the coherence point (a line cached
- * in this CU's vector L1 would never show the new parent and the retry loop below would not end) */
-__device__ __forceinline__ uint32_t loadParent(const uint32_t *parent, uint32_t v)
-{
-    return __hip_atomic_load(&parent[v], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ uint32_t findRoot(const uint32_t *parent, uint32_t v)
-{
-    uint32_t p = loadParent(parent, v);
-    while (p != v)
-    {
-        v = p;
-        p = loadParent(parent, v);
-    }
-    return v;
-}
-
-/* findRoot that shortens LONG walks: a start vertex more than `shortcut` steps from its root is re-parented to the root.
- * Parents only ever point to SMALLER ids and hooks re-parent roots only, so an ancestor stays an ancestor whatever the other
- * workgroups do meanwhile: a stale or lost store costs time, never correctness, and the root of a finished component is its
- * smallest id either way (the result does not depend on the schedule).  Measured: unconditional pointer jumping (a store
- * per step) takes the shells cloud's finalize from 17.4 to 14.3 ms but the noise cloud's from 96.5 to 115.9 (its chains are
- * short already: the stores are pure cost there); the shortcut beyond 1 / 3 / 8 steps: shells 13.3 / 12.8 / 14.1 ms, noise
- * 113.9 / 103.9 / 96.3 against 17.9 and 97.4 without.
- * Round 4: the threshold is a launch parameter chosen by the size of the mesh (unionShortcut below): surface-like jobs (tens of
- * millions of vertices in a handful of sheets: long chains) take 3, the hundreds of millions of vertices of a noise cloud 8. */
-__device__ __forceinline__ uint32_t findRootHalving(uint32_t *parent, uint32_t v, uint32_t shortcut)
-{
-    const uint32_t start = v;
-    uint32_t steps = 0;
-    uint32_t p = loadParent(parent, v);
-    while (p != v)
-    {
-        v = p;
-        p = loadParent(parent, v);
-        steps++;
-    }
-    if (steps > shortcut)
-        __hip_atomic_store(&parent[start], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return v;
-}
-
 /* union of the endpoints of two edges per triangle (the third is redundant, src/mesher.cpp:231-234) */
 __global__ void unionKernel(const uint32_t *tri, uint64_t nt, const uint32_t *compRep, uint32_t *parent, uint32_t *failed,
                             uint32_t shortcut)
@@ -174,26 +132,7 @@ __global__ void unionKernel(const uint32_t *tri, uint64_t nt, const uint32_t *co
 #pragma unroll
     for (int e = 0; e < 2; e++)
     {
-        uint32_t a = v[e], b = v[e + 1];
-        for (uint32_t attempt = 0;; attempt++)
-        {
-            if (attempt == (1u << 20))      /* cannot happen; a bound instead of a hung GPU if it ever does */
-            {
-                *failed = 1;
-                break;
-            }
-            a = findRootHalving(parent, a, shortcut);
-            b = findRootHalving(parent, b, shortcut);
-            if (a == b)
-                break;
-            if (a < b)
-            {
-                const uint32_t s = a; a = b; b = s;
-            }
-            /* hook the larger root under the smaller; retry if someone re-parented it first */
-            if (atomicCAS(&parent[a], a, b) == a)
-                break;
-        }
+        unite(parent, v[e], v[e + 1], failed, shortcut);
     }
 }
 
@@ -1264,6 +1203,17 @@ MLSGPU_API int mlsgpu_hip_mesher_chunk(mlsgpu_mesher *m, uint32_t i, uint64_t *c
     if (dVertices) *dVertices = m->outVertices + 3 * m->chunkVStart[c];
     if (dTriangles) *dTriangles = m->outTriangles + 3 * m->chunkTStart[c];
     return MLSGPU_OK;
+}
+
+/* the topology report (topology.hip) of output chunk i, where it lies */
+MLSGPU_API int mlsgpu_hip_mesher_chunk_topology(mlsgpu_mesher *m, uint32_t i, mlsgpu_topology *out)
+{
+    REQUIRE(m != nullptr && out != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized && i < m->outChunks.size(), MLSGPU_ERR_INVALID);
+    const uint32_t c = m->outChunks[i];
+    return mlsgpu_hip_mesh_topology(m->ctx, m->outTriangles + 3 * m->chunkTStart[c], m->chunkTStart[c + 1] - m->chunkTStart[c],
+                                    m->chunkVStart[c + 1] - m->chunkVStart[c], out);
 }
 
 MLSGPU_API int mlsgpu_hip_mesher_stats(mlsgpu_mesher *m, uint64_t out[8])

@@ -98,6 +98,41 @@ public:
     }
 };
 
+/// namespace Manifold of test/manifold.h for a mesh in device memory
+namespace Manifold
+{
+struct Metadata                 // test/manifold.h:53-75
+{
+    std::size_t numVertices, numTriangles, numComponents, numBoundaries;
+    Metadata() : numVertices(0), numTriangles(0), numComponents(0), numBoundaries(0) {}
+};
+inline std::string reason(const mlsgpu_topology &t)
+{
+    char text[128];
+    mlsgpu_hip_topology_reason(&t, text, sizeof(text));
+    return text;
+}
+/// Manifold::isManifold: "" if manifold (then *data is filled), else a sentence about the first defect (*data all zero).
+inline std::string isManifold(const Context &ctx, const Buffer<std::uint32_t> &triangles, std::uint64_t numTriangles,
+                              std::uint64_t numVertices, Metadata *data = NULL)
+{
+    mlsgpu_topology t;
+    check(mlsgpu_hip_mesh_topology(ctx.get(), triangles.get(), numTriangles, numVertices, &t));
+    if (data != NULL)
+    {
+        *data = Metadata();
+        if (t.manifold)
+        {
+            data->numVertices = t.numVertices;
+            data->numTriangles = t.numTriangles;
+            data->numComponents = t.numComponents;
+            data->numBoundaries = t.numBoundaries;
+        }
+    }
+    return reason(t);
+}
+} // namespace Manifold
+
 typedef mlsgpu_splat Splat;                 // src/splat.h:40-46
 enum MlsShape { MLS_SHAPE_SPHERE = MLSGPU_SHAPE_SPHERE, MLS_SHAPE_PLANE = MLSGPU_SHAPE_PLANE };  // src/mls.h:47-51
 
@@ -594,6 +629,13 @@ public:
         return chunks;
     }
     void getStatistics(std::uint64_t out[8]) const { check(mlsgpu_hip_mesher_stats(h, out)); }
+    /// The topology report of output chunk i of the last write(), computed on the device (Manifold::reason words it).
+    mlsgpu_topology topology(std::uint32_t i) const
+    {
+        mlsgpu_topology t;
+        check(mlsgpu_hip_mesher_chunk_topology(h, i, &t));
+        return t;
+    }
 };
 
 /**
