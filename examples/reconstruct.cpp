@@ -12,10 +12,12 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--simplify N] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
  * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
+ * --simplify N (device weld only, N > 0): before the write, every output chunk is vertex-clustered where it lies, in cells of
+ *   N grid spacings counted from one cell below the bounding grid's low corner; one line with the statistics.
  */
 #include <cstdio>
 #include <cstdlib>
@@ -35,6 +37,8 @@ int main(int argc, char **argv)
     std::vector<std::int32_t> devices(1, 0);
     bool hostWeld = false, checkTopology = false;
     std::uint64_t bufferBytes = 0, hbmSplats = 0;
+    float simplifyCells = 0.0f;
+    bool simplifyGiven = false;
     std::string tmpDir;
     std::vector<std::string> plys, rest;
     for (int i = 1; i < argc; i++)
@@ -52,6 +56,11 @@ int main(int argc, char **argv)
             hostWeld = std::string(argv[++i]) == "host";
         else if (a == "--check")
             checkTopology = true;
+        else if (a == "--simplify" && i + 1 < argc)
+        {
+            simplifyCells = (float) atof(argv[++i]);
+            simplifyGiven = true;
+        }
         else if (a == "--buffer" && i + 1 < argc)
             bufferBytes = strtoull(argv[++i], NULL, 10);
         else if (a == "--tmp-dir" && i + 1 < argc)             // --weld host: the welder's blocks in temporary files there (src/mlsgpu_core.cpp --tmp-dir)
@@ -65,8 +74,18 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--simplify N] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
+        return 2;
+    }
+    if (simplifyGiven && !(simplifyCells > 0.0f && simplifyCells <= std::numeric_limits<float>::max()))
+    {
+        std::cerr << "--simplify takes a number of grid spacings > 0\n";
+        return 2;
+    }
+    if (simplifyGiven && hostWeld)
+    {
+        std::cerr << "--simplify needs --weld device: the host welder's output is not on the device\n";
         return 2;
     }
     const std::string outName = plys.back();
@@ -127,6 +146,8 @@ int main(int argc, char **argv)
             hostMesher.setTmpDir(tmpDir, 0);
         std::size_t bins = 0, written = 0;
         std::uint64_t st[8];
+        mlsgpu_simplify_stats simplified = mlsgpu_simplify_stats();
+        float simplifyCell = 0.0f, simplifyOrigin[3] = {0.0f, 0.0f, 0.0f};
         {
             BucketFarm farm(devices, cfg, 4 /* --device-threads */, 1, hostWeld ? NULL : &deviceMesher);
             if (hostWeld)
@@ -156,7 +177,15 @@ int main(int argc, char **argv)
         }
         else
         {
-            written = deviceMesher.write([&](std::uint64_t) { return outName; }, comments);
+            const std::size_t chunks = deviceMesher.finalize();
+            if (simplifyGiven)
+            {
+                simplifyCell = simplifyCells * spacing;
+                for (int i = 0; i < 3; i++)
+                    simplifyOrigin[i] = cfg.gridOrigin[i] - simplifyCell;
+                simplified = deviceMesher.simplify(simplifyOrigin, simplifyCell);
+            }
+            written = deviceMesher.writeChunks(chunks, [&](std::uint64_t) { return outName; }, comments);
             deviceMesher.getStatistics(st);
         }
         std::printf("files in %zu splats %llu grid %d..%d %d..%d %d..%d bins %zu devices %zu weld %s files %zu vertices %llu "
@@ -165,6 +194,13 @@ int main(int argc, char **argv)
                     grid.extents[3], grid.extents[4], grid.extents[5], bins, devices.size(), hostWeld ? "host" : "device",
                     written, (unsigned long long) st[4], (unsigned long long) st[5], (unsigned long long) st[2],
                     (unsigned long long) st[3]);
+        if (simplifyGiven)
+            std::printf("simplify cell %.9g origin %.9g %.9g %.9g vertices %llu -> %llu triangles %llu -> %llu collapsed %llu "
+                        "duplicate %llu\n",
+                        simplifyCell, simplifyOrigin[0], simplifyOrigin[1], simplifyOrigin[2],
+                        (unsigned long long) simplified.inVertices, (unsigned long long) simplified.outVertices,
+                        (unsigned long long) simplified.inTriangles, (unsigned long long) simplified.outTriangles,
+                        (unsigned long long) simplified.collapsedTriangles, (unsigned long long) simplified.duplicateTriangles);
         if (checkTopology && !hostWeld)
             for (std::uint32_t i = 0; i < written; i++)
             {

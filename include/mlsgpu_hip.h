@@ -651,6 +651,54 @@ int mlsgpu_hip_mesher_chunk_topology(mlsgpu_mesher *mesher, uint32_t i, mlsgpu_t
  * triangle is not repeated).  At most len - 1 characters and a terminator are written to buf (which may be NULL); returns
  * the length of the whole sentence. */
 uint64_t mlsgpu_hip_topology_reason(const mlsgpu_topology *t, char *buf, uint64_t len);
+
+/* ---- vertex-clustering simplification of a device-resident mesh, so that a smaller mesh crosses the link.  The reference
+ *      has no counterpart: its meshes leave the device whole (src/mesher.cpp:763-852) and are decimated by other tools.
+ *      Deterministic: every float and double operation below is ONE correctly rounded IEEE operation (no contraction), and
+ *      every sum is an integer sum.
+ *      1. The cell of a vertex, per axis: c = floorf((p - origin) / cellSize) in float.  A vertex is invalid if a coordinate
+ *         is not finite or a c lies outside [0, 2^21).  key = z << 42 | y << 21 | x.
+ *      2. A cluster is the set of vertices with one key; clusters are ordered by ascending key.
+ *      3. A cluster of one member keeps that member's position bit for bit.  Otherwise, per axis in double:
+ *         d = p - origin, f = d / cellSize - c, q = llrint(f * 2^30); S = the int64 sum of q over the n members;
+ *         mean = (S / n) * 2^-30; out = (float) (origin + (c + mean) * cellSize).
+ *      4. Every index is replaced by its cluster.  A triangle with two equal clusters is collapsed and dropped; a survivor
+ *         is rotated (which keeps its orientation) so that its smallest cluster comes first; survivors are ordered by
+ *         (first, second, third) and of a run of equal triples one is kept -- (a, b, c) and (a, c, b) both stay.
+ *      5. The output vertices are the clusters a kept triangle uses, numbered densely in key order; clusters nothing uses
+ *         (and input vertices no triangle used) disappear.
+ *      Clustering can make a mesh non-manifold: mlsgpu_hip_mesh_topology says whether it did. ---- */
+typedef struct mlsgpu_simplify_stats
+{
+    uint64_t inVertices, inTriangles;
+    uint64_t outVertices, outTriangles;
+    uint64_t collapsedTriangles;    /* two of the three clusters equal */
+    uint64_t duplicateTriangles;    /* equal to a kept triangle: inTriangles = outTriangles + collapsed + duplicate */
+} mlsgpu_simplify_stats;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_simplify_stats) == 48, "mlsgpu_simplify_stats is part of the ABI");
+#else
+typedef char mlsgpu_simplify_stats_size_is_48[sizeof(mlsgpu_simplify_stats) == 48 ? 1 : -1];
+#endif
+/* numVertices packed float xyz and numTriangles uint32 index triples on ctx's device -> dOutVertices / dOutTriangles, which
+ * the caller allocates with room for the INPUT's sizes (the result is never larger; its sizes are in *stats) and which must
+ * not overlap the inputs.  MLSGPU_ERR_INVALID for a cellSize that is not finite or <= 0, a non-finite origin, an invalid
+ * vertex or a triangle index >= numVertices (counted on the device: compared, never used as an address); nothing is promised
+ * about the outputs then.  MLSGPU_ERR_LENGTH if 3 * numTriangles or numVertices does not fit 32 bits.  No vertices or no
+ * triangles is not an error: the result is an empty mesh.  Scratch is allocated for the call and freed on return: 60 bytes
+ * per vertex, 44 per triangle and the sorts' histogram; MLSGPU_ERR_NOMEM if the device does not have it.  Blocks until the
+ * statistics are there (one more stream synchronisation inside: the largest cells size the sort). */
+int mlsgpu_hip_mesh_simplify(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices, const uint32_t *dTriangles,
+                             uint64_t numTriangles, const float origin[3], float cellSize, float *dOutVertices,
+                             uint32_t *dOutTriangles, mlsgpu_simplify_stats *stats);
+/* The same for every output chunk of a finalized device sink, on the mesher's context: each chunk is replaced by its
+ * simplified mesh, the chunks are packed towards the front of the sink's output arrays, and mlsgpu_hip_mesher_chunk,
+ * _chunk_topology and _write_ply then serve the simplified chunks (a chunk that lost all its triangles stays in the list,
+ * empty).  *stats is the sum over the chunks; mlsgpu_hip_mesher_stats keeps reporting the finalize's numbers.  Chunks are
+ * simplified INDEPENDENTLY: the vertices two chunks share (the seams between split output files) are clustered with each
+ * chunk's own neighbours and are not matched afterwards.  MLSGPU_ERR_INVALID before finalize; may be called again (on the
+ * simplified chunks).  After an error the sink's results are dropped: finalize again. */
+int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *mesher, const float origin[3], float cellSize, mlsgpu_simplify_stats *stats);
 /* ---- host mesh sink: OOCMesher's weld as the reference runs it, on the host (src/mesher.cpp:220-469, north_star:
  *      "welding stays on host").  add() is MesherBase::InputFunctor: local components of the block by union-find over
  *      two edges per triangle (computeLocalComponents, :220-236), clumps merged across blocks through the external

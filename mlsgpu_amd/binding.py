@@ -125,6 +125,15 @@ class Topology(C.Structure):
                 ("manifold", C.c_uint32)]
 
 
+class SimplifyStats(C.Structure):
+    """mlsgpu_simplify_stats: inTriangles = outTriangles + collapsedTriangles + duplicateTriangles."""
+    _fields_ = [("inVertices", C.c_uint64), ("inTriangles", C.c_uint64), ("outVertices", C.c_uint64),
+                ("outTriangles", C.c_uint64), ("collapsedTriangles", C.c_uint64), ("duplicateTriangles", C.c_uint64)]
+
+    def as_dict(self):
+        return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
+
+
 # MLSGPU_TOPO_*: the index into Topology.count / firstOf, and firstKind
 TOPO_OUT_OF_RANGE, TOPO_DEGENERATE, TOPO_ISOLATED, TOPO_DUPLICATED, TOPO_MIXED, TOPO_TUNNEL, TOPO_NONE = range(7)
 TOPO_NAMES = ("out_of_range", "degenerate", "isolated", "duplicated", "mixed", "tunnel", "none")
@@ -317,6 +326,8 @@ def lib():
     sig("mlsgpu_hip_mesh_topology", C.c_int, vp, vp, u64, u64, P(Topology))
     sig("mlsgpu_hip_mesher_chunk_topology", C.c_int, vp, u32, P(Topology))
     sig("mlsgpu_hip_topology_reason", u64, P(Topology), C.c_char_p, u64)
+    sig("mlsgpu_hip_mesh_simplify", C.c_int, vp, vp, u64, vp, u64, P(f32), f32, vp, vp, P(SimplifyStats))
+    sig("mlsgpu_hip_mesher_simplify", C.c_int, vp, P(f32), f32, P(SimplifyStats))
     sig("mlsgpu_hip_write_ply", C.c_int, C.c_char_p, vp, u64, vp, u64, vp, u32)
     sig("mlsgpu_hip_bucket", C.c_int, vp, vp, u64, P(GridStruct), P(BucketParams), BUCKET_FN, vp, P(u64))
     sig("mlsgpu_hip_bucket_load", C.c_int, vp, vp, vp, u64, P(GridStruct), vp)
@@ -825,6 +836,14 @@ class Mesher:
         check(lib().mlsgpu_hip_mesher_chunk_topology(self.h, i, C.byref(t)))
         return t
 
+    def simplify(self, origin, cell_size):
+        """Every output chunk of the finalized sink replaced by its vertex-clustered mesh (mesh_simplify), where it lies:
+        chunk(), chunk_topology() and write_ply() then serve the simplified chunks.  Returns the statistics summed over
+        the chunks; stats() keeps the finalize's numbers."""
+        st = SimplifyStats()
+        check(lib().mlsgpu_hip_mesher_simplify(self.h, (C.c_float * 3)(*[float(x) for x in origin]), float(cell_size), C.byref(st)))
+        return st.as_dict()
+
     def write_ply(self, i, path, comments=(), buffer_bytes=0):
         """Output chunk i straight from HBM into FastPly::Writer's file through a bounded pinned buffer."""
         arr = (C.c_char_p * max(len(comments), 1))(*[c.encode("ascii") for c in comments])
@@ -868,6 +887,40 @@ def mesh_topology(ctx, triangles, num_vertices, num_triangles=None):
         if buf is not None:
             buf.free()
     return t
+
+
+def mesh_simplify(ctx, vertices, triangles, origin, cell_size, num_vertices=None, num_triangles=None):
+    """Vertex clustering on the device (mlsgpu_hip_mesh_simplify): vertices in one cell of side cell_size (cells counted from
+    `origin`) become one vertex at their mean, collapsed and repeated triangles go.  `vertices` / `triangles` are numpy
+    arrays (uploaded for the call) or DeviceBuffers of packed float32 xyz / uint32 triples.  Returns (vertices, triangles,
+    statistics as a dict), the arrays downloaded."""
+    own = []
+
+    def on_device(a, dtype, count):
+        if isinstance(a, DeviceBuffer):
+            return a, (a.nbytes // 12 if count is None else count)
+        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
+        buf = DeviceBuffer(ctx, array=a) if a.size else None
+        if buf is not None:
+            own.append(buf)
+        return buf, (len(a) if count is None else count)
+
+    st = SimplifyStats()
+    try:
+        dv, nv = on_device(vertices, np.float32, num_vertices)
+        dt, nt = on_device(triangles, np.uint32, num_triangles)
+        ov = DeviceBuffer(ctx, nbytes=12 * nv) if nv and dv is not None else None
+        ot = DeviceBuffer(ctx, nbytes=12 * nt) if nt and dt is not None else None
+        own.extend(x for x in (ov, ot) if x is not None)
+        check(lib().mlsgpu_hip_mesh_simplify(ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt,
+                                             (C.c_float * 3)(*[float(x) for x in origin]), float(cell_size),
+                                             ov.ptr if ov else None, ot.ptr if ot else None, C.byref(st)))
+        out_v = ov.download(np.float32, 3 * st.outVertices).reshape(-1, 3) if st.outVertices else np.zeros((0, 3), np.float32)
+        out_t = ot.download(np.uint32, 3 * st.outTriangles).reshape(-1, 3) if st.outTriangles else np.zeros((0, 3), np.uint32)
+    finally:
+        for buf in own:
+            buf.free()
+    return out_v, out_t, st.as_dict()
 
 
 def reason(t):

@@ -1216,6 +1216,67 @@ MLSGPU_API int mlsgpu_hip_mesher_chunk_topology(mlsgpu_mesher *m, uint32_t i, ml
                                     m->chunkVStart[c + 1] - m->chunkVStart[c], out);
 }
 
+/* Every output chunk through mlsgpu_hip_mesh_simplify (simplify.hip), into buffers of the chunk's size and from there to the
+ * front of the output arrays: a result is never larger than its chunk, so chunk c's lands at or before where chunk c began and
+ * never on a chunk that is still to be read. */
+MLSGPU_API int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *m, const float origin[3], float cellSize, mlsgpu_simplify_stats *stats)
+{
+    REQUIRE(m != nullptr && origin != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
+    mlsgpu_ctx *const ctx = m->ctx;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    std::memset(stats, 0, sizeof(*stats));
+    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
+    uint64_t maxV = 0, maxT = 0;
+    for (size_t c = 0; c < nc; c++)
+    {
+        maxV = std::max(maxV, m->chunkVStart[c + 1] - m->chunkVStart[c]);
+        maxT = std::max(maxT, m->chunkTStart[c + 1] - m->chunkTStart[c]);
+    }
+    DeviceArray<float> tmpV;
+    DeviceArray<uint32_t> tmpT;
+    PROPAGATE(tmpV.alloc(3 * maxV));
+    PROPAGATE(tmpT.alloc(3 * maxT));
+    uint64_t vAt = 0, tAt = 0;
+    for (size_t c = 0; c < nc; c++)
+    {
+        const uint64_t v0 = m->chunkVStart[c], t0 = m->chunkTStart[c];
+        const uint64_t nv = m->chunkVStart[c + 1] - v0, nt = m->chunkTStart[c + 1] - t0;
+        mlsgpu_simplify_stats one;
+        std::memset(&one, 0, sizeof(one));
+        int rc = MLSGPU_OK;
+        if (nt > 0)     /* a chunk without triangles has no output (finalize), and keeps none */
+            rc = mlsgpu_hip_mesh_simplify(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, origin, cellSize, tmpV, tmpT, &one);
+        if (rc == MLSGPU_OK && one.outVertices > 0
+            && hipMemcpyAsync(m->outVertices + 3 * vAt, tmpV, one.outVertices * 12, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+            rc = setError(MLSGPU_ERR_HIP, "mesher simplify: the copy of a chunk's vertices failed");
+        if (rc == MLSGPU_OK && one.outTriangles > 0
+            && hipMemcpyAsync(m->outTriangles + 3 * tAt, tmpT, one.outTriangles * 12, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+            rc = setError(MLSGPU_ERR_HIP, "mesher simplify: the copy of a chunk's triangles failed");
+        if (rc != MLSGPU_OK)
+        {
+            if (c > 0)
+                m->dropResults();       /* earlier chunks have moved: the chunk table no longer describes the arrays */
+            return rc;
+        }
+        m->chunkVStart[c] = vAt;
+        m->chunkTStart[c] = tAt;
+        vAt += one.outVertices;
+        tAt += one.outTriangles;
+        stats->inVertices += one.inVertices;
+        stats->inTriangles += one.inTriangles;
+        stats->outVertices += one.outVertices;
+        stats->outTriangles += one.outTriangles;
+        stats->collapsedTriangles += one.collapsedTriangles;
+        stats->duplicateTriangles += one.duplicateTriangles;
+    }
+    m->chunkVStart[nc] = vAt;
+    m->chunkTStart[nc] = tAt;
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));       /* the temporaries go with the call */
+    return MLSGPU_OK;
+}
+
 MLSGPU_API int mlsgpu_hip_mesher_stats(mlsgpu_mesher *m, uint64_t out[8])
 {
     REQUIRE(m != nullptr && out != nullptr && m->finalized, MLSGPU_ERR_INVALID);

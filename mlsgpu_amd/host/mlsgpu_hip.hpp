@@ -133,6 +133,18 @@ inline std::string isManifold(const Context &ctx, const Buffer<std::uint32_t> &t
 }
 } // namespace Manifold
 
+/// Vertex clustering of a mesh in device memory (mlsgpu_hip_mesh_simplify): outVertices / outTriangles have room for the
+/// input's sizes and do not overlap it; the result's sizes are in the returned statistics.
+inline mlsgpu_simplify_stats simplify(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
+                                      const Buffer<std::uint32_t> &triangles, std::uint64_t numTriangles, const float origin[3],
+                                      float cellSize, Buffer<float> &outVertices, Buffer<std::uint32_t> &outTriangles)
+{
+    mlsgpu_simplify_stats st;
+    check(mlsgpu_hip_mesh_simplify(ctx.get(), vertices.get(), numVertices, triangles.get(), numTriangles, origin, cellSize,
+                                   outVertices.get(), outTriangles.get(), &st));
+    return st;
+}
+
 typedef mlsgpu_splat Splat;                 // src/splat.h:40-46
 enum MlsShape { MLS_SHAPE_SPHERE = MLSGPU_SHAPE_SPHERE, MLS_SHAPE_PLANE = MLSGPU_SHAPE_PLANE };  // src/mls.h:47-51
 
@@ -608,11 +620,24 @@ public:
     }
     /// pinned host memory a write may hold (two buffers of half this; 0 = 64 MiB), whatever the size of the mesh
     std::uint64_t writeBufferBytes = 0;
-    /// MesherBase::write: returns the number of files written.
-    std::size_t write(const Namer &namer, const std::vector<std::string> &comments = std::vector<std::string>())
+    /// The first half of write(): weld, components, prune.  Returns the number of output chunks.
+    std::size_t finalize()
     {
         std::uint32_t chunks = 0;
         check(mlsgpu_hip_mesher_finalize(h, &chunks));
+        return chunks;
+    }
+    /// Every output chunk of the finalized mesher replaced by its vertex-clustered mesh (mlsgpu_hip_mesher_simplify);
+    /// between finalize() and writeChunks().  The statistics are summed over the chunks.
+    mlsgpu_simplify_stats simplify(const float origin[3], float cellSize)
+    {
+        mlsgpu_simplify_stats st;
+        check(mlsgpu_hip_mesher_simplify(h, origin, cellSize, &st));
+        return st;
+    }
+    /// The second half of write(): one file per chunk of the `chunks` that finalize() reported.
+    std::size_t writeChunks(std::size_t chunks, const Namer &namer, const std::vector<std::string> &comments = std::vector<std::string>())
+    {
         std::vector<const char *> cstr;
         for (const std::string &c : comments)
             cstr.push_back(c.c_str());
@@ -627,6 +652,11 @@ public:
                                               (std::uint32_t) cstr.size(), writeBufferBytes));
         }
         return chunks;
+    }
+    /// MesherBase::write: returns the number of files written.
+    std::size_t write(const Namer &namer, const std::vector<std::string> &comments = std::vector<std::string>())
+    {
+        return writeChunks(finalize(), namer, comments);
     }
     void getStatistics(std::uint64_t out[8]) const { check(mlsgpu_hip_mesher_stats(h, out)); }
     /// The topology report of output chunk i of the last write(), computed on the device (Manifold::reason words it).
