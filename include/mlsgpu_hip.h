@@ -859,6 +859,27 @@ int mlsgpu_hip_test_scan_u32_batch(mlsgpu_ctx *ctx, const uint32_t *const *dIn, 
                                    const uint32_t *seeds, uint32_t count, uint32_t repeats);
 int mlsgpu_hip_test_sort_u32(mlsgpu_ctx *ctx, uint32_t *dKeys, uint32_t *dValues, uint64_t n, uint32_t bits);
 int mlsgpu_hip_test_sort_u64(mlsgpu_ctx *ctx, uint64_t *dKeys, uint32_t *dValues, uint64_t n, uint32_t bits);
+/* The scan by element kind and form.  words: 1 scans uint32, 3 scans (a, b, c) triples of uint32 column by column (Marching's
+ * cells / vertices / indices).  form: the whole scan as its callers get it (one launch up to 1 024 tiles); the scan whose tile
+ * sums and prefixes are fed by two functor types (raw tile sums, then every workgroup adds up its predecessors'); or phase 1
+ * (tile sums scanned by one workgroup) followed by phase 2.  dIn -> dPrefix (exclusive prefix from `seed`) and dValues (the
+ * element as the consumer is handed it), n elements of `words` words each; *dTotal (`words` words on the device) = seed +
+ * sum.  dCount (optional, on the device): only the first min(n, *dCount) elements exist; nothing is written behind them. */
+#define MLSGPU_TEST_SCAN_WHOLE 0u
+#define MLSGPU_TEST_SCAN_TWO_INPUTS 1u
+#define MLSGPU_TEST_SCAN_PHASES 2u
+int mlsgpu_hip_test_scan(mlsgpu_ctx *ctx, uint32_t words, uint32_t form, const uint32_t *dIn, uint32_t *dPrefix,
+                         uint32_t *dValues, uint64_t n, const uint32_t seed[3], const uint32_t *dCount, uint32_t *dTotal);
+/* One batched sort of `count` (<= MLSGPU_MAX_BATCH) lanes of (key, value) pairs, keys of keyBytes (4 or 8) bytes, stable on key
+ * bits [doneBits, bits): lane k sorts (dKeys[k], dValues[k])[0 .. n[k]), or the first min(n[k], *dCount[k]) of them where
+ * dCount (optional, as may be each of its elements) names a count on the device.  iota: the values are the positions and
+ * dValues is not read.  doneBits: the input is sorted by that many low bits already.  keysWanted = 0: only the values are
+ * delivered.  The temporaries and the histogram are the entry point's own; it fails if anything was written behind a
+ * temporary's n[k] elements.  side[k] = 0 if lane k's result lies in dKeys[k] / dValues[k], 1 if in the temporaries; n[k]
+ * elements of it are copied to dKeysOut[k] / dValuesOut[k] where those (optional, as may be each element) are given. */
+int mlsgpu_hip_test_sort_batch(mlsgpu_ctx *ctx, uint32_t keyBytes, uint32_t count, void *const *dKeys, uint32_t *const *dValues,
+                               const uint64_t *n, const uint32_t *const *dCount, uint32_t bits, int iota, uint32_t doneBits,
+                               int keysWanted, void *const *dKeysOut, uint32_t *const *dValuesOut, uint32_t *side);
 
 #ifdef __cplusplus
 }

@@ -344,6 +344,8 @@ def lib():
     sig("mlsgpu_hip_test_scan_u32_batch", C.c_int, vp, vp, vp, vp, vp, u32, u32)
     sig("mlsgpu_hip_test_sort_u32", C.c_int, vp, vp, vp, u64, u32)
     sig("mlsgpu_hip_test_sort_u64", C.c_int, vp, vp, vp, u64, u32)
+    sig("mlsgpu_hip_test_scan", C.c_int, vp, u32, u32, vp, vp, vp, u64, P(u32), vp, vp)
+    sig("mlsgpu_hip_test_sort_batch", C.c_int, vp, u32, u32, vp, vp, vp, vp, u32, C.c_int, u32, C.c_int, vp, vp, P(u32))
     _lib = L
     return L
 

@@ -1110,73 +1110,3 @@ MLSGPU_API int mlsgpu_hip_test_point_box_dist2(mlsgpu_ctx *ctx, const float p[3]
     std::memcpy(out, &r, 4);
     return MLSGPU_OK;
 }
-
-/* ---- primitive tests ---- */
-MLSGPU_API int mlsgpu_hip_test_scan_u32(mlsgpu_ctx *ctx, uint32_t *dData, uint64_t n, uint32_t seed)
-{
-    REQUIRE(ctx != nullptr, MLSGPU_ERR_INVALID);
-    HIP_CHECK(hipSetDevice(ctx->device));
-    DeviceArray<uint32_t> dTiles;
-    PROPAGATE(dTiles.alloc((uint64_t) scanTiles(n) + 1));
-    int rc = exclusiveScan<uint32_t>(ctx, "test.scan", ArrayIn<uint32_t>{dData}, ArrayOut<uint32_t>{dData}, n, seed,
-                                     dTiles.get(), (uint32_t *) nullptr);
-    hipStreamSynchronize(ctx->stream);
-    return rc;
-}
-
-/* `repeats` scans of `count` lanes each (one set of launches per repeat, as the buckets of a batch), dIn[k] -> dOut[k],
- * enqueued back to back without a host synchronisation in between; returns when the last one has finished */
-MLSGPU_API int mlsgpu_hip_test_scan_u32_batch(mlsgpu_ctx *ctx, const uint32_t *const *dIn, uint32_t *const *dOut, const uint64_t *n,
-                                              const uint32_t *seeds, uint32_t count, uint32_t repeats)
-{
-    REQUIRE(ctx != nullptr && dIn != nullptr && dOut != nullptr && n != nullptr && seeds != nullptr, MLSGPU_ERR_INVALID);
-    REQUIRE(count >= 1 && count <= MAX_LANES, MLSGPU_ERR_LENGTH);
-    HIP_CHECK(hipSetDevice(ctx->device));
-    DeviceArray<uint32_t> dTiles[MAX_LANES];
-    typedef ScanJob<uint32_t, ArrayIn<uint32_t>, ArrayIn<uint32_t>, ArrayOut<uint32_t> > Job;
-    Job jobs[MAX_LANES];
-    int rc = MLSGPU_OK;
-    for (uint32_t k = 0; k < count && rc == MLSGPU_OK; k++)
-    {
-        rc = dTiles[k].alloc((uint64_t) scanTiles(n[k]) + 1);
-        jobs[k] = Job{ArrayIn<uint32_t>{dIn[k]}, ArrayIn<uint32_t>{dIn[k]}, ArrayOut<uint32_t>{dOut[k]}, n[k], seeds[k], dTiles[k],
-                      (uint32_t *) nullptr, (const uint32_t *) nullptr};
-    }
-    for (uint32_t r = 0; r < repeats && rc == MLSGPU_OK; r++)
-        rc = exclusiveScanBatch<uint32_t>(ctx, "test.scan", jobs, count);
-    hipStreamSynchronize(ctx->stream);
-    return rc;
-}
-
-template<typename K>
-static int testSort(mlsgpu_ctx *ctx, K *dKeys, uint32_t *dValues, uint64_t n, uint32_t bits)
-{
-    HIP_CHECK(hipSetDevice(ctx->device));
-    DeviceArray<K> kb;
-    DeviceArray<uint32_t> vb, hist, tiles;
-    PROPAGATE(kb.alloc(n + 1));
-    PROPAGATE(vb.alloc(n + 1));
-    PROPAGATE(hist.alloc(sortHistElems(n) + 1));
-    PROPAGATE(tiles.alloc((uint64_t) scanTiles(sortHistElems(n)) + 1));
-    SortResult<K> res;
-    int rc = radixSort<K>(ctx, "test.sort", dKeys, dValues, kb, vb, n, bits, false, hist, tiles, &res);
-    if (rc == MLSGPU_OK && res.keys != dKeys && n > 0)
-    {
-        hipMemcpyAsync(dKeys, res.keys, n * sizeof(K), hipMemcpyDeviceToDevice, ctx->stream);
-        hipMemcpyAsync(dValues, res.vals, n * 4, hipMemcpyDeviceToDevice, ctx->stream);
-    }
-    hipStreamSynchronize(ctx->stream);
-    return rc;
-}
-
-MLSGPU_API int mlsgpu_hip_test_sort_u32(mlsgpu_ctx *ctx, uint32_t *dKeys, uint32_t *dValues, uint64_t n, uint32_t bits)
-{
-    REQUIRE(ctx != nullptr, MLSGPU_ERR_INVALID);
-    return testSort<uint32_t>(ctx, dKeys, dValues, n, bits);
-}
-
-MLSGPU_API int mlsgpu_hip_test_sort_u64(mlsgpu_ctx *ctx, uint64_t *dKeys, uint32_t *dValues, uint64_t n, uint32_t bits)
-{
-    REQUIRE(ctx != nullptr, MLSGPU_ERR_INVALID);
-    return testSort<uint64_t>(ctx, dKeys, dValues, n, bits);
-}
