@@ -12,12 +12,14 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--simplify N] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--simplify N] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
  * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
  * --simplify N (device weld only, N > 0): before the write, every output chunk is vertex-clustered where it lies, in cells of
  *   N grid spacings counted from one cell below the bounding grid's low corner; one line with the statistics.
+ * --normals (device weld only): every output chunk is written with its area-weighted vertex normals (nx ny nz after z),
+ *   computed where the chunk lies -- after --simplify when both are given; one line per chunk.
  */
 #include <cstdio>
 #include <cstdlib>
@@ -35,7 +37,7 @@ static bool isPly(const std::string &a) { return a.size() > 4 && a.compare(a.siz
 int main(int argc, char **argv)
 {
     std::vector<std::int32_t> devices(1, 0);
-    bool hostWeld = false, checkTopology = false;
+    bool hostWeld = false, checkTopology = false, writeNormals = false;
     std::uint64_t bufferBytes = 0, hbmSplats = 0;
     float simplifyCells = 0.0f;
     bool simplifyGiven = false;
@@ -56,6 +58,8 @@ int main(int argc, char **argv)
             hostWeld = std::string(argv[++i]) == "host";
         else if (a == "--check")
             checkTopology = true;
+        else if (a == "--normals")
+            writeNormals = true;
         else if (a == "--simplify" && i + 1 < argc)
         {
             simplifyCells = (float) atof(argv[++i]);
@@ -74,7 +78,7 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--simplify N] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--simplify N] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
         return 2;
     }
@@ -86,6 +90,11 @@ int main(int argc, char **argv)
     if (simplifyGiven && hostWeld)
     {
         std::cerr << "--simplify needs --weld device: the host welder's output is not on the device\n";
+        return 2;
+    }
+    if (writeNormals && hostWeld)
+    {
+        std::cerr << "--normals needs --weld device: the host welder's output is not on the device\n";
         return 2;
     }
     const std::string outName = plys.back();
@@ -185,7 +194,7 @@ int main(int argc, char **argv)
                     simplifyOrigin[i] = cfg.gridOrigin[i] - simplifyCell;
                 simplified = deviceMesher.simplify(simplifyOrigin, simplifyCell);
             }
-            written = deviceMesher.writeChunks(chunks, [&](std::uint64_t) { return outName; }, comments);
+            written = deviceMesher.writeChunks(chunks, [&](std::uint64_t) { return outName; }, comments, writeNormals);
             deviceMesher.getStatistics(st);
         }
         std::printf("files in %zu splats %llu grid %d..%d %d..%d %d..%d bins %zu devices %zu weld %s files %zu vertices %llu "
@@ -201,6 +210,17 @@ int main(int argc, char **argv)
                         (unsigned long long) simplified.inVertices, (unsigned long long) simplified.outVertices,
                         (unsigned long long) simplified.inTriangles, (unsigned long long) simplified.outTriangles,
                         (unsigned long long) simplified.collapsedTriangles, (unsigned long long) simplified.duplicateTriangles);
+        if (writeNormals)
+            for (std::uint32_t i = 0; i < written; i++)
+            {
+                std::uint64_t id = 0;
+                check(mlsgpu_hip_mesher_chunk(deviceMesher.get(), i, &id, NULL, NULL, NULL, NULL));
+                const mlsgpu_normals_stats n = deviceMesher.normals(i);        // what the writer computed, served again
+                std::printf("normals chunk %llu vertices %llu zero %llu out-of-range %llu non-finite %llu exponent %lld\n",
+                            (unsigned long long) id, (unsigned long long) n.numVertices, (unsigned long long) n.zeroNormals,
+                            (unsigned long long) n.outOfRangeTriangles, (unsigned long long) n.nonFiniteTriangles,
+                            (long long) n.scaleExponent);
+            }
         if (checkTopology && !hostWeld)
             for (std::uint32_t i = 0; i < written; i++)
             {

@@ -699,6 +699,60 @@ int mlsgpu_hip_mesh_simplify(mlsgpu_ctx *ctx, const float *dVertices, uint64_t n
  * chunk's own neighbours and are not matched afterwards.  MLSGPU_ERR_INVALID before finalize; may be called again (on the
  * simplified chunks).  After an error the sink's results are dropped: finalize again. */
 int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *mesher, const float origin[3], float cellSize, mlsgpu_simplify_stats *stats);
+
+/* ---- area-weighted vertex normals of a device-resident mesh, so that what leaves the device can be shaded as it is.  The
+ *      reference has no counterpart: its files carry positions and faces (src/fast_ply.cpp:443-521).  Computed from the
+ *      FINISHED mesh (after prune, after a simplify, whose cluster means no MLS fit belongs to).  Deterministic: every float
+ *      and double operation below is ONE correctly rounded IEEE operation (no contraction), and every sum is an integer sum.
+ *      1. A triangle with an index >= V is counted in outOfRangeTriangles and takes no part (the index is compared, never
+ *         used as an address).
+ *      2. The face vector, in double: a = p1 - p0, b = p2 - p0 per axis on the float coordinates converted to double;
+ *         c = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x), each component two products and one subtraction.
+ *         If a component of c is not finite the triangle is counted in nonFiniteTriangles and takes no part.  A degenerate
+ *         triangle has c = 0 and adds nothing.
+ *      3. M = the largest |component| of c over the triangles that take part.  M == 0 (or no triangles): every normal is
+ *         zero and scaleExponent = 0.  Otherwise e is the integer with 2^e <= M < 2^(e + 1) (frexp's exponent minus 1; a
+ *         subnormal M has its true exponent), q = llrint(ldexp(component, 30 - e)) with ties to even -- |q| <= 2^31, so the
+ *         int64 sums of fewer than 2^32 / 3 triangles cannot overflow -- and scaleExponent = e.
+ *      4. S[v] = the int64 sum, per axis, of q over every corner of every participating triangle that is v.
+ *      5. x = (double) S per axis, l2 = (x.x*x.x + x.y*x.y) + x.z*x.z, l = sqrt(l2), normal = (float) (x / l) per axis.
+ *         l == 0: the normal is (0, 0, 0) and the vertex is counted in zeroNormals (vertices no triangle uses among them).
+ *      6. Orientation: c = cross(p1 - p0, p2 - p0) is what the triangle order gives.  The pipeline's closed surfaces have
+ *         positive signed volume (the field is negative inside), so these normals point OUT of the surface, the same way as
+ *         the input splats' normals.
+ *      Scaling every coordinate by a power of two leaves the normals bit for bit (and moves scaleExponent by twice the shift).
+ *      Limits: a triangle whose face vector is below 2^-31 of the largest one's quantises to nothing (meshes here have
+ *      triangles of one grid's size); the float coordinates of a finite mesh cannot overflow the double products. ---- */
+typedef struct mlsgpu_normals_stats
+{
+    uint64_t numVertices, numTriangles;
+    uint64_t outOfRangeTriangles;   /* an index >= numVertices */
+    uint64_t nonFiniteTriangles;    /* in range, but a component of the face vector is NaN or infinite */
+    uint64_t zeroNormals;           /* vertices whose sum is (0, 0, 0): unused, or all their triangles degenerate / too small */
+    int64_t scaleExponent;          /* e of step 3 */
+} mlsgpu_normals_stats;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_normals_stats) == 48, "mlsgpu_normals_stats is part of the ABI");
+#else
+typedef char mlsgpu_normals_stats_size_is_48[sizeof(mlsgpu_normals_stats) == 48 ? 1 : -1];
+#endif
+/* numVertices packed float xyz and numTriangles uint32 index triples on ctx's device -> dOutNormals, packed float xyz with
+ * room for 3 * numVertices floats, which must not overlap the inputs.  MLSGPU_ERR_LENGTH if 3 * numTriangles or numVertices
+ * does not fit 32 bits (checked before anything is allocated).  No vertices or no triangles is not an error.  Scratch is
+ * allocated for the call and freed on return: 24 bytes per vertex (the int64 sums) and four counters; MLSGPU_ERR_NOMEM if
+ * the device does not have it.  Blocks until the statistics are there: one stream synchronisation, at the end (M stays on
+ * the device).  MLSGPU_HIP_NORMALS_ACCUMULATE=plain takes the sums with nine atomics per triangle instead of combining the
+ * lanes of a wave that share a vertex first; the result is the same bit for bit. */
+int mlsgpu_hip_mesh_normals(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices, const uint32_t *dTriangles,
+                            uint64_t numTriangles, float *dOutNormals, mlsgpu_normals_stats *stats);
+/* The normals of output chunk i of a finalized device sink (the mesh of mlsgpu_hip_mesher_chunk), on the mesher's context:
+ * *dNormals is 3 floats per vertex of the chunk in an array the sink owns beside its vertices (allocated at the first call).
+ * A chunk is computed at its first request and served again afterwards; finalize, finalize_with, reset and
+ * mlsgpu_hip_mesher_simplify invalidate it, so normals requested after a simplify are those of the simplified chunk.
+ * MLSGPU_ERR_INVALID before finalize.  Chunks are INDEPENDENT, as for simplify: a vertex two chunks share gets, in each
+ * chunk, the sum over that chunk's triangles only -- the seams between split output files are not matched.  dNormals and
+ * stats may each be NULL. */
+int mlsgpu_hip_mesher_chunk_normals(mlsgpu_mesher *mesher, uint32_t i, const float **dNormals, mlsgpu_normals_stats *stats);
 /* ---- host mesh sink: OOCMesher's weld as the reference runs it, on the host (src/mesher.cpp:220-469, north_star:
  *      "welding stays on host").  add() is MesherBase::InputFunctor: local components of the block by union-find over
  *      two edges per triangle (computeLocalComponents, :220-236), clumps merged across blocks through the external
@@ -779,6 +833,18 @@ int mlsgpu_hip_mesher_write_ply(mlsgpu_mesher *mesher, uint32_t i, const char *p
  * float32 x y z, faces as uint8 3 + 3 x uint32 */
 int mlsgpu_hip_write_ply(const char *path, const float *vertices, uint64_t numVertices, const uint32_t *triangles,
                          uint64_t numTriangles, const char *const *comments, uint32_t numComments);
+
+/* The same files with the vertex normals: property float32 nx / ny / nz after z, 24-byte vertex rows, everything else as
+ * above.  Host memory in (normals: 3 floats per vertex) ... */
+int mlsgpu_hip_write_ply_normals(const char *path, const float *vertices, const float *normals, uint64_t numVertices,
+                                 const uint32_t *triangles, uint64_t numTriangles, const char *const *comments,
+                                 uint32_t numComments);
+/* ... or output chunk i of a finalized mesher straight from HBM through the two pinned buffers of
+ * mlsgpu_hip_mesher_write_ply, the rows interleaved on the device as the faces are packed: the chunk's normals are those of
+ * mlsgpu_hip_mesher_chunk_normals, computed now if nobody asked for them yet.  Same bytes as mlsgpu_hip_write_ply_normals of
+ * the downloaded arrays. */
+int mlsgpu_hip_mesher_write_ply_normals(mlsgpu_mesher *mesher, uint32_t i, const char *path, const char *const *comments,
+                                        uint32_t numComments, uint64_t bufferBytes);
 
 /* ---- splat input: FastPly::Reader, src/fast_ply.h:77-262; host only ---- */
 typedef struct mlsgpu_ply_reader mlsgpu_ply_reader;

@@ -134,6 +134,15 @@ class SimplifyStats(C.Structure):
         return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
 
 
+class NormalsStats(C.Structure):
+    """mlsgpu_normals_stats: what took no part, the vertices left without a normal, and the scale's exponent."""
+    _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
+                ("nonFiniteTriangles", C.c_uint64), ("zeroNormals", C.c_uint64), ("scaleExponent", C.c_int64)]
+
+    def as_dict(self):
+        return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
+
+
 # MLSGPU_TOPO_*: the index into Topology.count / firstOf, and firstKind
 TOPO_OUT_OF_RANGE, TOPO_DEGENERATE, TOPO_ISOLATED, TOPO_DUPLICATED, TOPO_MIXED, TOPO_TUNNEL, TOPO_NONE = range(7)
 TOPO_NAMES = ("out_of_range", "degenerate", "isolated", "duplicated", "mixed", "tunnel", "none")
@@ -329,6 +338,10 @@ def lib():
     sig("mlsgpu_hip_mesh_simplify", C.c_int, vp, vp, u64, vp, u64, P(f32), f32, vp, vp, P(SimplifyStats))
     sig("mlsgpu_hip_mesher_simplify", C.c_int, vp, P(f32), f32, P(SimplifyStats))
     sig("mlsgpu_hip_write_ply", C.c_int, C.c_char_p, vp, u64, vp, u64, vp, u32)
+    sig("mlsgpu_hip_mesh_normals", C.c_int, vp, vp, u64, vp, u64, vp, P(NormalsStats))
+    sig("mlsgpu_hip_mesher_chunk_normals", C.c_int, vp, u32, P(vp), P(NormalsStats))
+    sig("mlsgpu_hip_write_ply_normals", C.c_int, C.c_char_p, vp, vp, u64, vp, u64, vp, u32)
+    sig("mlsgpu_hip_mesher_write_ply_normals", C.c_int, vp, C.c_uint32, C.c_char_p, vp, C.c_uint32, u64)
     sig("mlsgpu_hip_bucket", C.c_int, vp, vp, u64, P(GridStruct), P(BucketParams), BUCKET_FN, vp, P(u64))
     sig("mlsgpu_hip_bucket_load", C.c_int, vp, vp, vp, u64, P(GridStruct), vp)
     sig("mlsgpu_hip_fileset_bounding_grid", C.c_int, vp, vp, C.c_float, C.c_uint32, u64, C.c_uint32, P(GridStruct))
@@ -852,6 +865,26 @@ class Mesher:
         check(lib().mlsgpu_hip_mesher_write_ply(self.h, i, str(path).encode(), C.cast(arr, C.c_void_p) if comments else None,
                                                 len(comments), buffer_bytes))
 
+    def chunk_normals(self, i, download=True):
+        """The area-weighted vertex normals (mesh_normals) of output chunk i, computed where the chunk lies at the first
+        request and served again until a finalize, reset or simplify: dict(d_normals=device address, stats=dict) and,
+        downloaded, normals float32 [V, 3]."""
+        st, pn = NormalsStats(), C.c_void_p()
+        check(lib().mlsgpu_hip_mesher_chunk_normals(self.h, i, C.byref(pn), C.byref(st)))
+        out = dict(d_normals=pn.value, stats=st.as_dict())
+        if download:
+            n = np.empty((st.numVertices, 3), np.float32)
+            if n.size:
+                check(lib().mlsgpu_hip_memcpy_d2h(self.ctx.h, _p(n), pn.value, n.nbytes, 0))
+            out["normals"] = n
+        return out
+
+    def write_ply_normals(self, i, path, comments=(), buffer_bytes=0):
+        """write_ply with the chunk's normals (chunk_normals, computed now if need be) as nx ny nz after z."""
+        arr = (C.c_char_p * max(len(comments), 1))(*[c.encode("ascii") for c in comments])
+        check(lib().mlsgpu_hip_mesher_write_ply_normals(self.h, i, str(path).encode(), C.cast(arr, C.c_void_p) if comments else None,
+                                                        len(comments), buffer_bytes))
+
     def stats(self):
         out = np.zeros(8, np.uint64)
         check(lib().mlsgpu_hip_mesher_stats(self.h, _p(out)))
@@ -923,6 +956,47 @@ def mesh_simplify(ctx, vertices, triangles, origin, cell_size, num_vertices=None
         for buf in own:
             buf.free()
     return out_v, out_t, st.as_dict()
+
+
+def mesh_normals(ctx, vertices, triangles, num_vertices=None, num_triangles=None):
+    """Area-weighted vertex normals on the device (mlsgpu_hip_mesh_normals), bit-reproducible whatever the schedule.
+    `vertices` / `triangles` are numpy arrays (uploaded for the call) or DeviceBuffers of packed float32 xyz / uint32
+    triples.  Returns (normals float32 [V, 3] downloaded, statistics as a dict)."""
+    own = []
+
+    def on_device(a, dtype, count):
+        if isinstance(a, DeviceBuffer):
+            return a, (a.nbytes // 12 if count is None else count)
+        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
+        buf = DeviceBuffer(ctx, array=a) if a.size else None
+        if buf is not None:
+            own.append(buf)
+        return buf, (len(a) if count is None else count)
+
+    st = NormalsStats()
+    try:
+        dv, nv = on_device(vertices, np.float32, num_vertices)
+        dt, nt = on_device(triangles, np.uint32, num_triangles)
+        on = DeviceBuffer(ctx, nbytes=12 * nv) if nv and dv is not None else None
+        if on is not None:
+            own.append(on)
+        check(lib().mlsgpu_hip_mesh_normals(ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt,
+                                            on.ptr if on else None, C.byref(st)))
+        out = on.download(np.float32, 3 * nv).reshape(-1, 3) if on is not None else np.zeros((0, 3), np.float32)
+    finally:
+        for buf in own:
+            buf.free()
+    return out, st.as_dict()
+
+
+def mesher_chunk_normals(mesher, i, download=True):
+    """Mesher.chunk_normals as a function, beside mesh_normals."""
+    return mesher.chunk_normals(i, download)
+
+
+def mesher_write_ply_normals(mesher, i, path, comments=(), buffer_bytes=0):
+    """Mesher.write_ply_normals as a function, beside write_ply_normals."""
+    mesher.write_ply_normals(i, path, comments, buffer_bytes)
 
 
 def reason(t):
@@ -1167,6 +1241,18 @@ def write_ply(path, vertices, triangles, comments=()):
     arr = (C.c_char_p * max(len(comments), 1))(*[c.encode("ascii") for c in comments])
     check(lib().mlsgpu_hip_write_ply(str(path).encode(), _p(vertices), len(vertices), _p(triangles), len(triangles),
                                      arr, len(comments)))
+
+
+def write_ply_normals(path, vertices, normals, triangles, comments=()):
+    """write_ply's file with property float32 nx ny nz after z (24-byte vertex rows)."""
+    vertices = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    triangles = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    if len(normals) != len(vertices):
+        raise ValueError("write_ply_normals: %d normals for %d vertices" % (len(normals), len(vertices)))
+    arr = (C.c_char_p * max(len(comments), 1))(*[c.encode("ascii") for c in comments])
+    check(lib().mlsgpu_hip_write_ply_normals(str(path).encode(), _p(vertices), _p(normals), len(vertices), _p(triangles),
+                                             len(triangles), arr, len(comments)))
 
 
 class Marching:

@@ -510,6 +510,11 @@ struct mlsgpu_mesher
     std::vector<uint64_t> chunkVStart, chunkTStart;     /* [chunks + 1] */
     std::vector<uint32_t> outChunks;                    /* dense chunk indices that have triangles */
     uint64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    /* vertex normals (mlsgpu_hip_mesher_chunk_normals): beside outVertices, a chunk's filled at its first request; whatever
+     * changes the outputs empties normalsOf */
+    DeviceArray<float> outNormals;              /* 3 per vertex */
+    std::vector<char> normalsReady;             /* per dense chunk */
+    std::vector<mlsgpu_normals_stats> normalsOf;
     /* boundary export (mlsgpu_hip_mesher_boundary): valid until the next add */
     bool analyzed = false;
     /* the export's keys and their roots land in PINNED memory (tens of MB: a copy into pageable memory goes through the
@@ -576,7 +581,9 @@ struct mlsgpu_mesher
         return MLSGPU_OK;
     }
     int regroupByChunk();
-    void dropResults() { finalized = false; }
+    void dropNormals() { normalsReady.clear(); }
+    void dropResults() { finalized = false; dropNormals(); }
+    int chunkNormals(uint32_t c, const float **dNormals, mlsgpu_normals_stats *out);
     int finalizeImpl(uint32_t *numChunks, bool analyzeOnly, const uint8_t *keepRoots, uint64_t numRoots);
     ~mlsgpu_mesher()
     {
@@ -789,7 +796,7 @@ MLSGPU_API int mlsgpu_hip_mesher_reset(mlsgpu_mesher *m)
     m->blocks.clear();
     m->chunkIds.clear();
     m->outChunks.clear();
-    m->finalized = false;
+    m->dropResults();
     m->analyzed = false;
     m->cacheKind = 0;
     return MLSGPU_OK;
@@ -1226,6 +1233,7 @@ MLSGPU_API int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *m, const float origin[3
     REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
     mlsgpu_ctx *const ctx = m->ctx;
     HIP_CHECK(hipSetDevice(ctx->device));
+    m->dropNormals();           /* the chunks change and move */
     std::memset(stats, 0, sizeof(*stats));
     const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
     uint64_t maxV = 0, maxT = 0;
@@ -1277,6 +1285,43 @@ MLSGPU_API int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *m, const float origin[3
     return MLSGPU_OK;
 }
 
+/* The normals (normals.hip) of dense chunk c of a finalized sink, computed where the chunk lies at the first request.  Under
+ * the mutex. */
+int mlsgpu_mesher::chunkNormals(uint32_t c, const float **dNormals, mlsgpu_normals_stats *out)
+{
+    const size_t nc = chunkVStart.size() - 1;
+    const uint64_t total = chunkVStart[nc];
+    HIP_CHECK(hipSetDevice(ctx->device));
+    if (outNormals.get() == nullptr || outNormals.capacity() < 3 * total)
+    {
+        dropNormals();          /* growing discards what was computed */
+        PROPAGATE(outNormals.reserve(std::max<uint64_t>(3 * total, 1)));
+    }
+    if (normalsReady.size() != nc)
+    {
+        normalsReady.assign(nc, 0);
+        normalsOf.assign(nc, mlsgpu_normals_stats());
+    }
+    const uint64_t v0 = chunkVStart[c], t0 = chunkTStart[c];
+    if (!normalsReady[c])
+    {
+        PROPAGATE(mlsgpu_hip_mesh_normals(ctx, outVertices + 3 * v0, chunkVStart[c + 1] - v0, outTriangles + 3 * t0,
+                                          chunkTStart[c + 1] - t0, outNormals + 3 * v0, &normalsOf[c]));
+        normalsReady[c] = 1;
+    }
+    if (dNormals) *dNormals = outNormals + 3 * v0;
+    if (out) *out = normalsOf[c];
+    return MLSGPU_OK;
+}
+
+MLSGPU_API int mlsgpu_hip_mesher_chunk_normals(mlsgpu_mesher *m, uint32_t i, const float **dNormals, mlsgpu_normals_stats *stats)
+{
+    REQUIRE(m != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized && i < m->outChunks.size(), MLSGPU_ERR_INVALID);
+    return m->chunkNormals(m->outChunks[i], dNormals, stats);
+}
+
 MLSGPU_API int mlsgpu_hip_mesher_stats(mlsgpu_mesher *m, uint64_t out[8])
 {
     REQUIRE(m != nullptr && out != nullptr && m->finalized, MLSGPU_ERR_INVALID);
@@ -1321,12 +1366,15 @@ MLSGPU_API int mlsgpu_hip_mesher_finalize_with(mlsgpu_mesher *m, const uint8_t *
 
 namespace
 {
-std::string plyHeader(uint64_t numVertices, uint64_t numTriangles, const char *const *comments, uint32_t numComments)
+std::string plyHeader(uint64_t numVertices, uint64_t numTriangles, const char *const *comments, uint32_t numComments,
+                      bool normals = false)
 {
     std::string head = "ply\nformat binary_little_endian 1.0\n";
     for (uint32_t i = 0; i < numComments; i++)
         head += std::string("comment ") + comments[i] + "\n";
     head += "element vertex " + std::to_string(numVertices) + "\nproperty float32 x\nproperty float32 y\nproperty float32 z\n";
+    if (normals)
+        head += "property float32 nx\nproperty float32 ny\nproperty float32 nz\n";
     head += "element face " + std::to_string(numTriangles) + "\nproperty list uint8 uint32 vertex_indices\ncomment padding:";
     size_t size = head.size() + 12;
     while (size % 4 != 0)
@@ -1356,6 +1404,20 @@ __global__ __launch_bounds__(256) void packFacesKernel(const uint32_t *triangles
         o[4 + 4 * k] = (uint8_t) (v >> 24);
     }
 }
+
+/* a vertex of the file with normals: x y z nx ny nz, 24 bytes, interleaved on the device */
+__global__ __launch_bounds__(256) void packVerticesKernel(const float *vertices, const float *normals, uint64_t n, float *out)
+{
+    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+    {
+        out[6 * i + k] = vertices[3 * i + k];
+        out[6 * i + 3 + k] = normals[3 * i + k];
+    }
+}
 } // namespace
 
 /*
@@ -1363,9 +1425,13 @@ __global__ __launch_bounds__(256) void packFacesKernel(const uint32_t *triangles
  * bufferBytes / 2: while one piece is written, the next travels (the role of src/async_io.h:95-140 behind the reference's
  * writer: the host never holds more of the mesh than the buffer).  Faces are packed into the file's 13-byte records on the
  * device.  The file is byte for byte what mlsgpu_hip_write_ply makes of the downloaded arrays.
+ * withNormals: the chunk's normals (computed now if nobody asked for them yet) interleaved with its vertices into 24-byte
+ * rows on the device, as the faces are packed; the file is mlsgpu_hip_write_ply_normals'.
  */
-MLSGPU_API int mlsgpu_hip_mesher_write_ply(mlsgpu_mesher *m, uint32_t i, const char *path, const char *const *comments,
-                                           uint32_t numComments, uint64_t bufferBytes)
+namespace
+{
+int writeChunkPly(mlsgpu_mesher *m, uint32_t i, const char *path, const char *const *comments, uint32_t numComments,
+                  uint64_t bufferBytes, bool withNormals)
 {
     REQUIRE(m != nullptr && path != nullptr, MLSGPU_ERR_INVALID);
     std::lock_guard<std::mutex> lock(m->mutex);
@@ -1373,13 +1439,18 @@ MLSGPU_API int mlsgpu_hip_mesher_write_ply(mlsgpu_mesher *m, uint32_t i, const c
     mlsgpu_ctx *ctx = m->ctx;
     HIP_CHECK(hipSetDevice(ctx->device));
     const uint32_t c = m->outChunks[i];
+    const float *dN = nullptr;
+    if (withNormals)
+        PROPAGATE(m->chunkNormals(c, &dN, nullptr));
+    const uint64_t rowBytes = withNormals ? 24 : 12;
     const uint64_t nv = m->chunkVStart[c + 1] - m->chunkVStart[c], nt = m->chunkTStart[c + 1] - m->chunkTStart[c];
     const uint8_t *dV = reinterpret_cast<const uint8_t *>(m->outVertices + 3 * (uint64_t) m->chunkVStart[c]);
     const uint32_t *dT = m->outTriangles + 3 * (uint64_t) m->chunkTStart[c];
     if (bufferBytes == 0)
         bufferBytes = uint64_t(64) << 20;
-    /* a piece holds whole 12-byte vertices and whole 13-byte faces */
-    const uint64_t piece = std::max<uint64_t>(bufferBytes / 2 / 156, 1) * 156;
+    /* a piece holds whole 12-byte (with normals 24-byte) vertices and whole 13-byte faces */
+    const uint64_t unit = 13 * rowBytes;
+    const uint64_t piece = std::max<uint64_t>(bufferBytes / 2 / unit, 1) * unit;
     PinnedArray<uint8_t> pinned[2];
     DeviceArray<uint8_t> dPack;
     hipEvent_t done[2] = {nullptr, nullptr};
@@ -1404,10 +1475,10 @@ MLSGPU_API int mlsgpu_hip_mesher_write_ply(mlsgpu_mesher *m, uint32_t i, const c
         cleanup();
         return rc;
     }
-    const std::string head = plyHeader(nv, nt, comments, numComments);
+    const std::string head = plyHeader(nv, nt, comments, numComments, withNormals);
     bool ok = std::fwrite(head.data(), 1, head.size(), f) == head.size();
     /* the pieces of the file body in order: vertex bytes, then face records; piece k + 1 is on its way while k is written */
-    const uint64_t vBytes = 12 * nv, fBytes = 13 * nt, total = vBytes + fBytes;
+    const uint64_t vBytes = rowBytes * nv, fBytes = 13 * nt, total = vBytes + fBytes;
     const uint64_t vPieces = (vBytes + piece - 1) / piece, fPieces = (fBytes + piece - 1) / piece, pieces = vPieces + fPieces;
     auto issue = [&](uint64_t k) -> hipError_t
     {
@@ -1415,7 +1486,20 @@ MLSGPU_API int mlsgpu_hip_mesher_write_ply(mlsgpu_mesher *m, uint32_t i, const c
         if (k < vPieces)
         {
             const uint64_t off = k * piece, n = std::min(piece, vBytes - off);
-            hipError_t e = hipMemcpyAsync(pinned[slot], dV + off, n, hipMemcpyDeviceToHost, ctx->stream);
+            const uint8_t *from = dV + off;
+            hipError_t e = hipSuccess;
+            if (withNormals)
+            {
+                const uint64_t firstRow = off / 24, rows = n / 24;
+                uint8_t *pack = dPack + (uint64_t) slot * piece;
+                hipLaunchKernelGGL(packVerticesKernel, dim3(divUp(rows, 256)), dim3(256), 0, ctx->stream,
+                                   reinterpret_cast<const float *>(dV) + 3 * firstRow, dN + 3 * firstRow, rows,
+                                   reinterpret_cast<float *>(pack));
+                e = hipGetLastError();
+                from = pack;
+            }
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(pinned[slot], from, n, hipMemcpyDeviceToHost, ctx->stream);
             return e != hipSuccess ? e : hipEventRecord(done[slot], ctx->stream);
         }
         const uint64_t off = (k - vPieces) * piece, n = std::min(piece, fBytes - off);
@@ -1451,6 +1535,42 @@ MLSGPU_API int mlsgpu_hip_mesher_write_ply(mlsgpu_mesher *m, uint32_t i, const c
         return setError(MLSGPU_ERR_INVALID, "writing %s failed", path);
     return MLSGPU_OK;
 }
+} // namespace
+
+MLSGPU_API int mlsgpu_hip_mesher_write_ply(mlsgpu_mesher *m, uint32_t i, const char *path, const char *const *comments,
+                                           uint32_t numComments, uint64_t bufferBytes)
+{
+    return writeChunkPly(m, i, path, comments, numComments, bufferBytes, false);
+}
+
+MLSGPU_API int mlsgpu_hip_mesher_write_ply_normals(mlsgpu_mesher *m, uint32_t i, const char *path, const char *const *comments,
+                                                   uint32_t numComments, uint64_t bufferBytes)
+{
+    return writeChunkPly(m, i, path, comments, numComments, bufferBytes, true);
+}
+
+namespace
+{
+/* the faces of the file from host memory: uint8 3 + 3 x uint32 each */
+bool writeFaces(FILE *f, const uint32_t *triangles, uint64_t numTriangles)
+{
+    bool ok = true;
+    std::vector<unsigned char> faces;
+    const uint64_t batch = 1 << 20;
+    for (uint64_t first = 0; ok && first < numTriangles; first += batch)
+    {
+        const uint64_t n = std::min(batch, numTriangles - first);
+        faces.resize(13 * n);
+        for (uint64_t i = 0; i < n; i++)
+        {
+            faces[13 * i] = 3;
+            std::memcpy(&faces[13 * i + 1], triangles + 3 * (first + i), 12);
+        }
+        ok = std::fwrite(faces.data(), 13, n, f) == n;
+    }
+    return ok;
+}
+} // namespace
 
 /* FastPly::Writer's file (src/fast_ply.cpp:443-521): header padded to a multiple of 4, float32 x y z per vertex,
  * uint8 3 + 3 x uint32 per face; host memory in, one file out */
@@ -1465,19 +1585,39 @@ MLSGPU_API int mlsgpu_hip_write_ply(const char *path, const float *vertices, uin
         return setError(MLSGPU_ERR_INVALID, "cannot open %s for writing", path);
     bool ok = std::fwrite(head.data(), 1, head.size(), f) == head.size();
     ok = ok && std::fwrite(vertices, 12, numVertices, f) == numVertices;
-    std::vector<unsigned char> faces;
+    ok = ok && writeFaces(f, triangles, numTriangles);
+    ok = (std::fclose(f) == 0) && ok;
+    if (!ok)
+        return setError(MLSGPU_ERR_INVALID, "writing %s failed", path);
+    return MLSGPU_OK;
+}
+
+/* The same file with property float32 nx / ny / nz after z: 24-byte vertex rows */
+MLSGPU_API int mlsgpu_hip_write_ply_normals(const char *path, const float *vertices, const float *normals, uint64_t numVertices,
+                                            const uint32_t *triangles, uint64_t numTriangles, const char *const *comments,
+                                            uint32_t numComments)
+{
+    REQUIRE(path != nullptr && (numVertices == 0 || (vertices != nullptr && normals != nullptr))
+            && (numTriangles == 0 || triangles != nullptr), MLSGPU_ERR_INVALID);
+    const std::string head = plyHeader(numVertices, numTriangles, comments, numComments, true);
+    FILE *f = std::fopen(path, "wb");
+    if (f == nullptr)
+        return setError(MLSGPU_ERR_INVALID, "cannot open %s for writing", path);
+    bool ok = std::fwrite(head.data(), 1, head.size(), f) == head.size();
     const uint64_t batch = 1 << 20;
-    for (uint64_t first = 0; ok && first < numTriangles; first += batch)
+    std::vector<float> rows;
+    for (uint64_t first = 0; ok && first < numVertices; first += batch)
     {
-        const uint64_t n = std::min(batch, numTriangles - first);
-        faces.resize(13 * n);
+        const uint64_t n = std::min(batch, numVertices - first);
+        rows.resize(6 * n);
         for (uint64_t i = 0; i < n; i++)
         {
-            faces[13 * i] = 3;
-            std::memcpy(&faces[13 * i + 1], triangles + 3 * (first + i), 12);
+            std::memcpy(&rows[6 * i], vertices + 3 * (first + i), 12);
+            std::memcpy(&rows[6 * i + 3], normals + 3 * (first + i), 12);
         }
-        ok = std::fwrite(faces.data(), 13, n, f) == n;
+        ok = std::fwrite(rows.data(), 24, n, f) == n;
     }
+    ok = ok && writeFaces(f, triangles, numTriangles);
     ok = (std::fclose(f) == 0) && ok;
     if (!ok)
         return setError(MLSGPU_ERR_INVALID, "writing %s failed", path);

@@ -145,6 +145,16 @@ inline mlsgpu_simplify_stats simplify(const Context &ctx, const Buffer<float> &v
     return st;
 }
 
+/// Area-weighted vertex normals of a mesh in device memory (mlsgpu_hip_mesh_normals): outNormals has room for 3 floats per
+/// vertex and does not overlap the inputs.
+inline mlsgpu_normals_stats normals(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
+                                    const Buffer<std::uint32_t> &triangles, std::uint64_t numTriangles, Buffer<float> &outNormals)
+{
+    mlsgpu_normals_stats st;
+    check(mlsgpu_hip_mesh_normals(ctx.get(), vertices.get(), numVertices, triangles.get(), numTriangles, outNormals.get(), &st));
+    return st;
+}
+
 typedef mlsgpu_splat Splat;                 // src/splat.h:40-46
 enum MlsShape { MLS_SHAPE_SPHERE = MLSGPU_SHAPE_SPHERE, MLS_SHAPE_PLANE = MLSGPU_SHAPE_PLANE };  // src/mls.h:47-51
 
@@ -635,8 +645,10 @@ public:
         check(mlsgpu_hip_mesher_simplify(h, origin, cellSize, &st));
         return st;
     }
-    /// The second half of write(): one file per chunk of the `chunks` that finalize() reported.
-    std::size_t writeChunks(std::size_t chunks, const Namer &namer, const std::vector<std::string> &comments = std::vector<std::string>())
+    /// The second half of write(): one file per chunk of the `chunks` that finalize() reported; withNormals: the files of
+    /// writePlyNormals().
+    std::size_t writeChunks(std::size_t chunks, const Namer &namer, const std::vector<std::string> &comments = std::vector<std::string>(),
+                            bool withNormals = false)
     {
         std::vector<const char *> cstr;
         for (const std::string &c : comments)
@@ -648,10 +660,15 @@ public:
             const std::uint32_t *dT;
             check(mlsgpu_hip_mesher_chunk(h, i, &id, &nv, &nt, &dV, &dT));
             // straight from HBM through a bounded pinned buffer (the reference's asynchronous writer, src/async_io.h)
-            check(mlsgpu_hip_mesher_write_ply(h, i, namer(id).c_str(), cstr.empty() ? NULL : cstr.data(),
-                                              (std::uint32_t) cstr.size(), writeBufferBytes));
+            check((withNormals ? mlsgpu_hip_mesher_write_ply_normals : mlsgpu_hip_mesher_write_ply)(
+                h, i, namer(id).c_str(), cstr.empty() ? NULL : cstr.data(), (std::uint32_t) cstr.size(), writeBufferBytes));
         }
         return chunks;
+    }
+    /// writeChunks() with every chunk's area-weighted vertex normals (normals(i)) as nx ny nz after z.
+    std::size_t writePlyNormals(std::size_t chunks, const Namer &namer, const std::vector<std::string> &comments = std::vector<std::string>())
+    {
+        return writeChunks(chunks, namer, comments, true);
     }
     /// MesherBase::write: returns the number of files written.
     std::size_t write(const Namer &namer, const std::vector<std::string> &comments = std::vector<std::string>())
@@ -665,6 +682,14 @@ public:
         mlsgpu_topology t;
         check(mlsgpu_hip_mesher_chunk_topology(h, i, &t));
         return t;
+    }
+    /// The area-weighted vertex normals of output chunk i (mlsgpu_hip_mesher_chunk_normals): computed on the device at the
+    /// first request, kept beside the vertices until the next finalize() or simplify(); *dNormals is 3 floats per vertex.
+    mlsgpu_normals_stats normals(std::uint32_t i, const float **dNormals = NULL) const
+    {
+        mlsgpu_normals_stats st;
+        check(mlsgpu_hip_mesher_chunk_normals(h, i, dNormals, &st));
+        return st;
     }
 };
 
