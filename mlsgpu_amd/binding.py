@@ -556,6 +556,19 @@ class SplatTree:
         check(lib().mlsgpu_hip_tree_build(self.h, splats.ptr, first_splat, num_splats, _p(_u3(size)),
                                           _p(_i3(offset)), subsampling_shift))
 
+    @staticmethod
+    def build_batch(trees, builds, subsampling_shift):
+        """mlsgpu_hip_tree_build_batch: trees[k] is built on builds[k] = (splats, first_splat, num_splats, size, offset) --
+        the arguments of enqueue_build -- by one set of launches; the trees share their levels and their context."""
+        assert len(trees) == len(builds)
+        reqs = (TreeBuild * len(builds))()
+        for r, (splats, first_splat, num_splats, size, offset) in zip(reqs, builds):
+            r.dSplats, r.firstSplat, r.numSplats = splats.ptr, first_splat, num_splats
+            r.size[:] = [int(v) for v in size]
+            r.offset[:] = [int(v) for v in offset]
+        handles = (C.c_void_p * len(trees))(*[t.h.value for t in trees])
+        check(lib().mlsgpu_hip_tree_build_batch(handles, reqs, len(trees), subsampling_shift))
+
     def set_mutate(self, mutate):
         """False: builds leave the splats untouched (the radius stays the radius); MlsFunctor.set() follows."""
         check(lib().mlsgpu_hip_tree_set_mutate(self.h, 1 if mutate else 0))

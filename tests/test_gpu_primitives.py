@@ -494,14 +494,15 @@ def run_route(variable, selection):
 
 def test_route_without_one_launch_scan():
     """MLSGPU_HIP_SCAN_ONEPASS=0: every scan in its two- or three-launch form -- the scan tests of this file, the octree at
-    every depth, and one Marching volume."""
+    every depth, on saturated tiles and on a batch of mixed lanes, and one Marching volume."""
     import test_gpu_marching
     import test_gpu_tree
     me = sys.modules[__name__]
     selection = [_cases(me, name) for name in ("test_scan_u32", "test_scan_launches_back_to_back", "test_scan_batch_lanes",
                                                "test_scan_one_launch_under_contention", "test_scan_forms",
                                                "test_scan_device_count")]
-    selection.append(_cases(test_gpu_tree, "test_every_tree_depth"))
+    selection += [_cases(test_gpu_tree, name) for name in ("test_every_tree_depth", "test_saturated_tiles",
+                                                           "test_build_batch_mixed_lanes")]
     assert "tsphere" in test_gpu_marching.GENERATE_CASES
     selection.append((_cases(test_gpu_marching, "test_generate_manifold_and_parity")[0] + "[tsphere]", 1))
     run_route("MLSGPU_HIP_SCAN_ONEPASS", selection)
@@ -509,9 +510,10 @@ def test_route_without_one_launch_scan():
 
 def test_route_without_fused_octree_pass():
     """MLSGPU_HIP_OCTREE_FUSED=0: the octree's entries sorted by the generic radix sort -- every depth, the default geometry,
-    and the worker on trees that are not the default."""
+    saturated tiles, skewed keys, the grid's faces, and the worker on trees that are not the default."""
     import test_gpu_fp64
     import test_gpu_tree
     selection = [_cases(test_gpu_tree, "test_every_tree_depth"), _cases(test_gpu_tree, "test_parity_default_geometry"),
                  _cases(test_gpu_fp64, "test_worker_non_default_tree")]
+    selection += [_cases(test_gpu_tree, name) for name in ("test_saturated_tiles", "test_skewed_keys", "test_grid_faces")]
     run_route("MLSGPU_HIP_OCTREE_FUSED", selection)
