@@ -12,14 +12,17 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--simplify N] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--simplify N] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
  * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
  * --simplify N (device weld only, N > 0): before the write, every output chunk is vertex-clustered where it lies, in cells of
  *   N grid spacings counted from one cell below the bounding grid's low corner; one line with the statistics.
+ * --smooth N (device weld only, N > 0): before the write, every output chunk gets N Taubin iterations (lambda 0.5, mu -0.53)
+ *   where it lies, the vertices on a chunk's boundary held fixed -- after --simplify when both are given; one line with the
+ *   statistics.
  * --normals (device weld only): every output chunk is written with its area-weighted vertex normals (nx ny nz after z),
- *   computed where the chunk lies -- after --simplify when both are given; one line per chunk.
+ *   computed where the chunk lies -- after --simplify and --smooth when they are given; one line per chunk.
  */
 #include <cstdio>
 #include <cstdlib>
@@ -40,7 +43,8 @@ int main(int argc, char **argv)
     bool hostWeld = false, checkTopology = false, writeNormals = false;
     std::uint64_t bufferBytes = 0, hbmSplats = 0;
     float simplifyCells = 0.0f;
-    bool simplifyGiven = false;
+    bool simplifyGiven = false, smoothGiven = false;
+    long smoothIterations = 0;
     std::string tmpDir;
     std::vector<std::string> plys, rest;
     for (int i = 1; i < argc; i++)
@@ -65,6 +69,11 @@ int main(int argc, char **argv)
             simplifyCells = (float) atof(argv[++i]);
             simplifyGiven = true;
         }
+        else if (a == "--smooth" && i + 1 < argc)
+        {
+            smoothIterations = atol(argv[++i]);
+            smoothGiven = true;
+        }
         else if (a == "--buffer" && i + 1 < argc)
             bufferBytes = strtoull(argv[++i], NULL, 10);
         else if (a == "--tmp-dir" && i + 1 < argc)             // --weld host: the welder's blocks in temporary files there (src/mlsgpu_core.cpp --tmp-dir)
@@ -78,7 +87,7 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--simplify N] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--simplify N] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
         return 2;
     }
@@ -90,6 +99,16 @@ int main(int argc, char **argv)
     if (simplifyGiven && hostWeld)
     {
         std::cerr << "--simplify needs --weld device: the host welder's output is not on the device\n";
+        return 2;
+    }
+    if (smoothGiven && !(smoothIterations > 0 && smoothIterations <= 1000000))
+    {
+        std::cerr << "--smooth takes a number of iterations > 0\n";
+        return 2;
+    }
+    if (smoothGiven && hostWeld)
+    {
+        std::cerr << "--smooth needs --weld device: the host welder's output is not on the device\n";
         return 2;
     }
     if (writeNormals && hostWeld)
@@ -157,6 +176,8 @@ int main(int argc, char **argv)
         std::uint64_t st[8];
         mlsgpu_simplify_stats simplified = mlsgpu_simplify_stats();
         float simplifyCell = 0.0f, simplifyOrigin[3] = {0.0f, 0.0f, 0.0f};
+        mlsgpu_smooth_stats smoothed = mlsgpu_smooth_stats();
+        std::size_t smoothedChunks = 0;
         {
             BucketFarm farm(devices, cfg, 4 /* --device-threads */, 1, hostWeld ? NULL : &deviceMesher);
             if (hostWeld)
@@ -194,6 +215,11 @@ int main(int argc, char **argv)
                     simplifyOrigin[i] = cfg.gridOrigin[i] - simplifyCell;
                 simplified = deviceMesher.simplify(simplifyOrigin, simplifyCell);
             }
+            if (smoothGiven)
+            {
+                smoothed = deviceMesher.smooth((std::uint32_t) smoothIterations, 0.5f, -0.53f, MLSGPU_SMOOTH_BOUNDARY_FIXED);
+                smoothedChunks = chunks;
+            }
             written = deviceMesher.writeChunks(chunks, [&](std::uint64_t) { return outName; }, comments, writeNormals);
             deviceMesher.getStatistics(st);
         }
@@ -210,6 +236,11 @@ int main(int argc, char **argv)
                         (unsigned long long) simplified.inVertices, (unsigned long long) simplified.outVertices,
                         (unsigned long long) simplified.inTriangles, (unsigned long long) simplified.outTriangles,
                         (unsigned long long) simplified.collapsedTriangles, (unsigned long long) simplified.duplicateTriangles);
+        if (smoothGiven)
+            std::printf("smooth chunks %zu vertices %llu edges %llu boundary-vertices %llu isolated %llu passes %llu max-move %.9g\n",
+                        smoothedChunks, (unsigned long long) smoothed.numVertices, (unsigned long long) smoothed.numEdges,
+                        (unsigned long long) smoothed.boundaryVertices, (unsigned long long) smoothed.isolatedVertices,
+                        (unsigned long long) smoothed.passes, smoothed.maxMove);
         if (writeNormals)
             for (std::uint32_t i = 0; i < written; i++)
             {

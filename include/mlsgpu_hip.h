@@ -753,6 +753,84 @@ int mlsgpu_hip_mesh_normals(mlsgpu_ctx *ctx, const float *dVertices, uint64_t nu
  * chunk, the sum over that chunk's triangles only -- the seams between split output files are not matched.  dNormals and
  * stats may each be NULL. */
 int mlsgpu_hip_mesher_chunk_normals(mlsgpu_mesher *mesher, uint32_t i, const float **dNormals, mlsgpu_normals_stats *stats);
+
+/* ---- Taubin lambda|mu smoothing of a device-resident mesh: the low-pass that takes out the terraces a simplify leaves and
+ *      the facet noise of marching tetrahedra without shrinking the surface, before the mesh crosses the link.  The reference
+ *      has no counterpart.  The triangles are left alone, so the topology report does not change.  Deterministic: every
+ *      float and double operation below is ONE correctly rounded IEEE operation (no contraction), and every sum is an integer
+ *      sum -- the output depends neither on the schedule nor on the order of the triangles, and renumbering the vertices
+ *      permutes it bit for bit.
+ *      1. A triangle with an index >= V is counted in outOfRangeTriangles (the index is compared, never used as an address);
+ *         otherwise a triangle with two equal indices is counted in degenerateTriangles.  Neither takes part.
+ *      2. The undirected edges {a, b} of the participating triangles are counted once each in numEdges.  An edge is a
+ *         BOUNDARY edge (boundaryEdges) if exactly one triangle side uses it, a -> b and b -> a counted together (a side used
+ *         twice in the same direction is no boundary).  A vertex on a boundary edge is a boundary vertex (boundaryVertices),
+ *         a vertex on no edge is isolated (isolatedVertices).
+ *      3. The neighbour set N(v): for an interior vertex every vertex it shares an edge with; for a boundary vertex the
+ *         empty set under MLSGPU_SMOOTH_BOUNDARY_FIXED (it keeps its position bit for bit through every pass) and the
+ *         vertices it shares a BOUNDARY edge with under MLSGPU_SMOOTH_BOUNDARY_CURVE.  k = |N(v)|; a vertex with k = 0
+ *         never moves.
+ *      4. M = the largest |coordinate| over all V input vertices.  M == 0 or V == 0: the output is the input and
+ *         scaleExponent = 0.  Otherwise e is the integer with 2^e <= M < 2^(e + 1) (as for the normals), fixed for the whole
+ *         call, and scaleExponent = e.
+ *      5. One pass with factor f, F = (double) f: for every vertex with k > 0, per axis, on the positions p as the previous
+ *         pass left them (Jacobi: all reads come before all writes):
+ *           Q(x) = llrint(ldexp((double) x, 30 - e)), ties to even;  S = the int64 sum of Q(p_n) over n in N(v), modulo 2^64;
+ *           D = S - k * Q(p_v), modulo 2^64;  d = ldexp((double) D / (double) k, e - 30);  out = (float) ((double) p_v + F * d).
+ *         The vertex's own position is never quantised: a vertex whose neighbours balance keeps its bits.
+ *      6. An iteration is a lambda pass followed, if mu != 0, by a mu pass.  passes = iterations * (mu != 0 ? 2 : 1), also
+ *         where step 4 makes them the identity.  iterations = 0 copies the input; the counts of steps 1-2 are still filled.
+ *      7. maxMove = the largest |(double) out - (double) in| over vertices and axes; maxCoordinate = the largest |coordinate|
+ *         of the input and of every pass's output.  If maxCoordinate is not finite or exceeds 2^(e + 21) the call has
+ *         DIVERGED: MLSGPU_ERR_INVALID, and nothing is promised about the outputs.  (Values are clamped before they become
+ *         integers, so every conversion is defined, and no address ever depends on a coordinate.)
+ *      Scaling every coordinate by 2^s scales the output exactly and moves scaleExponent by s (away from the subnormals). ---- */
+#define MLSGPU_SMOOTH_BOUNDARY_FIXED 0
+#define MLSGPU_SMOOTH_BOUNDARY_CURVE 1
+typedef struct mlsgpu_smooth_stats
+{
+    uint64_t numVertices, numTriangles;
+    uint64_t outOfRangeTriangles;   /* an index >= numVertices */
+    uint64_t degenerateTriangles;   /* in range, two indices equal */
+    uint64_t numEdges;              /* undirected, of the participating triangles */
+    uint64_t boundaryEdges;         /* used by exactly one triangle side */
+    uint64_t boundaryVertices;      /* on a boundary edge */
+    uint64_t isolatedVertices;      /* on no edge */
+    uint64_t passes;                /* step 6 */
+    int64_t scaleExponent;          /* e of step 4 */
+    double maxMove, maxCoordinate;  /* step 7 */
+} mlsgpu_smooth_stats;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_smooth_stats) == 96, "mlsgpu_smooth_stats is part of the ABI");
+#else
+typedef char mlsgpu_smooth_stats_size_is_96[sizeof(mlsgpu_smooth_stats) == 96 ? 1 : -1];
+#endif
+/* numVertices packed float xyz and numTriangles uint32 index triples on ctx's device -> dOutVertices, packed float xyz with
+ * room for 3 * numVertices floats, which may be exactly dVertices (in place); any other overlap is not allowed.
+ * MLSGPU_ERR_INVALID, before anything touches the device, unless lambda and mu are finite, 0 < lambda <= 1, -1 <= mu <= 0,
+ * boundary is one of the two values above and stats is not NULL; MLSGPU_ERR_INVALID for a coordinate that is not finite
+ * (counted on the device) and for a call that diverged (step 7).  MLSGPU_ERR_LENGTH, before anything is allocated, unless
+ * numVertices < 2^32 and 6 * numTriangles < 2^32: both directions of every triangle side are sorted, and the sort's values
+ * are 32-bit.  No vertices or no triangles is not an error.  Scratch is allocated for the call and freed on return: 144 bytes
+ * per triangle (six directed edge records: the two sides of the sort's 64-bit keys and 32-bit values; the neighbour lists
+ * reuse the side the sort leaves free), 41 bytes per vertex (two working position arrays of 16-byte rows, the neighbour
+ * run 8, a boundary flag 1), the sort's histogram and the scan's tile sums; MLSGPU_ERR_NOMEM if the device does not have it.
+ * Blocks until the statistics are there: one stream synchronisation behind the adjacency build (the input's extent sizes the
+ * fixed point), one at the end.  MLSGPU_HIP_SMOOTH_PASS=serial walks a neighbour list one entry after the other instead of
+ * four entries a round with their loads issued together; the result is the same bit for bit. */
+int mlsgpu_hip_mesh_smooth(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices, const uint32_t *dTriangles,
+                           uint64_t numTriangles, uint32_t iterations, float lambda, float mu, uint32_t boundary,
+                           float *dOutVertices, mlsgpu_smooth_stats *stats);
+/* The same for every output chunk of a finalized device sink, on the mesher's context: each chunk's vertices are smoothed
+ * where they lie, in place; triangles and chunk layout are untouched, and the chunks' normals are dropped, so normals
+ * requested afterwards are those of the smoothed chunk.  *stats: the counts summed over the chunks, passes as for one chunk,
+ * scaleExponent, maxMove and maxCoordinate the maxima over the chunks.  Chunks are smoothed INDEPENDENTLY, as for simplify
+ * and normals.  Under MLSGPU_SMOOTH_BOUNDARY_FIXED a vertex two chunks share lies on the boundary of each and so keeps its
+ * bits in both: the seams between split output files stay closed.  (Under _CURVE it moves with each chunk's own boundary
+ * neighbours, and the seams may open.)  MLSGPU_ERR_INVALID before finalize; may be called again, and after a simplify.  After
+ * an error the sink's results are dropped: finalize again. */
+int mlsgpu_hip_mesher_smooth(mlsgpu_mesher *mesher, uint32_t iterations, float lambda, float mu, uint32_t boundary,
+                             mlsgpu_smooth_stats *stats);
 /* ---- host mesh sink: OOCMesher's weld as the reference runs it, on the host (src/mesher.cpp:220-469, north_star:
  *      "welding stays on host").  add() is MesherBase::InputFunctor: local components of the block by union-find over
  *      two edges per triangle (computeLocalComponents, :220-236), clumps merged across blocks through the external

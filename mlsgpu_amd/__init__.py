@@ -6,9 +6,11 @@ a thin ctypes binding of the same C-ABI, used by the tests and by bench.py.  The
 fallback: importing :mod:`mlsgpu_amd.binding` without the built library raises.
 """
 from .binding import (BucketFarm, Context, DensityError, DeviceBuffer, FormatError, HipError, HostMesher, InvalidArgument, LengthError, Marching, Mesher, MlsError,
-                      MlsFunctor, NormalsStats, SPLAT_DTYPE, SimplifyStats, SplatTree, Swathe, Topology, Worker, WorkerConfig, lib, library_path, mesh_normals, mesh_simplify,
+                      MlsFunctor, NormalsStats, SPLAT_DTYPE, SimplifyStats, SmoothStats, SplatTree, Swathe, Topology, Worker, WorkerConfig, lib, library_path, mesh_normals, mesh_simplify,
+                      mesh_smooth,
                       mesh_topology)
 
 __all__ = ["BucketFarm", "Context", "DensityError", "DeviceBuffer", "FormatError", "HipError", "HostMesher", "InvalidArgument", "LengthError", "Marching", "Mesher", "MlsError",
-           "MlsFunctor", "NormalsStats", "SPLAT_DTYPE", "SimplifyStats", "SplatTree", "Swathe", "Topology", "Worker", "WorkerConfig", "lib", "library_path", "mesh_normals", "mesh_simplify",
+           "MlsFunctor", "NormalsStats", "SPLAT_DTYPE", "SimplifyStats", "SmoothStats", "SplatTree", "Swathe", "Topology", "Worker", "WorkerConfig", "lib", "library_path", "mesh_normals", "mesh_simplify",
+           "mesh_smooth",
            "mesh_topology"]

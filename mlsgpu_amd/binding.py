@@ -143,6 +143,21 @@ class NormalsStats(C.Structure):
         return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
 
 
+class SmoothStats(C.Structure):
+    """mlsgpu_smooth_stats: what took no part, edges and boundary, the passes run, the scale's exponent, how far it moved."""
+    _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
+                ("degenerateTriangles", C.c_uint64), ("numEdges", C.c_uint64), ("boundaryEdges", C.c_uint64),
+                ("boundaryVertices", C.c_uint64), ("isolatedVertices", C.c_uint64), ("passes", C.c_uint64),
+                ("scaleExponent", C.c_int64), ("maxMove", C.c_double), ("maxCoordinate", C.c_double)]
+
+    def as_dict(self):
+        return dict((name, (float if kind is C.c_double else int)(getattr(self, name))) for name, kind in self._fields_)
+
+
+# MLSGPU_SMOOTH_BOUNDARY_*: what the vertices on a boundary edge do
+SMOOTH_BOUNDARY_FIXED, SMOOTH_BOUNDARY_CURVE = 0, 1
+
+
 # MLSGPU_TOPO_*: the index into Topology.count / firstOf, and firstKind
 TOPO_OUT_OF_RANGE, TOPO_DEGENERATE, TOPO_ISOLATED, TOPO_DUPLICATED, TOPO_MIXED, TOPO_TUNNEL, TOPO_NONE = range(7)
 TOPO_NAMES = ("out_of_range", "degenerate", "isolated", "duplicated", "mixed", "tunnel", "none")
@@ -340,6 +355,8 @@ def lib():
     sig("mlsgpu_hip_write_ply", C.c_int, C.c_char_p, vp, u64, vp, u64, vp, u32)
     sig("mlsgpu_hip_mesh_normals", C.c_int, vp, vp, u64, vp, u64, vp, P(NormalsStats))
     sig("mlsgpu_hip_mesher_chunk_normals", C.c_int, vp, u32, P(vp), P(NormalsStats))
+    sig("mlsgpu_hip_mesh_smooth", C.c_int, vp, vp, u64, vp, u64, u32, C.c_float, C.c_float, u32, vp, P(SmoothStats))
+    sig("mlsgpu_hip_mesher_smooth", C.c_int, vp, u32, C.c_float, C.c_float, u32, P(SmoothStats))
     sig("mlsgpu_hip_write_ply_normals", C.c_int, C.c_char_p, vp, vp, u64, vp, u64, vp, u32)
     sig("mlsgpu_hip_mesher_write_ply_normals", C.c_int, vp, C.c_uint32, C.c_char_p, vp, C.c_uint32, u64)
     sig("mlsgpu_hip_bucket", C.c_int, vp, vp, u64, P(GridStruct), P(BucketParams), BUCKET_FN, vp, P(u64))
@@ -872,6 +889,13 @@ class Mesher:
         check(lib().mlsgpu_hip_mesher_simplify(self.h, (C.c_float * 3)(*[float(x) for x in origin]), float(cell_size), C.byref(st)))
         return st.as_dict()
 
+    def smooth(self, iterations, lam=0.5, mu=-0.53, boundary=SMOOTH_BOUNDARY_FIXED):
+        """Every output chunk of the finalized sink smoothed in place (mesh_smooth): positions only, the triangles and the
+        chunk layout stay.  Returns the statistics: counts summed over the chunks, exponent and maxima the largest."""
+        st = SmoothStats()
+        check(lib().mlsgpu_hip_mesher_smooth(self.h, int(iterations), float(lam), float(mu), int(boundary), C.byref(st)))
+        return st.as_dict()
+
     def write_ply(self, i, path, comments=(), buffer_bytes=0):
         """Output chunk i straight from HBM into FastPly::Writer's file through a bounded pinned buffer."""
         arr = (C.c_char_p * max(len(comments), 1))(*[c.encode("ascii") for c in comments])
@@ -1000,6 +1024,44 @@ def mesh_normals(ctx, vertices, triangles, num_vertices=None, num_triangles=None
         for buf in own:
             buf.free()
     return out, st.as_dict()
+
+
+def mesh_smooth(ctx, vertices, triangles, iterations, lam, mu, boundary=SMOOTH_BOUNDARY_FIXED, num_vertices=None, num_triangles=None,
+                in_place=False):
+    """Taubin lambda|mu smoothing on the device (mlsgpu_hip_mesh_smooth), bit-reproducible whatever the schedule, the order
+    of the triangles or the numbering of the vertices.  `vertices` / `triangles` are numpy arrays (uploaded for the call) or
+    DeviceBuffers of packed float32 xyz / uint32 triples; in_place writes the result over the vertices on the device.
+    Returns (vertices float32 [V, 3] downloaded, statistics as a dict)."""
+    own = []
+
+    def on_device(a, dtype, count):
+        if isinstance(a, DeviceBuffer):
+            return a, (a.nbytes // 12 if count is None else count)
+        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
+        buf = DeviceBuffer(ctx, array=a) if a.size else None
+        if buf is not None:
+            own.append(buf)
+        return buf, (len(a) if count is None else count)
+
+    st = SmoothStats()
+    try:
+        dv, nv = on_device(vertices, np.float32, num_vertices)
+        dt, nt = on_device(triangles, np.uint32, num_triangles)
+        ov = dv if in_place else DeviceBuffer(ctx, nbytes=12 * nv) if nv and dv is not None else None
+        if ov is not None and not in_place:
+            own.append(ov)
+        check(lib().mlsgpu_hip_mesh_smooth(ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, int(iterations), float(lam),
+                                           float(mu), int(boundary), ov.ptr if ov else None, C.byref(st)))
+        out = ov.download(np.float32, 3 * nv).reshape(-1, 3) if ov is not None else np.zeros((0, 3), np.float32)
+    finally:
+        for buf in own:
+            buf.free()
+    return out, st.as_dict()
+
+
+def mesher_smooth(mesher, iterations, lam=0.5, mu=-0.53, boundary=SMOOTH_BOUNDARY_FIXED):
+    """Mesher.smooth as a function, beside mesh_smooth."""
+    return mesher.smooth(iterations, lam, mu, boundary)
 
 
 def mesher_chunk_normals(mesher, i, download=True):

@@ -1285,6 +1285,53 @@ MLSGPU_API int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *m, const float origin[3
     return MLSGPU_OK;
 }
 
+/* Every output chunk through mlsgpu_hip_mesh_smooth (smooth.hip), in place: only the positions change. */
+MLSGPU_API int mlsgpu_hip_mesher_smooth(mlsgpu_mesher *m, uint32_t iterations, float lambda, float mu, uint32_t boundary,
+                                        mlsgpu_smooth_stats *stats)
+{
+    REQUIRE(m != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
+    /* mlsgpu_hip_mesh_smooth's own checks, here so that a refused parameter costs no results */
+    REQUIRE(std::isfinite(lambda) && lambda > 0.0f && lambda <= 1.0f && std::isfinite(mu) && mu >= -1.0f && mu <= 0.0f, MLSGPU_ERR_INVALID);
+    REQUIRE(boundary == MLSGPU_SMOOTH_BOUNDARY_FIXED || boundary == MLSGPU_SMOOTH_BOUNDARY_CURVE, MLSGPU_ERR_INVALID);
+    mlsgpu_ctx *const ctx = m->ctx;
+    m->dropNormals();           /* the positions change */
+    std::memset(stats, 0, sizeof(*stats));
+    stats->passes = (uint64_t) iterations * (mu != 0.0f ? 2 : 1);
+    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
+    bool first = true;
+    for (size_t c = 0; c < nc; c++)
+    {
+        const uint64_t v0 = m->chunkVStart[c], t0 = m->chunkTStart[c];
+        const uint64_t nv = m->chunkVStart[c + 1] - v0, nt = m->chunkTStart[c + 1] - t0;
+        if (nt == 0)
+            continue;           /* a chunk without triangles has no output (finalize) */
+        mlsgpu_smooth_stats one;
+        const int rc = mlsgpu_hip_mesh_smooth(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, iterations, lambda, mu,
+                                              boundary, m->outVertices + 3 * v0, &one);
+        if (rc != MLSGPU_OK)
+        {
+            m->dropResults();   /* earlier chunks are smoothed already, and a chunk that diverged holds what it reached */
+            return rc;
+        }
+        stats->numVertices += one.numVertices;
+        stats->numTriangles += one.numTriangles;
+        stats->outOfRangeTriangles += one.outOfRangeTriangles;
+        stats->degenerateTriangles += one.degenerateTriangles;
+        stats->numEdges += one.numEdges;
+        stats->boundaryEdges += one.boundaryEdges;
+        stats->boundaryVertices += one.boundaryVertices;
+        stats->isolatedVertices += one.isolatedVertices;
+        stats->passes = one.passes;
+        stats->scaleExponent = first ? one.scaleExponent : std::max(stats->scaleExponent, one.scaleExponent);
+        stats->maxMove = std::max(stats->maxMove, one.maxMove);
+        stats->maxCoordinate = std::max(stats->maxCoordinate, one.maxCoordinate);
+        first = false;
+    }
+    return MLSGPU_OK;
+}
+
 /* The normals (normals.hip) of dense chunk c of a finalized sink, computed where the chunk lies at the first request.  Under
  * the mutex. */
 int mlsgpu_mesher::chunkNormals(uint32_t c, const float **dNormals, mlsgpu_normals_stats *out)

@@ -145,6 +145,18 @@ inline mlsgpu_simplify_stats simplify(const Context &ctx, const Buffer<float> &v
     return st;
 }
 
+/// Taubin lambda|mu smoothing of a mesh in device memory (mlsgpu_hip_mesh_smooth): outVertices has room for 3 floats per
+/// vertex and is either `vertices` itself (in place) or does not overlap the inputs.
+inline mlsgpu_smooth_stats smooth(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
+                                  const Buffer<std::uint32_t> &triangles, std::uint64_t numTriangles, std::uint32_t iterations,
+                                  float lambda, float mu, std::uint32_t boundary, Buffer<float> &outVertices)
+{
+    mlsgpu_smooth_stats st;
+    check(mlsgpu_hip_mesh_smooth(ctx.get(), vertices.get(), numVertices, triangles.get(), numTriangles, iterations, lambda, mu,
+                                 boundary, outVertices.get(), &st));
+    return st;
+}
+
 /// Area-weighted vertex normals of a mesh in device memory (mlsgpu_hip_mesh_normals): outNormals has room for 3 floats per
 /// vertex and does not overlap the inputs.
 inline mlsgpu_normals_stats normals(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
@@ -643,6 +655,15 @@ public:
     {
         mlsgpu_simplify_stats st;
         check(mlsgpu_hip_mesher_simplify(h, origin, cellSize, &st));
+        return st;
+    }
+    /// Every output chunk of the finalized mesher smoothed in place (mlsgpu_hip_mesher_smooth); between finalize() -- or
+    /// simplify() -- and writeChunks().  Counts summed over the chunks, exponent and maxima the largest.
+    mlsgpu_smooth_stats smooth(std::uint32_t iterations, float lambda = 0.5f, float mu = -0.53f,
+                               std::uint32_t boundary = MLSGPU_SMOOTH_BOUNDARY_FIXED)
+    {
+        mlsgpu_smooth_stats st;
+        check(mlsgpu_hip_mesher_smooth(h, iterations, lambda, mu, boundary, &st));
         return st;
     }
     /// The second half of write(): one file per chunk of the `chunks` that finalize() reported; withNormals: the files of
