@@ -583,7 +583,12 @@ int mlsgpu_hip_mesher_reset(mlsgpu_mesher *mesher);
  * added and exports every distinct external key with the (densely numbered) component that holds its vertex, and the
  * vertex / triangle count of every component; finalize_with() produces the output with the caller's verdict per component
  * in place of the prune rule.  No add between the two calls.  mlsgpu_amd/dist_sink.py merges the exports of all ranks in
- * one all-gather. */
+ * one all-gather.
+ * The export is reproducible and its numbering is part of the contract: the keys ascend; with the blocks taken in the
+ * order (chunk by first arrival, arrival within the chunk) and their vertices numbered through, a component's root is the
+ * smallest of its welded vertices (an external vertex is welded to the first vertex with its key in that order), and the
+ * roots are numbered densely in ascending order of that vertex.  rootTriangles counts the triangles whose first index
+ * lies in the component. */
 int mlsgpu_hip_mesher_boundary(mlsgpu_mesher *mesher, uint64_t *numKeys, uint64_t *numRoots);
 int mlsgpu_hip_mesher_boundary_read(mlsgpu_mesher *mesher, uint64_t *keys, uint32_t *keyRoot, uint64_t *rootVertices,
                                     uint64_t *rootTriangles);

@@ -16,6 +16,80 @@ from scipy.sparse import coo_matrix
 from scipy.sparse.csgraph import connected_components
 
 
+def mesh_sink_labels(meshes):
+    """What the sink knows before it numbers any output, for the concatenation of the blocks in the order
+    (chunk by first arrival, arrival within the chunk) -- the order in which a sink that groups its blocks by chunk
+    holds them, and in which equal keys therefore sort.  Returns a dict:
+      order      the block permutation: position p of the concatenation holds meshes[order[p]];
+      chunk_of   per position, the dense chunk index (first arrival);   chunks: dense index -> the caller's chunk;
+      bases      [blocks + 1] first vertex of every position;   tri_bases: the same for triangles;
+      comp_rep   per vertex, the welded identity for components: the first vertex with its key (itself if internal);
+      out_rep    per vertex, the identity inside its chunk's file: the first vertex with its key in the same chunk;
+      label      per vertex, its connected component (arbitrary numbers);
+      triangles  (t, 3) int64, vertex ids of the concatenation;
+      ext_gid, ext_key   every external vertex with its key, in concatenation order."""
+    dense, chunks = {}, []
+    for m in meshes:
+        if m["chunk"] not in dense:
+            dense[m["chunk"]] = len(chunks)
+            chunks.append(m["chunk"])
+    arrival = np.array([dense[m["chunk"]] for m in meshes], np.int64)
+    order = np.argsort(arrival, kind="stable")
+    chunk_of = arrival[order]
+    nv = np.array([len(meshes[i]["vertices"]) for i in order], np.int64)
+    ni = np.array([int(meshes[i]["num_internal"]) for i in order], np.int64)
+    nt = np.array([len(np.asarray(meshes[i]["triangles"]).reshape(-1, 3)) for i in order], np.int64)
+    bases = np.concatenate([[0], np.cumsum(nv)]).astype(np.int64)
+    tri_bases = np.concatenate([[0], np.cumsum(nt)]).astype(np.int64)
+    n = int(bases[-1])
+    ext_gid = [np.arange(bases[p] + ni[p], bases[p + 1]) for p in range(len(order))]
+    ext_gid = np.concatenate(ext_gid) if ext_gid else np.zeros(0, np.int64)
+    ext_key = [np.asarray(meshes[i]["keys"], np.uint64).reshape(-1) for i in order]
+    ext_key = np.concatenate(ext_key) if ext_key else np.zeros(0, np.uint64)
+    assert len(ext_key) == len(ext_gid), "one key per external vertex"
+    ext_chunk = np.repeat(chunk_of, nv - ni)
+    comp_rep = np.arange(n, dtype=np.int64)
+    out_rep = np.arange(n, dtype=np.int64)
+    if len(ext_key):
+        by_key = np.argsort(ext_key, kind="stable")              # ties stay in concatenation order
+        k, g, c = ext_key[by_key], ext_gid[by_key], ext_chunk[by_key]
+        new_key = np.concatenate([[True], k[1:] != k[:-1]])
+        new_chunk = new_key | np.concatenate([[True], c[1:] != c[:-1]])     # chunks ascend inside a key's run
+        comp_rep[g] = g[np.flatnonzero(new_key)[np.cumsum(new_key) - 1]]
+        out_rep[g] = g[np.flatnonzero(new_chunk)[np.cumsum(new_chunk) - 1]]
+    tris = [np.asarray(meshes[i]["triangles"], np.int64).reshape(-1, 3) + bases[p] for p, i in enumerate(order)]
+    all_t = np.concatenate(tris) if tris else np.zeros((0, 3), np.int64)
+    ct = comp_rep[all_t]
+    rows = np.concatenate([ct[:, 0], ct[:, 1], np.arange(n)])
+    cols = np.concatenate([ct[:, 1], ct[:, 2], comp_rep])
+    graph = coo_matrix((np.ones(len(rows), np.int8), (rows, cols)), shape=(n, n))
+    label = connected_components(graph, directed=False)[1] if n else np.zeros(0, np.int64)
+    return dict(order=order, chunk_of=chunk_of, chunks=chunks, bases=bases, tri_bases=tri_bases, comp_rep=comp_rep,
+                out_rep=out_rep, label=label.astype(np.int64), triangles=all_t, ext_gid=ext_gid, ext_key=ext_key)
+
+
+def expected_boundary(meshes):
+    """The exact boundary export of a sink that holds `meshes`: (keys, key_root, root_vertices, root_triangles).
+    keys: the distinct external keys, ascending.  A component's root is the smallest vertex id among its welded
+    representatives (comp_rep[g] == g) in mesh_sink_labels' order; roots are numbered densely in ascending id.
+    key_root[k]: the dense root of the component that holds key k; root_vertices[d]: its welded vertices;
+    root_triangles[d]: the triangles whose first index lies in it."""
+    L = mesh_sink_labels(meshes)
+    n = len(L["comp_rep"])
+    reps = np.flatnonzero(L["comp_rep"] == np.arange(n))                    # ascending ids
+    ncomp = int(L["label"].max()) + 1 if n else 0
+    root_id = np.full(ncomp, n, np.int64)
+    np.minimum.at(root_id, L["label"][reps], reps)                          # smallest representative per component
+    assert (root_id < n).all()
+    dense_of_label = np.argsort(np.argsort(root_id))                        # rank of the root among all roots
+    dense = dense_of_label[L["label"]] if n else np.zeros(0, np.int64)      # per vertex
+    root_vertices = np.bincount(dense[reps], minlength=ncomp).astype(np.uint64)
+    root_triangles = np.bincount(dense[L["triangles"][:, 0]], minlength=ncomp).astype(np.uint64)
+    keys, first = np.unique(L["ext_key"], return_index=True)
+    key_root = dense[L["ext_gid"][first]].astype(np.uint32)
+    return keys.astype(np.uint64), key_root, root_vertices, root_triangles
+
+
 def mesh_sink(meshes, prune_threshold=0.0):
     """meshes: dicts with chunk (hashable, arrival order = chunk order), vertices (n,3) float32 with the internal
     vertices first, num_internal, keys (n - num_internal,) uint64, triangles (t,3) uint32.
