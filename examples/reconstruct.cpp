@@ -12,10 +12,13 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--simplify N] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
  * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
+ * --fill-holes N (device weld only, 3 <= N <= 1048576): directly after the weld, every boundary loop of at most N sides of every
+ *   output chunk is capped by a fan to the mean of its vertices, where the chunk lies -- before --check, --simplify, --smooth
+ *   and --normals; the loops on a seam between two chunks stay open; one line with the statistics.
  * --simplify N (device weld only, N > 0): before the write, every output chunk is vertex-clustered where it lies, in cells of
  *   N grid spacings counted from one cell below the bounding grid's low corner; one line with the statistics.
  * --smooth N (device weld only, N > 0): before the write, every output chunk gets N Taubin iterations (lambda 0.5, mu -0.53)
@@ -43,8 +46,8 @@ int main(int argc, char **argv)
     bool hostWeld = false, checkTopology = false, writeNormals = false;
     std::uint64_t bufferBytes = 0, hbmSplats = 0;
     float simplifyCells = 0.0f;
-    bool simplifyGiven = false, smoothGiven = false;
-    long smoothIterations = 0;
+    bool simplifyGiven = false, smoothGiven = false, fillGiven = false;
+    long smoothIterations = 0, fillEdges = 0;
     std::string tmpDir;
     std::vector<std::string> plys, rest;
     for (int i = 1; i < argc; i++)
@@ -74,6 +77,11 @@ int main(int argc, char **argv)
             smoothIterations = atol(argv[++i]);
             smoothGiven = true;
         }
+        else if (a == "--fill-holes" && i + 1 < argc)
+        {
+            fillEdges = atol(argv[++i]);
+            fillGiven = true;
+        }
         else if (a == "--buffer" && i + 1 < argc)
             bufferBytes = strtoull(argv[++i], NULL, 10);
         else if (a == "--tmp-dir" && i + 1 < argc)             // --weld host: the welder's blocks in temporary files there (src/mlsgpu_core.cpp --tmp-dir)
@@ -87,7 +95,7 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--simplify N] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
         return 2;
     }
@@ -109,6 +117,16 @@ int main(int argc, char **argv)
     if (smoothGiven && hostWeld)
     {
         std::cerr << "--smooth needs --weld device: the host welder's output is not on the device\n";
+        return 2;
+    }
+    if (fillGiven && !(fillEdges >= 3 && fillEdges <= (long) MLSGPU_FILL_MAX_EDGES))
+    {
+        std::cerr << "--fill-holes takes the longest loop to fill, 3 to 1048576 sides\n";
+        return 2;
+    }
+    if (fillGiven && hostWeld)
+    {
+        std::cerr << "--fill-holes needs --weld device: the host welder's output is not on the device\n";
         return 2;
     }
     if (writeNormals && hostWeld)
@@ -178,6 +196,8 @@ int main(int argc, char **argv)
         float simplifyCell = 0.0f, simplifyOrigin[3] = {0.0f, 0.0f, 0.0f};
         mlsgpu_smooth_stats smoothed = mlsgpu_smooth_stats();
         std::size_t smoothedChunks = 0;
+        mlsgpu_fill_stats filled = mlsgpu_fill_stats();
+        std::size_t filledChunks = 0;
         {
             BucketFarm farm(devices, cfg, 4 /* --device-threads */, 1, hostWeld ? NULL : &deviceMesher);
             if (hostWeld)
@@ -208,6 +228,11 @@ int main(int argc, char **argv)
         else
         {
             const std::size_t chunks = deviceMesher.finalize();
+            if (fillGiven)
+            {
+                filled = deviceMesher.fillHoles((std::uint32_t) fillEdges);
+                filledChunks = chunks;
+            }
             if (simplifyGiven)
             {
                 simplifyCell = simplifyCells * spacing;
@@ -229,6 +254,14 @@ int main(int argc, char **argv)
                     grid.extents[3], grid.extents[4], grid.extents[5], bins, devices.size(), hostWeld ? "host" : "device",
                     written, (unsigned long long) st[4], (unsigned long long) st[5], (unsigned long long) st[2],
                     (unsigned long long) st[3]);
+        if (fillGiven)
+            std::printf("fill-holes chunks %zu boundary-edges %llu loops %llu filled %llu long %llu pinned %llu irregular-edges %llu "
+                        "vertices %llu -> %llu triangles %llu -> %llu\n",
+                        filledChunks, (unsigned long long) filled.boundaryEdges, (unsigned long long) filled.loops,
+                        (unsigned long long) filled.filledLoops, (unsigned long long) filled.longLoops,
+                        (unsigned long long) filled.pinnedLoops, (unsigned long long) filled.irregularEdges,
+                        (unsigned long long) filled.numVertices, (unsigned long long) filled.outVertices,
+                        (unsigned long long) filled.numTriangles, (unsigned long long) filled.outTriangles);
         if (simplifyGiven)
             std::printf("simplify cell %.9g origin %.9g %.9g %.9g vertices %llu -> %llu triangles %llu -> %llu collapsed %llu "
                         "duplicate %llu\n",

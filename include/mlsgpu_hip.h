@@ -836,6 +836,98 @@ int mlsgpu_hip_mesh_smooth(mlsgpu_ctx *ctx, const float *dVertices, uint64_t num
  * an error the sink's results are dropped: finalize again. */
 int mlsgpu_hip_mesher_smooth(mlsgpu_mesher *mesher, uint32_t iterations, float lambda, float mu, uint32_t boundary,
                              mlsgpu_smooth_stats *stats);
+
+/* ---- hole filling of a device-resident mesh: every small boundary loop is capped by a fan of triangles to the mean of its
+ *      vertices, before the mesh crosses the link.  An MLS surface stops where the splats get sparse, and
+ *      mlsgpu_hip_mesh_topology counts the holes that leaves (numBoundaries); this closes them.  The reference has no
+ *      counterpart.  Deterministic: every float and double operation below is ONE correctly rounded IEEE operation (no
+ *      contraction), and every sum is an integer sum -- the output depends neither on the schedule nor on the order of the
+ *      triangles.
+ *      1. A triangle with an index >= V is counted in outOfRangeTriangles (the index is compared, never used as an address);
+ *         otherwise a triangle with two equal indices is counted in degenerateTriangles.  Neither takes part; both are
+ *         copied to the output unchanged.
+ *      2. A participating triangle (a, b, c) gives the directed sides a -> b, b -> c, c -> a.  A directed side a -> b is a
+ *         BOUNDARY side if it occurs exactly once and b -> a does not occur at all; boundaryEdges is their number (it agrees
+ *         with mlsgpu_smooth_stats.boundaryEdges).
+ *      3. A vertex on a boundary side is REGULAR if exactly one boundary side leaves it and exactly one enters it.
+ *      4. In the graph whose edges are the boundary sides, a connected component in which every vertex is regular is one
+ *         simple directed cycle of n >= 3 sides over n vertices: a LOOP (loops).  The sides of a component with an irregular
+ *         vertex are counted in irregularEdges and never filled.  longestLoop is the largest n, 0 without a loop.
+ *      5. A loop with n > maxEdges is long (longLoops); otherwise a loop with a pinned vertex is pinned (pinnedLoops); every
+ *         other loop is filled (filledLoops): loops = filledLoops + longLoops + pinnedLoops, and filledEdges is the sum of n
+ *         over the filled loops.
+ *      6. M = the largest |coordinate| over all V input vertices; e is the integer with 2^e <= M < 2^(e + 1) (a subnormal M
+ *         has its true exponent), e = 0 if M == 0 or V == 0.  scaleExponent = e, as for the smoothing.
+ *      7. Q(x) = llrint(ldexp((double) x, 30 - e)), ties to even.  For a filled loop, per axis, S = the int64 sum of Q over
+ *         its n vertices (|S| < 2^51: (double) S is exact); the new vertex is (float) ldexp((double) S / (double) n, e - 30).
+ *      8. The filled loops are numbered j = 0, 1, ... in ascending order of their smallest vertex index; loop j's new vertex
+ *         has index V + j.
+ *      9. Each boundary side a -> b of filled loop j gives the triangle (b, a, V + j): it carries the missing opposite side,
+ *         so the orientation is kept.
+ *      10. Output vertices: the V input vertices bit for bit, then the new ones.  Output triangles: the T input triangles
+ *         bit for bit and in their order, then the new ones -- over all filled loops together -- in ascending order of a
+ *         (a regular a leaves exactly one boundary side, so the order is total).
+ *      Renumbering the input vertices leaves the output the same as a set of triangles over position triples.  On a
+ *      manifold input the output is manifold; per filled loop numBoundaries drops by 1, boundaryEdges by n, and the Euler
+ *      characteristic rises by 1.  Scaling every coordinate by 2^s scales the new vertices exactly and moves scaleExponent
+ *      by s (away from the subnormals).
+ *      Limit: a fan to the mean is meant for small, roughly flat loops.  The outer rim of a small open sheet is a loop like
+ *      any other and is capped too: maxEdges is the caller's guard against that. ---- */
+#define MLSGPU_FILL_MAX_EDGES 1048576u  /* 2^20 */
+typedef struct mlsgpu_fill_stats
+{
+    uint64_t numVertices, numTriangles;
+    uint64_t outOfRangeTriangles;   /* an index >= numVertices */
+    uint64_t degenerateTriangles;   /* in range, two indices equal */
+    uint64_t boundaryEdges;         /* step 2 */
+    uint64_t irregularEdges;        /* boundary sides of components with an irregular vertex */
+    uint64_t loops, filledLoops, longLoops, pinnedLoops;        /* steps 4 and 5 */
+    uint64_t filledEdges;           /* boundary sides of the filled loops = new triangles */
+    uint64_t longestLoop;           /* sides of the longest loop, filled or not */
+    uint64_t outVertices;           /* numVertices + filledLoops */
+    uint64_t outTriangles;          /* numTriangles + filledEdges */
+    int64_t scaleExponent;          /* e of step 6 */
+} mlsgpu_fill_stats;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_fill_stats) == 120, "mlsgpu_fill_stats is part of the ABI");
+#else
+typedef char mlsgpu_fill_stats_size_is_120[sizeof(mlsgpu_fill_stats) == 120 ? 1 : -1];
+#endif
+/* numVertices packed float xyz and numTriangles uint32 index triples on ctx's device -> dOutVertices with room for
+ * capVertices vertices and dOutTriangles with room for capTriangles triangles, which must not overlap the inputs.  dPinned is
+ * NULL or one byte per input vertex, non-zero for a pinned one (step 5).  MLSGPU_ERR_INVALID, before anything touches the
+ * device, unless 3 <= maxEdges <= MLSGPU_FILL_MAX_EDGES and stats is not NULL; MLSGPU_ERR_LENGTH, before anything is
+ * allocated, unless numVertices < 2^32 and 3 * numTriangles < 2^32.  MLSGPU_ERR_INVALID for a coordinate that is not finite
+ * (counted on the device).  MLSGPU_ERR_LENGTH if the result would break outVertices < 2^32 or 3 * outTriangles < 2^32.
+ * MLSGPU_ERR_LENGTH if capVertices < outVertices or capTriangles < outTriangles: *stats is complete then and the outputs are
+ * untouched, which is how a caller asks for the sizes -- NULL outputs with zero capacities.  No vertices or no triangles is
+ * not an error.  Scratch is allocated for the call and freed on return: 72 bytes per triangle (three directed side records:
+ * the two sides of the sort's 64-bit keys and 32-bit values), 52 bytes per vertex (the boundary forest's parent, the counts
+ * of sides out and in, the next vertex, the loop's length, flags and number 4 each, the three sums 24), the sort's histogram
+ * and the scan's tile sums; MLSGPU_ERR_NOMEM if the device does not have it.  Blocks until the statistics are there: one stream
+ * synchronisation behind the sums (the counts size the result; M stays on the device), and, if the capacities suffice, one
+ * at the end. */
+int mlsgpu_hip_mesh_fill_holes(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices, const uint32_t *dTriangles,
+                               uint64_t numTriangles, uint32_t maxEdges, const uint8_t *dPinned, float *dOutVertices,
+                               uint64_t capVertices, uint32_t *dOutTriangles, uint64_t capTriangles, mlsgpu_fill_stats *stats);
+/* The same for every output chunk of a finalized device sink that has triangles, on the mesher's context.  The chunks GROW:
+ * new output arrays of the summed sizes are built, each filled chunk behind the one before, and take the place of the old
+ * ones; the chunks' normals are dropped, so normals requested afterwards are those of the filled chunk.  While both
+ * generations exist the sink holds 12 bytes per vertex and per triangle of the old AND of the new meshes, plus one chunk's
+ * scratch as above and, with more than one chunk, the seam mask: 1 byte per vertex, and 40 bytes per vertex and a sort's
+ * histogram while it is built.  Chunks without triangles stay in the list, empty; mlsgpu_hip_mesher_chunk, _chunk_topology,
+ * _chunk_normals and _write_ply then serve the filled chunks, and mlsgpu_hip_mesher_stats keeps reporting the finalize's
+ * numbers.  *stats is the sum over the chunks, longestLoop and scaleExponent the maxima.
+ * SEAMS: the seam between two chunks (split output files) is a boundary of each and must not be capped.  With more than one
+ * chunk every vertex whose 12 position bytes equal, as bits, those of a vertex of ANOTHER chunk is pinned -- a welded vertex
+ * two chunks share is copied to both with identical bits -- so a loop that touches a seam is counted in pinnedLoops and left
+ * open.  A simplify and a smooth under MLSGPU_SMOOTH_BOUNDARY_CURVE move the shared vertices of each chunk on their own and
+ * un-match the seams: fill holes BEFORE them.
+ * Every chunk runs twice, once for its sizes and once into its place.  MLSGPU_ERR_INVALID before finalize and for a maxEdges
+ * outside its range; may be called again (on the filled chunks).  The new arrays take the old ones' place only when every chunk
+ * is done: an error leaves the sink's results as they were. */
+int mlsgpu_hip_mesher_fill_holes(mlsgpu_mesher *mesher, uint32_t maxEdges, mlsgpu_fill_stats *stats);
+
 /* ---- host mesh sink: OOCMesher's weld as the reference runs it, on the host (src/mesher.cpp:220-469, north_star:
  *      "welding stays on host").  add() is MesherBase::InputFunctor: local components of the block by union-find over
  *      two edges per triangle (computeLocalComponents, :220-236), clumps merged across blocks through the external

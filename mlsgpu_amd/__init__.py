@@ -5,12 +5,10 @@ classes in ``mlsgpu_amd/host`` that mirror the reference's call surface.  This P
 a thin ctypes binding of the same C-ABI, used by the tests and by bench.py.  There is no CPU
 fallback: importing :mod:`mlsgpu_amd.binding` without the built library raises.
 """
-from .binding import (BucketFarm, Context, DensityError, DeviceBuffer, FormatError, HipError, HostMesher, InvalidArgument, LengthError, Marching, Mesher, MlsError,
-                      MlsFunctor, NormalsStats, SPLAT_DTYPE, SimplifyStats, SmoothStats, SplatTree, Swathe, Topology, Worker, WorkerConfig, lib, library_path, mesh_normals, mesh_simplify,
-                      mesh_smooth,
-                      mesh_topology)
+from .binding import (BucketFarm, Context, DensityError, DeviceBuffer, FillStats, FormatError, HipError, HostMesher, InvalidArgument, LengthError, Marching, Mesher, MlsError,
+                      MlsFunctor, NormalsStats, SPLAT_DTYPE, SimplifyStats, SmoothStats, SplatTree, Swathe, Topology, Worker, WorkerConfig, lib, library_path, mesh_fill_holes,
+                      mesh_normals, mesh_simplify, mesh_smooth, mesh_topology, mesher_fill_holes)
 
-__all__ = ["BucketFarm", "Context", "DensityError", "DeviceBuffer", "FormatError", "HipError", "HostMesher", "InvalidArgument", "LengthError", "Marching", "Mesher", "MlsError",
-           "MlsFunctor", "NormalsStats", "SPLAT_DTYPE", "SimplifyStats", "SmoothStats", "SplatTree", "Swathe", "Topology", "Worker", "WorkerConfig", "lib", "library_path", "mesh_normals", "mesh_simplify",
-           "mesh_smooth",
-           "mesh_topology"]
+__all__ = ["BucketFarm", "Context", "DensityError", "DeviceBuffer", "FillStats", "FormatError", "HipError", "HostMesher", "InvalidArgument", "LengthError", "Marching", "Mesher", "MlsError",
+           "MlsFunctor", "NormalsStats", "SPLAT_DTYPE", "SimplifyStats", "SmoothStats", "SplatTree", "Swathe", "Topology", "Worker", "WorkerConfig", "lib", "library_path", "mesh_fill_holes",
+           "mesh_normals", "mesh_simplify", "mesh_smooth", "mesh_topology", "mesher_fill_holes"]

@@ -154,6 +154,22 @@ class SmoothStats(C.Structure):
         return dict((name, (float if kind is C.c_double else int)(getattr(self, name))) for name, kind in self._fields_)
 
 
+class FillStats(C.Structure):
+    """mlsgpu_fill_stats: what took no part, the boundary sides and their loops, what was filled, the sizes of the result."""
+    _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
+                ("degenerateTriangles", C.c_uint64), ("boundaryEdges", C.c_uint64), ("irregularEdges", C.c_uint64),
+                ("loops", C.c_uint64), ("filledLoops", C.c_uint64), ("longLoops", C.c_uint64), ("pinnedLoops", C.c_uint64),
+                ("filledEdges", C.c_uint64), ("longestLoop", C.c_uint64), ("outVertices", C.c_uint64),
+                ("outTriangles", C.c_uint64), ("scaleExponent", C.c_int64)]
+
+    def as_dict(self):
+        return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
+
+
+# MLSGPU_FILL_MAX_EDGES: the longest loop that max_edges may admit
+FILL_MAX_EDGES = 1 << 20
+
+
 # MLSGPU_SMOOTH_BOUNDARY_*: what the vertices on a boundary edge do
 SMOOTH_BOUNDARY_FIXED, SMOOTH_BOUNDARY_CURVE = 0, 1
 
@@ -357,6 +373,8 @@ def lib():
     sig("mlsgpu_hip_mesher_chunk_normals", C.c_int, vp, u32, P(vp), P(NormalsStats))
     sig("mlsgpu_hip_mesh_smooth", C.c_int, vp, vp, u64, vp, u64, u32, C.c_float, C.c_float, u32, vp, P(SmoothStats))
     sig("mlsgpu_hip_mesher_smooth", C.c_int, vp, u32, C.c_float, C.c_float, u32, P(SmoothStats))
+    sig("mlsgpu_hip_mesh_fill_holes", C.c_int, vp, vp, u64, vp, u64, u32, vp, vp, u64, vp, u64, P(FillStats))
+    sig("mlsgpu_hip_mesher_fill_holes", C.c_int, vp, u32, P(FillStats))
     sig("mlsgpu_hip_write_ply_normals", C.c_int, C.c_char_p, vp, vp, u64, vp, u64, vp, u32)
     sig("mlsgpu_hip_mesher_write_ply_normals", C.c_int, vp, C.c_uint32, C.c_char_p, vp, C.c_uint32, u64)
     sig("mlsgpu_hip_bucket", C.c_int, vp, vp, u64, P(GridStruct), P(BucketParams), BUCKET_FN, vp, P(u64))
@@ -381,6 +399,7 @@ def lib():
 
 
 _ERRORS = {1: InvalidArgument, 2: LengthError, 3: HipError, 4: HipError, 5: MlsError, 6: DensityError, 7: FormatError}
+_LENGTH = 2     # MLSGPU_ERR_LENGTH: also how mesh_fill_holes answers a question for its sizes
 
 
 def check(rc):
@@ -896,6 +915,15 @@ class Mesher:
         check(lib().mlsgpu_hip_mesher_smooth(self.h, int(iterations), float(lam), float(mu), int(boundary), C.byref(st)))
         return st.as_dict()
 
+    def fill_holes(self, max_edges):
+        """Every output chunk of the finalized sink with its boundary loops of at most max_edges sides capped (mesh_fill_holes);
+        the loops that touch a seam between two chunks stay open.  The chunks grow into new arrays: addresses from an earlier
+        chunk() are gone.  Call it before simplify and smooth.  Returns the statistics: counts summed over the chunks,
+        longestLoop and scaleExponent the largest."""
+        st = FillStats()
+        check(lib().mlsgpu_hip_mesher_fill_holes(self.h, int(max_edges), C.byref(st)))
+        return st.as_dict()
+
     def write_ply(self, i, path, comments=(), buffer_bytes=0):
         """Output chunk i straight from HBM into FastPly::Writer's file through a bounded pinned buffer."""
         arr = (C.c_char_p * max(len(comments), 1))(*[c.encode("ascii") for c in comments])
@@ -1057,6 +1085,59 @@ def mesh_smooth(ctx, vertices, triangles, iterations, lam, mu, boundary=SMOOTH_B
         for buf in own:
             buf.free()
     return out, st.as_dict()
+
+
+def mesh_fill_holes(ctx, vertices, triangles, max_edges, pinned=None, num_vertices=None, num_triangles=None):
+    """Hole filling on the device (mlsgpu_hip_mesh_fill_holes): every boundary loop of at most max_edges sides, none of whose
+    vertices is pinned, gets a fan of triangles to the mean of its vertices; bit-reproducible whatever the schedule or the
+    order of the triangles.  `vertices` / `triangles` are numpy arrays (uploaded for the call) or DeviceBuffers of packed
+    float32 xyz / uint32 triples, `pinned` is None, a numpy array of one flag per vertex or a DeviceBuffer of one byte per
+    vertex.  One call asks for the sizes, a second one fills.  Returns (vertices float32 [V', 3], triangles uint32 [T', 3],
+    statistics as a dict), the arrays downloaded: the input's rows first, then the new ones."""
+    own = []
+
+    def on_device(a, dtype, count):
+        if isinstance(a, DeviceBuffer):
+            return a, (a.nbytes // 12 if count is None else count)
+        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
+        buf = DeviceBuffer(ctx, array=a) if a.size else None
+        if buf is not None:
+            own.append(buf)
+        return buf, (len(a) if count is None else count)
+
+    st = FillStats()
+    try:
+        dv, nv = on_device(vertices, np.float32, num_vertices)
+        dt, nt = on_device(triangles, np.uint32, num_triangles)
+        dp = pinned
+        if pinned is not None and not isinstance(pinned, DeviceBuffer):
+            mask = np.ascontiguousarray(np.asarray(pinned) != 0, np.uint8).reshape(-1)
+            if len(mask) != nv:
+                raise InvalidArgument("pinned has %d entries for %d vertices" % (len(mask), nv))
+            dp = DeviceBuffer(ctx, array=mask) if mask.size else None
+            if dp is not None:
+                own.append(dp)
+        args = (ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, int(max_edges), dp.ptr if dp else None)
+        rc = lib().mlsgpu_hip_mesh_fill_holes(*args, None, 0, None, 0, C.byref(st))
+        if rc != 0 and not (rc == _LENGTH and st.outVertices + st.outTriangles > 0):
+            check(rc)
+        ov = DeviceBuffer(ctx, nbytes=12 * st.outVertices) if st.outVertices else None
+        ot = DeviceBuffer(ctx, nbytes=12 * st.outTriangles) if st.outTriangles else None
+        own.extend(x for x in (ov, ot) if x is not None)
+        if rc != 0:
+            check(lib().mlsgpu_hip_mesh_fill_holes(*args, ov.ptr if ov else None, st.outVertices, ot.ptr if ot else None,
+                                                   st.outTriangles, C.byref(st)))
+        out_v = ov.download(np.float32, 3 * st.outVertices).reshape(-1, 3) if ov else np.zeros((0, 3), np.float32)
+        out_t = ot.download(np.uint32, 3 * st.outTriangles).reshape(-1, 3) if ot else np.zeros((0, 3), np.uint32)
+    finally:
+        for buf in own:
+            buf.free()
+    return out_v, out_t, st.as_dict()
+
+
+def mesher_fill_holes(mesher, max_edges):
+    """Mesher.fill_holes as a function, beside mesh_fill_holes."""
+    return mesher.fill_holes(max_edges)
 
 
 def mesher_smooth(mesher, iterations, lam=0.5, mu=-0.53, boundary=SMOOTH_BOUNDARY_FIXED):

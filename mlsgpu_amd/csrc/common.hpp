@@ -328,6 +328,10 @@ static inline uint32_t mostOfLanes(uint32_t count, Extent extent)
 static inline uint32_t divUp(uint64_t a, uint64_t b) { return (uint32_t) ((a + b - 1) / b); }
 static inline uint32_t roundUp(uint32_t a, uint32_t b) { return (a + b - 1) / b * b; }
 
+/* fill.hip, for the sink's hole filling (mesher.hip): dPinned[g] = 1 for each of the n packed xyz rows that equals, bit for
+ * bit, a row of another chunk, 0 for the others; chunk c holds the rows [starts[c], starts[c + 1]) (host memory).  Blocks. */
+int seamMask(mlsgpu_ctx *ctx, const float *dVertices, uint64_t n, const uint64_t *starts, uint32_t numChunks, uint8_t *dPinned);
+
 /* ---------------------------------------------------------------- device helpers */
 
 #ifdef __HIPCC__

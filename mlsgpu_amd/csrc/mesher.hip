@@ -1332,6 +1332,86 @@ MLSGPU_API int mlsgpu_hip_mesher_smooth(mlsgpu_mesher *m, uint32_t iterations, f
     return MLSGPU_OK;
 }
 
+/* Every output chunk that has triangles through mlsgpu_hip_mesh_fill_holes (fill.hip).  The chunks grow, so they cannot stay
+ * where they lie: a first round asks every chunk for its sizes, a second fills it into new arrays, behind the chunk before.
+ * Nothing of the sink changes before the last chunk is done: an error leaves the results as they were. */
+MLSGPU_API int mlsgpu_hip_mesher_fill_holes(mlsgpu_mesher *m, uint32_t maxEdges, mlsgpu_fill_stats *stats)
+{
+    REQUIRE(m != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
+    /* mlsgpu_hip_mesh_fill_holes's own check, here so that a refused parameter does no work */
+    REQUIRE(maxEdges >= 3 && maxEdges <= MLSGPU_FILL_MAX_EDGES, MLSGPU_ERR_INVALID);
+    mlsgpu_ctx *const ctx = m->ctx;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    std::memset(stats, 0, sizeof(*stats));
+    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
+    /* the seams: with several chunks, a vertex that another chunk has too is pinned */
+    DeviceArray<uint8_t> pinned;
+    if (m->outChunks.size() > 1)
+    {
+        PROPAGATE(pinned.alloc(m->chunkVStart[nc]));
+        PROPAGATE(seamMask(ctx, m->outVertices, m->chunkVStart[nc], m->chunkVStart.data(), (uint32_t) nc, pinned));
+    }
+    std::vector<mlsgpu_fill_stats> one(nc);
+    std::vector<uint64_t> vStart(nc + 1, 0), tStart(nc + 1, 0);
+    for (size_t c = 0; c < nc; c++)
+    {
+        const uint64_t v0 = m->chunkVStart[c], t0 = m->chunkTStart[c];
+        const uint64_t nv = m->chunkVStart[c + 1] - v0, nt = m->chunkTStart[c + 1] - t0;
+        std::memset(&one[c], 0, sizeof(one[c]));
+        if (nt > 0)     /* a chunk without triangles has no output (finalize), and keeps none */
+        {
+            /* no room at all: the call stops at its capacity check, with the sizes */
+            const int rc = mlsgpu_hip_mesh_fill_holes(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, maxEdges,
+                                                      pinned.get() != nullptr ? pinned + v0 : nullptr, nullptr, 0, nullptr, 0, &one[c]);
+            if (rc != MLSGPU_ERR_LENGTH)
+                return rc != MLSGPU_OK ? rc : setError(MLSGPU_ERR_HIP, "mesher fill holes: a chunk with triangles has an empty result");
+        }
+        vStart[c + 1] = vStart[c] + one[c].outVertices;
+        tStart[c + 1] = tStart[c] + one[c].outTriangles;
+    }
+    DeviceArray<float> newVertices;
+    DeviceArray<uint32_t> newTriangles;
+    PROPAGATE(newVertices.alloc(std::max<uint64_t>(3 * vStart[nc], 1)));
+    PROPAGATE(newTriangles.alloc(std::max<uint64_t>(3 * tStart[nc], 1)));
+    bool first = true;
+    for (size_t c = 0; c < nc; c++)
+    {
+        const uint64_t v0 = m->chunkVStart[c], t0 = m->chunkTStart[c];
+        const uint64_t nv = m->chunkVStart[c + 1] - v0, nt = m->chunkTStart[c + 1] - t0;
+        if (nt == 0)
+            continue;
+        PROPAGATE(mlsgpu_hip_mesh_fill_holes(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, maxEdges,
+                                             pinned.get() != nullptr ? pinned + v0 : nullptr, newVertices + 3 * vStart[c],
+                                             one[c].outVertices, newTriangles + 3 * tStart[c], one[c].outTriangles, &one[c]));
+        const mlsgpu_fill_stats &s = one[c];
+        stats->numVertices += s.numVertices;
+        stats->numTriangles += s.numTriangles;
+        stats->outOfRangeTriangles += s.outOfRangeTriangles;
+        stats->degenerateTriangles += s.degenerateTriangles;
+        stats->boundaryEdges += s.boundaryEdges;
+        stats->irregularEdges += s.irregularEdges;
+        stats->loops += s.loops;
+        stats->filledLoops += s.filledLoops;
+        stats->longLoops += s.longLoops;
+        stats->pinnedLoops += s.pinnedLoops;
+        stats->filledEdges += s.filledEdges;
+        stats->longestLoop = std::max(stats->longestLoop, s.longestLoop);
+        stats->outVertices += s.outVertices;
+        stats->outTriangles += s.outTriangles;
+        stats->scaleExponent = first ? s.scaleExponent : std::max(stats->scaleExponent, s.scaleExponent);
+        first = false;
+    }
+    /* the new generation takes the old one's place (which goes with this call) */
+    m->outVertices = std::move(newVertices);
+    m->outTriangles = std::move(newTriangles);
+    m->chunkVStart = vStart;
+    m->chunkTStart = tStart;
+    m->dropNormals();           /* the chunks have changed and moved */
+    return MLSGPU_OK;
+}
+
 /* The normals (normals.hip) of dense chunk c of a finalized sink, computed where the chunk lies at the first request.  Under
  * the mutex. */
 int mlsgpu_mesher::chunkNormals(uint32_t c, const float **dNormals, mlsgpu_normals_stats *out)

@@ -145,6 +145,22 @@ inline mlsgpu_simplify_stats simplify(const Context &ctx, const Buffer<float> &v
     return st;
 }
 
+/// Hole filling of a mesh in device memory (mlsgpu_hip_mesh_fill_holes): every boundary loop of at most maxEdges sides, none of
+/// whose vertices `pinned` (NULL, or one byte per vertex) marks, gets a fan to the mean of its vertices.  outVertices /
+/// outTriangles have room for capVertices / capTriangles and do not overlap the inputs; with too little room (NULL and 0 ask for
+/// the sizes) nothing is written, *st is complete and std::length_error is thrown.
+inline mlsgpu_fill_stats fillHoles(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
+                                   const Buffer<std::uint32_t> &triangles, std::uint64_t numTriangles, std::uint32_t maxEdges,
+                                   const std::uint8_t *pinned, float *outVertices, std::uint64_t capVertices,
+                                   std::uint32_t *outTriangles, std::uint64_t capTriangles, mlsgpu_fill_stats *st = NULL)
+{
+    mlsgpu_fill_stats own;
+    mlsgpu_fill_stats *const s = st != NULL ? st : &own;
+    check(mlsgpu_hip_mesh_fill_holes(ctx.get(), vertices.get(), numVertices, triangles.get(), numTriangles, maxEdges, pinned,
+                                     outVertices, capVertices, outTriangles, capTriangles, s));
+    return *s;
+}
+
 /// Taubin lambda|mu smoothing of a mesh in device memory (mlsgpu_hip_mesh_smooth): outVertices has room for 3 floats per
 /// vertex and is either `vertices` itself (in place) or does not overlap the inputs.
 inline mlsgpu_smooth_stats smooth(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
@@ -655,6 +671,15 @@ public:
     {
         mlsgpu_simplify_stats st;
         check(mlsgpu_hip_mesher_simplify(h, origin, cellSize, &st));
+        return st;
+    }
+    /// Every output chunk of the finalized mesher with its boundary loops of at most maxEdges sides capped
+    /// (mlsgpu_hip_mesher_fill_holes); directly behind finalize(), before simplify() and smooth(), which un-match the seams
+    /// between the chunks that this call leaves open.  Counts summed over the chunks, longestLoop and exponent the largest.
+    mlsgpu_fill_stats fillHoles(std::uint32_t maxEdges)
+    {
+        mlsgpu_fill_stats st;
+        check(mlsgpu_hip_mesher_fill_holes(h, maxEdges, &st));
         return st;
     }
     /// Every output chunk of the finalized mesher smoothed in place (mlsgpu_hip_mesher_smooth); between finalize() -- or
