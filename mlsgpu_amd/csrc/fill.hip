@@ -16,16 +16,14 @@
  *   number     a scan over the vertices with the flag at the roots of the filled loops: loop j, and its new vertex V + j
  *   emit       a scan over the vertices with the flag at the vertices of the filled loops: vertex a writes (next[a], a, V + j)
  *
- * No kernel walks a loop: no running time depends on a loop's length.  The lanes of a wave that share a root combine before
- * they touch it (a rim of 10^5 vertices hangs on ONE root).  An index >= V is compared and counted, never used as an
- * address; no address depends on a coordinate.
+ * No kernel walks a loop: no running time depends on a loop's length (meshpost.hpp's forEachRoot combines the lanes of a wave
+ * that share a root).  An index >= V is compared and counted, never used as an address; no address depends on a coordinate.
  *
  * Scratch belongs to the call: 72 bytes per triangle (three records: the two sides of the sort's 64-bit keys and 32-bit
  * values), 52 bytes per vertex (parent, out- and in-count, next, length, flags, loop number 4 each, the sums 24), the sort's
  * histogram (4 KB per 4096 records) and the scan's tile sums.
  */
-#include "common.hpp"
-#include "primitives.hpp"
+#include "meshpost.hpp"
 #include "unionfind.hpp"
 
 #include <cmath>
@@ -34,8 +32,6 @@ using namespace mlsgpu;
 
 namespace
 {
-
-typedef unsigned long long Counter;
 
 enum
 {
@@ -50,7 +46,7 @@ enum
     C_FILLED_EDGES = 8,
     C_LONGEST_LOOP = 9,
     C_NON_FINITE = 10,          /* input coordinates */
-    C_INPUT_MAX = 11,           /* the bits of the largest |coordinate|: non-negative floats order as their bits */
+    C_INPUT_MAX = 11,           /* the bits of the largest |coordinate| */
     C_FAILED = 12,              /* the union-find's retry bound was reached (its low 32 bits are the flag) */
     C_WORDS = 13
 };
@@ -61,50 +57,8 @@ enum
     F_PINNED = 2                /* a vertex of the component is pinned */
 };
 
-const uint32_t UNION_SHORTCUT = 3;      /* findRootHalving's threshold: the meshes are surfaces (as in topology.hip) */
-const uint32_t LOOP_BLOCKS = 1024;      /* workgroups of a kernel that loops over its elements and sends its counts once */
-const uint32_t SIDES_BLOCKS = 4096;     /* ... of the sides kernel, which waits for its binary searches: more waves in flight */
-const double CLAMP = 4611686018427387904.0;     /* 2^62: what a value is clamped to before it becomes an integer */
-
-/* The lanes of the wave for which `hit` holds add their number to *count with one atomic. */
-__device__ __forceinline__ void tally(bool hit, Counter *count)
-{
-    const uint64_t mask = __ballot(hit);
-    if (hit && popcBelow(mask) == 0)
-        atomicAdd(count, (Counter) __popcll(mask));
-}
-
-/* the sum over the wave, in every lane; needs the full wave */
-__device__ __forceinline__ long long waveSum64(long long v)
-{
-#pragma unroll
-    for (int step = 1; step < WAVE; step <<= 1)
-        v += __shfl_xor(v, step, WAVE);
-    return v;
-}
-
-/* step 6 of the contract: e with 2^e <= M < 2^(e + 1) from the bits of M >= 0 (a subnormal's true exponent), 0 for M == 0 */
-__host__ __device__ inline int exponentOfBits(uint32_t bits)
-{
-    if (bits == 0)
-        return 0;
-    const uint32_t field = bits >> 23;
-    if (field != 0)
-        return (int) field - 127;
-    int high = 0;
-    while ((bits >> (high + 1)) != 0)
-        high++;
-    return high - 149;
-}
-
-/* 2^k as a double, for a k that gives a normal one */
-__host__ __device__ inline double powerOfTwo(int k)
-{
-    const long long bits = (long long) (1023 + k) << 52;
-    double d;
-    __builtin_memcpy(&d, &bits, sizeof(d));
-    return d;
-}
+/* LOOP_BLOCKS for the sides kernel, which waits for its binary searches: more waves in flight */
+const uint32_t SIDES_BLOCKS = 4096;
 
 /* step 5 of the contract, from what the loops kernel left at a component's root */
 __device__ __forceinline__ bool isLoop(uint32_t length, uint32_t flags) { return length != 0 && (flags & F_IRREGULAR) == 0; }
@@ -116,13 +70,9 @@ __device__ __forceinline__ bool isFilled(uint32_t length, uint32_t flags, uint32
 /* A workgroup loops over the 3 V coordinates and sends its maximum and its count once. */
 __global__ __launch_bounds__(256) void extentKernel(const float *vertices, uint64_t numCoordinates, Counter *counters)
 {
-    __shared__ uint32_t sMost, sBad;
-    if (threadIdx.x == 0)
-    {
-        sMost = 0;
-        sBad = 0;
-    }
-    __syncthreads();
+    __shared__ GroupCounts<1, 1> totals;
+    totals.clear();
+    const int at[2] = {C_NON_FINITE, C_INPUT_MAX};
     uint32_t most = 0, bad = 0;
     for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < numCoordinates; i += (uint64_t) gridDim.x * blockDim.x)
     {
@@ -130,20 +80,9 @@ __global__ __launch_bounds__(256) void extentKernel(const float *vertices, uint6
         most = max(most, __float_as_uint(fabsf(x)));
         bad += isfinite(x) ? 0u : 1u;
     }
-    const uint32_t mostOfWave = waveMax(most), badOfWave = waveSum(bad);
-    if (laneId() == 0)
-    {
-        atomicMax(&sMost, mostOfWave);
-        if (badOfWave != 0)
-            atomicAdd(&sBad, badOfWave);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        atomicMax(&counters[C_INPUT_MAX], (Counter) sMost);
-        if (sBad != 0)
-            atomicAdd(&counters[C_NON_FINITE], (Counter) sBad);
-    }
+    totals.add(0, bad);
+    totals.raise(0, most);
+    totals.flush(counters, at);
 }
 
 __global__ __launch_bounds__(256) void identityKernel(uint32_t *parent, uint64_t numVertices)
@@ -153,59 +92,31 @@ __global__ __launch_bounds__(256) void identityKernel(uint32_t *parent, uint64_t
         parent[v] = (uint32_t) v;
 }
 
-/* Step 1.  The three records of a triangle that takes no part get from = V: they sort behind every other record and nothing
- * looks at them again. */
-__global__ __launch_bounds__(256) void classifyKernel(const uint32_t *tri, uint64_t numTriangles, uint64_t numVertices, uint32_t b,
-                                                      uint64_t *keys, Counter *counters)
+/* Step 1: the three directed sides of a triangle; three dead records for one that takes no part */
+__global__ __launch_bounds__(256) void classifyKernel(const uint32_t *tri, uint64_t numTriangles, SideKeys K, uint64_t *keys,
+                                                      Counter *counters)
 {
     const uint64_t t = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= numTriangles)
         return;
     const uint64_t i[3] = {tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]};
-    const bool outOfRange = i[0] >= numVertices || i[1] >= numVertices || i[2] >= numVertices;
-    const bool degenerate = !outOfRange && (i[0] == i[1] || i[1] == i[2] || i[2] == i[0]);
-    tally(outOfRange, &counters[C_OUT_OF_RANGE]);
-    tally(degenerate, &counters[C_DEGENERATE]);
-    const bool part = !outOfRange && !degenerate;
+    const TriangleDefect d = defectOf(i, K.numVertices);
+    tally(d.outOfRange, &counters[C_OUT_OF_RANGE]);
+    tally(d.degenerate, &counters[C_DEGENERATE]);
 #pragma unroll
     for (int k = 0; k < 3; k++)
-        keys[3 * t + k] = part ? (i[k] << b) | i[k == 2 ? 0 : k + 1] : numVertices << b;
+        keys[3 * t + k] = d.none() ? K.keyOf(i[k], i[k == 2 ? 0 : k + 1]) : K.dead();
 }
-
-/* the sorted records */
-struct Records
-{
-    const uint64_t *keys;
-    uint64_t n;
-    uint64_t numVertices;
-    uint32_t b;
-
-    __device__ __forceinline__ uint64_t fromOf(uint64_t key) const { return key >> b; }
-    __device__ __forceinline__ uint32_t toOf(uint64_t key) const { return (uint32_t) (key & ((uint64_t(1) << b) - 1)); }
-    /* is there a record with this key: at most 32 halvings, n < 2^32 */
-    __device__ __forceinline__ bool has(uint64_t key) const
-    {
-        uint64_t lo = 0, hi = n;
-        while (lo < hi)
-        {
-            const uint64_t mid = lo + ((hi - lo) >> 1);
-            if (keys[mid] < key) lo = mid + 1; else hi = mid;
-        }
-        return lo < n && keys[lo] == key;
-    }
-};
 
 /* Steps 2 and 3.  A vertex with several sides out keeps whichever `next` was stored last: it is irregular, and the next of an
  * irregular vertex is never read.  A workgroup loops over the records (at most 2^32 / SIDES_BLOCKS of them: its count fits 32
- * bits) and sends its count once: a real chunk has a boundary side in most waves, and one atomic per wave to ONE address is
- * served at about 10 ns apiece. */
+ * bits) and sends its count once: a real chunk has a boundary side in most waves. */
 __global__ __launch_bounds__(256) void sidesKernel(Records R, uint32_t *outCount, uint32_t *inCount, uint32_t *next, uint32_t *parent,
                                                    Counter *counters)
 {
-    __shared__ uint32_t sCount;
-    if (threadIdx.x == 0)
-        sCount = 0;
-    __syncthreads();
+    __shared__ GroupCounts<1> sides;
+    sides.clear();
+    const int at[1] = {C_BOUNDARY_EDGES};
     uint32_t count = 0;
     for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < R.n; i += (uint64_t) gridDim.x * blockDim.x)
     {
@@ -213,8 +124,7 @@ __global__ __launch_bounds__(256) void sidesKernel(Records R, uint32_t *outCount
         if (from >= R.numVertices)
             continue;           /* the record of a triangle that takes no part */
         const uint32_t to = R.toOf(key);
-        const bool alone = (i == 0 || R.keys[i - 1] != key) && (i + 1 == R.n || R.keys[i + 1] != key);
-        if (!alone || R.has(((uint64_t) to << R.b) | from))
+        if (!R.single(i, key) || R.has(R.keyOf(to, from)))
             continue;
         count++;
         atomicAdd(&outCount[from], 1u);
@@ -222,12 +132,8 @@ __global__ __launch_bounds__(256) void sidesKernel(Records R, uint32_t *outCount
         next[from] = to;
         unite(parent, (uint32_t) from, to, reinterpret_cast<uint32_t *>(&counters[C_FAILED]), UNION_SHORTCUT);
     }
-    const uint32_t ofWave = waveSum(count);
-    if (laneId() == 0 && ofWave != 0)
-        atomicAdd(&sCount, ofWave);
-    __syncthreads();
-    if (threadIdx.x == 0 && sCount != 0)
-        atomicAdd(&counters[C_BOUNDARY_EDGES], (Counter) sCount);
+    sides.add(0, count);
+    sides.flush(counters, at);
 }
 
 /* Step 4, first half.  The forest is finished (a launch lies between): a root is its component's smallest vertex.  Every
@@ -254,53 +160,33 @@ __global__ __launch_bounds__(256) void loopsKernel(uint64_t numVertices, const u
         irregular = out != 1 || in != 1;
         pin = pinned != nullptr && pinned[v] != 0;
     }
-    const uint32_t lane = laneId();
-    uint64_t pending = __ballot(on);
-    while (pending != 0)
-    {
-        const uint32_t leader = (uint32_t) __ffsll((unsigned long long) pending) - 1;
-        const uint32_t r = (uint32_t) __shfl((int) root, (int) leader, WAVE);
-        const bool same = on && root == r;
-        const uint64_t sharers = __ballot(same);
+    forEachRoot(on, root, [&](uint32_t r, bool same, uint64_t sharers, bool leads) {
         const uint32_t bits = (__ballot(same && irregular) != 0 ? F_IRREGULAR : 0) | (__ballot(same && pin) != 0 ? F_PINNED : 0);
-        if (lane == leader)
+        if (leads)
         {
             atomicAdd(&length[r], (uint32_t) __popcll(sharers));
             if (bits != 0)
                 atomicOr(&flags[r], bits);
         }
-        pending &= ~sharers;
-    }
+    });
 }
 
-/* Q of step 7: the multiplication by a power of two is exact (a float times 2^(30 - e) is a normal double or zero); rint
- * rounds ties to even.  The clamp changes no value of a finite input (those are within 2^31) and makes the conversion of
- * every other one defined: such a call is refused by its count of coordinates that are not finite. */
-__device__ __forceinline__ long long quantise(float x, double scale)
-{
-    return (long long) rint(fmin(fmax((double) x * scale, -CLAMP), CLAMP));
-}
-
-/* Steps 4 and 5, and the sums of step 7.  parent[] holds roots now, length[] and flags[] are complete.  A root counts its
+/* Steps 4 and 5, and the sums of step 7 (Q is meshpost.hpp's quantise: a finite input stays within 2^31, and a call with
+ * another is refused by its count of them).  parent[] holds roots now, length[] and flags[] are complete.  A root counts its
  * component; a vertex of an irregular component counts its sides out; a vertex of a loop that will be filled adds its
  * quantised position to the root's sums, the lanes of the wave that share the root through ONE lane.  A workgroup loops over
  * blocks of 256 vertices -- every lane of it as often, so that the wave is whole where its lanes talk -- and sends its seven
- * counts once: a real chunk has tens of thousands of small loops, and a count sent per wave to ONE address is served at about
- * 10 ns apiece (its counts fit 32 bits: filledEdges and irregularEdges are at most 3 T < 2^32 over the whole launch). */
+ * counts and its maximum once: a real chunk has tens of thousands of small loops (its counts fit 32 bits: filledEdges and
+ * irregularEdges are at most 3 T < 2^32 over the whole launch). */
 __global__ __launch_bounds__(256) void sumsKernel(const float *vertices, uint64_t numVertices, const uint32_t *outCount, const uint32_t *inCount,
                                                   const uint32_t *parent, const uint32_t *length, const uint32_t *flags, uint32_t maxEdges,
                                                   Counter *sums, Counter *counters)
 {
     enum { LOOPS, FILLED, LONG, PINNED, FILLED_EDGES, IRREGULAR_EDGES, COUNTS };
-    const int slot[COUNTS] = {C_LOOPS, C_FILLED_LOOPS, C_LONG_LOOPS, C_PINNED_LOOPS, C_FILLED_EDGES, C_IRREGULAR_EDGES};
-    __shared__ uint32_t sCount[COUNTS], sLongest;
-    if (threadIdx.x < COUNTS)
-        sCount[threadIdx.x] = 0;
-    if (threadIdx.x == COUNTS)
-        sLongest = 0;
-    __syncthreads();
+    const int at[COUNTS + 1] = {C_LOOPS, C_FILLED_LOOPS, C_LONG_LOOPS, C_PINNED_LOOPS, C_FILLED_EDGES, C_IRREGULAR_EDGES, C_LONGEST_LOOP};
+    __shared__ GroupCounts<COUNTS, 1> totals;
+    totals.clear();
     const double scale = powerOfTwo(30 - exponentOfBits((uint32_t) counters[C_INPUT_MAX]));
-    const uint32_t lane = laneId();
     uint32_t count[COUNTS] = {0, 0, 0, 0, 0, 0}, longest = 0;
     for (uint64_t base = (uint64_t) blockIdx.x * blockDim.x; base < numVertices; base += (uint64_t) gridDim.x * blockDim.x)
     {
@@ -337,38 +223,21 @@ __global__ __launch_bounds__(256) void sumsKernel(const float *vertices, uint64_
 #pragma unroll
             for (int k = 0; k < 3; k++)
                 q[k] = quantise(vertices[3 * v + k], scale);
-        uint64_t pending = __ballot(adds);
-        while (pending != 0)
-        {
-            const uint32_t leader = (uint32_t) __ffsll((unsigned long long) pending) - 1;
-            const uint32_t r = (uint32_t) __shfl((int) root, (int) leader, WAVE);
-            const bool same = adds && root == r;
-            long long s[3];
+        forEachRoot(adds, root, [&](uint32_t r, bool same, uint64_t, bool leads) {
 #pragma unroll
             for (int k = 0; k < 3; k++)
-                s[k] = waveSum64(same ? q[k] : 0);
-            if (lane == leader)
-#pragma unroll
-                for (int k = 0; k < 3; k++)
-                    atomicAdd(&sums[3 * (uint64_t) r + k], (Counter) s[k]);
-            pending &= ~__ballot(same);
-        }
+            {
+                const long long s = waveSum64(same ? q[k] : 0);
+                if (leads)
+                    atomicAdd(&sums[3 * (uint64_t) r + k], (Counter) s);
+            }
+        });
     }
 #pragma unroll
     for (int k = 0; k < COUNTS; k++)
-    {
-        const uint32_t ofWave = waveSum(count[k]);
-        if (lane == 0 && ofWave != 0)
-            atomicAdd(&sCount[k], ofWave);
-    }
-    const uint32_t longestOfWave = waveMax(longest);
-    if (lane == 0)
-        atomicMax(&sLongest, longestOfWave);
-    __syncthreads();
-    if (threadIdx.x < COUNTS && sCount[threadIdx.x] != 0)
-        atomicAdd(&counters[slot[threadIdx.x]], (Counter) sCount[threadIdx.x]);
-    if (threadIdx.x == COUNTS && sLongest != 0)
-        atomicMax(&counters[C_LONGEST_LOOP], (Counter) sLongest);
+        totals.add(k, count[k]);
+    totals.raise(0, longest);
+    totals.flush(counters, at);
 }
 
 /* Step 8: the flag stands at the root -- the smallest vertex -- of every filled loop.  (length is non-zero at roots only.) */
@@ -425,17 +294,6 @@ struct NewTriangleOut
         outTriangles[3 * (uint64_t) before + 2] = firstNew + loopOf[parent[v]];
     }
 };
-
-uint32_t bitLength(uint64_t v)
-{
-    uint32_t b = 0;
-    while (v != 0)
-    {
-        b++;
-        v >>= 1;
-    }
-    return b;
-}
 
 /* ---- the seams of a sink's chunks (mlsgpu::seamMask) ---- */
 
@@ -577,11 +435,11 @@ MLSGPU_API int mlsgpu_hip_mesh_fill_holes(mlsgpu_ctx *ctx, const float *dVertice
 
     HIP_CHECK(hipSetDevice(ctx->device));
     const uint64_t nv = numVertices, nt = numTriangles, n = 3 * nt;
-    const uint32_t b = bitLength(nv);           /* V itself fits: the key of the records that take no part */
+    const SideKeys K = SideKeys::of(nv);
     const dim3 B(256);
     DeviceArray<Counter> counters, sums;
-    DeviceArray<uint32_t> parent, outCount, inCount, next, length, flags, loopOf, valsA, valsB, hist, tileSums;
-    DeviceArray<uint64_t> keysA, keysB;
+    DeviceArray<uint32_t> parent, outCount, inCount, next, length, flags, loopOf, tileSums;
+    SortScratch records;
     Counter h[C_WORDS];
     std::memset(h, 0, sizeof(h));
     const bool sides = nv > 0 && nt > 0;        /* without vertices every triangle is out of range */
@@ -601,12 +459,8 @@ MLSGPU_API int mlsgpu_hip_mesh_fill_holes(mlsgpu_ctx *ctx, const float *dVertice
         double scratch = (double) (counters.bytes(C_WORDS) + sums.bytes(3 * nv) + 7 * parent.bytes(nv) + tileSums.bytes(tileElems));
         if (sides)
         {
-            PROPAGATE(keysA.alloc(n));
-            PROPAGATE(keysB.alloc(n));
-            PROPAGATE(valsA.alloc(n));
-            PROPAGATE(valsB.alloc(n));
-            PROPAGATE(hist.alloc(sortHistElems(n)));
-            scratch += (double) (2 * keysA.bytes(n) + 2 * valsA.bytes(n) + hist.bytes(sortHistElems(n)));
+            PROPAGATE(records.alloc(n));
+            scratch += (double) records.bytes();
         }
         if (ctx->timing)
             ctx->addValue("fill.scratch.bytes", scratch);
@@ -621,10 +475,9 @@ MLSGPU_API int mlsgpu_hip_mesh_fill_holes(mlsgpu_ctx *ctx, const float *dVertice
         if (sides)
         {
             LAUNCH(ctx, "kernel.fill.init", identityKernel, dim3(divUp(nv, 256)), B, parent.get(), nv);
-            LAUNCH(ctx, "kernel.fill.classify", classifyKernel, dim3(divUp(nt, 256)), B, dTriangles, nt, nv, b, keysA.get(), counters.get());
-            SortResult<uint64_t> sorted = {nullptr, nullptr};
-            PROPAGATE(radixSort<uint64_t>(ctx, "kernel.fill.sort", keysA, valsA, keysB, valsB, n, 2 * b, true, hist, nullptr, &sorted));
-            const Records R = {sorted.keys, n, nv, b};
+            LAUNCH(ctx, "kernel.fill.classify", classifyKernel, dim3(divUp(nt, 256)), B, dTriangles, nt, K, records.keys(), counters.get());
+            Records R;
+            PROPAGATE(records.sort(ctx, "kernel.fill.sort", K, true, &R));
             LAUNCH(ctx, "kernel.fill.sides", sidesKernel, dim3(std::min(divUp(n, 256), SIDES_BLOCKS)), B, R, outCount.get(), inCount.get(), next.get(), parent.get(),
                    counters.get());
             LAUNCH(ctx, "kernel.fill.loops", loopsKernel, dim3(divUp(nv, 256)), B, nv, (const uint32_t *) outCount.get(),

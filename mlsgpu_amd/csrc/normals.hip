@@ -14,7 +14,7 @@
  *
  * Scratch belongs to the call: 24 bytes per vertex (the sums) and four 64-bit words.
  */
-#include "common.hpp"
+#include "meshpost.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -24,26 +24,16 @@ using namespace mlsgpu;
 namespace
 {
 
-typedef unsigned long long Counter;
-
 enum
 {
     C_OUT_OF_RANGE = 0,
     C_NON_FINITE = 1,
     C_ZERO_NORMALS = 2,
-    C_MAX_BITS = 3,             /* the bits of the largest |component|: non-negative doubles order as their bits */
+    C_MAX_BITS = 3,             /* the bits of the largest |component|, a double */
     C_WORDS = 4
 };
 
 const uint32_t NO_VERTEX = 0xFFFFFFFFu;     /* what a lane that adds nothing holds: an index that takes part is < V <= 2^32 - 1 */
-
-/* The lanes of the wave for which `hit` holds add their number to *count with one atomic. */
-__device__ __forceinline__ void tally(bool hit, Counter *count)
-{
-    const uint64_t mask = __ballot(hit);
-    if (hit && popcBelow(mask) == 0)
-        atomicAdd(count, (Counter) __popcll(mask));
-}
 
 struct Face
 {
@@ -89,7 +79,7 @@ __device__ __forceinline__ Face faceOf(const float *vertices, uint64_t numVertic
     return f;
 }
 
-/* Every lane of every wave stays to the end: waveMax needs the full wave. */
+/* Every lane of every wave stays to the end: waveMax64 needs the full wave. */
 __global__ __launch_bounds__(256) void extentKernel(const float *vertices, uint64_t numVertices, const uint32_t *triangles,
                                                     uint64_t numTriangles, Counter *counters)
 {
@@ -103,27 +93,12 @@ __global__ __launch_bounds__(256) void extentKernel(const float *vertices, uint6
     tally(f.outOfRange, &counters[C_OUT_OF_RANGE]);
     tally(f.nonFinite, &counters[C_NON_FINITE]);
     const uint64_t bits = (uint64_t) __double_as_longlong(fmax(fmax(fabs(f.c[0]), fabs(f.c[1])), fabs(f.c[2])));
-    /* the largest 64-bit pattern of the wave: the largest high word, then the largest low word among its holders */
-    const uint32_t hi = waveMax((uint32_t) (bits >> 32));
-    const uint32_t lo = waveMax((uint32_t) (bits >> 32) == hi ? (uint32_t) bits : 0u);
-    const uint64_t most = (uint64_t) hi << 32 | lo;
+    const uint64_t most = waveMax64(bits);
     if (laneId() == 0 && most != 0)
         atomicMax(&counters[C_MAX_BITS], (Counter) most);
 }
 
-/* step 3: the e with 2^e <= M < 2^(e + 1) from the bits of M > 0 (a subnormal has its true exponent) */
-__host__ __device__ __forceinline__ int exponentOf(uint64_t bits)
-{
-    const int field = (int) (bits >> 52);
-    if (field != 0)
-        return field - 1023;
-    int top = 0;
-    for (uint64_t m = bits; m > 1; m >>= 1)
-        top++;
-    return top - 1074;
-}
-
-/* q = llrint(ldexp(component, shift)): ldexp is exact wherever the result is normal, and a result that is not is far below
+/* step 3 is meshpost.hpp's exponentOfDoubleBits of the largest component; q = llrint(ldexp(component, shift)): ldexp is exact wherever the result is normal, and a result that is not is far below
  * 1/2; rint rounds ties to even */
 __device__ __forceinline__ void quantise(const double c[3], int shift, long long q[3])
 {
@@ -144,7 +119,7 @@ __global__ __launch_bounds__(256) void accumulatePlainKernel(const float *vertic
     if (!f.takesPart())
         return;
     long long q[3];
-    quantise(f.c, 30 - exponentOf(maxBits), q);
+    quantise(f.c, 30 - exponentOfDoubleBits(maxBits), q);
 #pragma unroll
     for (int corner = 0; corner < 3; corner++)
 #pragma unroll
@@ -173,7 +148,7 @@ __global__ __launch_bounds__(256) void accumulateWaveKernel(const float *vertice
     const bool adds = f.takesPart();
     long long q[3] = {0, 0, 0};
     if (adds)
-        quantise(f.c, 30 - exponentOf(maxBits), q);
+        quantise(f.c, 30 - exponentOfDoubleBits(maxBits), q);
     const uint32_t lane = laneId();
 #pragma unroll
     for (int corner = 0; corner < 3; corner++)
@@ -281,6 +256,6 @@ MLSGPU_API int mlsgpu_hip_mesh_normals(mlsgpu_ctx *ctx, const float *dVertices, 
     stats->outOfRangeTriangles = hCounters[C_OUT_OF_RANGE];
     stats->nonFiniteTriangles = hCounters[C_NON_FINITE];
     stats->zeroNormals = hCounters[C_ZERO_NORMALS];
-    stats->scaleExponent = hCounters[C_MAX_BITS] != 0 ? exponentOf(hCounters[C_MAX_BITS]) : 0;
+    stats->scaleExponent = hCounters[C_MAX_BITS] != 0 ? exponentOfDoubleBits(hCounters[C_MAX_BITS]) : 0;
     return MLSGPU_OK;
 }

@@ -24,8 +24,7 @@
  * used / new index 4) and 44 bytes per triangle (cluster triple 12, the two sides of the 32-bit sort 16 and of the 64-bit
  * sort's keys 16), the sort's histogram (4 KB per 4096 elements of the larger of the two) and the scans' tile sums.
  */
-#include "common.hpp"
-#include "primitives.hpp"
+#include "meshpost.hpp"
 
 #include <cmath>
 
@@ -33,8 +32,6 @@ using namespace mlsgpu;
 
 namespace
 {
-
-typedef unsigned long long Counter;
 
 /* 64-bit counters, read back twice */
 enum
@@ -80,14 +77,6 @@ struct KeyBits
         c[2] = (uint32_t) (key >> (x + y));
     }
 };
-
-/* The lanes of the wave for which `hit` holds add their number to *count with one atomic. */
-__device__ __forceinline__ void tally(bool hit, Counter *count)
-{
-    const uint64_t mask = __ballot(hit);
-    if (hit && popcBelow(mask) == 0)
-        atomicAdd(count, (Counter) __popcll(mask));
-}
 
 /* step 1 of the contract: c = floorf((p - origin) / cellSize) per axis, two correctly rounded f32 operations; false for a
  * non-finite coordinate or a cell outside [0, 2^21) */
@@ -219,10 +208,7 @@ __global__ __launch_bounds__(256) void sumsKernel(const float *vertices, const u
 #pragma unroll
         for (int k = 0; k < 3; k++)
         {
-            long long s = q[k];         /* zero in the lanes that do not add */
-#pragma unroll
-            for (int step = 32; step >= 1; step >>= 1)
-                s += __shfl_down(s, step, 64);
+            const long long s = waveSum64(q[k]);        /* zero in the lanes that do not add */
             if (laneId() == 0)
                 atomicAdd(&sums[3 * (uint64_t) firstCluster + k], (Counter) s);
         }
@@ -392,17 +378,6 @@ __global__ __launch_bounds__(256) void reindexKernel(uint32_t *outTriangles, con
     if (i >= 3 * (uint64_t) *numOutTriangles)
         return;
     outTriangles[i] = newIndex[outTriangles[i]];
-}
-
-uint32_t bitLength(uint64_t v)
-{
-    uint32_t b = 0;
-    while (v != 0)
-    {
-        b++;
-        v >>= 1;
-    }
-    return b;
 }
 
 } // namespace

@@ -21,8 +21,7 @@
  * neighbour lists lie in the key side the sort leaves free), 41 bytes per vertex (two working arrays 32, neighbour run 8,
  * boundary flag 1), the sort's histogram (4 KB per 4096 records) and the scan's tile sums.
  */
-#include "common.hpp"
-#include "primitives.hpp"
+#include "meshpost.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -31,8 +30,6 @@ using namespace mlsgpu;
 
 namespace
 {
-
-typedef unsigned long long Counter;
 
 enum
 {
@@ -43,40 +40,15 @@ enum
     C_USED_VERTICES = 4,        /* vertices with a segment: the others are isolated */
     C_BOUNDARY_VERTICES = 5,
     C_NON_FINITE = 6,           /* input coordinates */
-    C_INPUT_MAX = 7,            /* the bits of the largest |coordinate| of the input: non-negative floats order as their bits, */
-    C_PASS_MAX = 8,             /* ... of the passes' outputs                                        and a NaN above infinity */
+    C_INPUT_MAX = 7,            /* the bits of the largest |coordinate| of the input */
+    C_PASS_MAX = 8,             /* ... of the passes' outputs */
     C_MAX_MOVE = 9,             /* the bits of the largest move, a double */
     C_WORDS = 10
 };
 
-const double CLAMP = 4611686018427387904.0;     /* 2^62: what a value is clamped to before it becomes an integer */
-
-/* The lanes of the wave for which `hit` holds add their number to *count with one atomic. */
-__device__ __forceinline__ void tally(bool hit, Counter *count)
-{
-    const uint64_t mask = __ballot(hit);
-    if (hit && popcBelow(mask) == 0)
-        atomicAdd(count, (Counter) __popcll(mask));
-}
-
 __device__ __forceinline__ uint32_t absBits(float x) { return __float_as_uint(fabsf(x)); }
 
-/* What a launch may use of the device for a kernel whose workgroups loop over the elements: a count or a maximum that every
- * wave of a thread-per-element grid sends to ONE address costs about 10 ns apiece there (the atomics of one address are
- * served one after the other), 10 ms for the 22 M records of a 4 M-triangle chunk; these workgroups add up in registers and
- * LDS and send one atomic each. */
-const uint32_t LOOP_BLOCKS = 1024;
-
-/* the largest of the wave's bit patterns into *word; needs the full wave.  The word is read first: a maximum is reached by
- * the first few waves, and the others then have nothing to send (a stale read costs an atomic, never the result). */
-__device__ __forceinline__ void foldMax(uint32_t bits, Counter *word)
-{
-    const uint32_t most = waveMax(bits);
-    if (laneId() == 0 && (Counter) most > __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-        atomicMax(word, (Counter) most);
-}
-
-/* Every lane of every wave stays to the end: waveMax needs the full wave. */
+/* Every lane of every wave stays to the end: foldMax needs the full wave. */
 __global__ __launch_bounds__(256) void loadKernel(const float *vertices, uint64_t numVertices, float4 *work, Counter *counters)
 {
     const uint64_t v = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -93,57 +65,36 @@ __global__ __launch_bounds__(256) void loadKernel(const float *vertices, uint64_
     foldMax(max(max(absBits(p.x), absBits(p.y)), absBits(p.z)), &counters[C_INPUT_MAX]);
 }
 
-/* steps 1 and 2 of the contract.  The six records of a triangle that takes no part get from = V: they sort behind every
- * other record and nothing follows them. */
-__global__ __launch_bounds__(256) void recordsKernel(const uint32_t *tri, uint64_t numTriangles, uint64_t numVertices, uint32_t b,
-                                                     uint64_t *keys, Counter *counters)
+/* steps 1 and 2 of the contract: both directions of a triangle's three sides; six dead records for one that takes no part */
+__global__ __launch_bounds__(256) void recordsKernel(const uint32_t *tri, uint64_t numTriangles, SideKeys K, uint64_t *keys,
+                                                     Counter *counters)
 {
     const uint64_t t = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= numTriangles)
         return;
     const uint64_t i[3] = {tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]};
-    const bool outOfRange = i[0] >= numVertices || i[1] >= numVertices || i[2] >= numVertices;
-    const bool degenerate = !outOfRange && (i[0] == i[1] || i[1] == i[2] || i[2] == i[0]);
-    tally(outOfRange, &counters[C_OUT_OF_RANGE]);
-    tally(degenerate, &counters[C_DEGENERATE]);
+    const TriangleDefect d = defectOf(i, K.numVertices);
+    tally(d.outOfRange, &counters[C_OUT_OF_RANGE]);
+    tally(d.degenerate, &counters[C_DEGENERATE]);
 #pragma unroll
     for (int k = 0; k < 3; k++)
     {
         const uint64_t from = i[k], to = i[k == 2 ? 0 : k + 1];
-        const bool part = !outOfRange && !degenerate;
-        keys[6 * t + 2 * k] = part ? (from << b) | to : numVertices << b;
-        keys[6 * t + 2 * k + 1] = part ? (to << b) | from : numVertices << b;
+        keys[6 * t + 2 * k] = d.none() ? K.keyOf(from, to) : K.dead();
+        keys[6 * t + 2 * k + 1] = d.none() ? K.keyOf(to, from) : K.dead();
     }
 }
 
-/* the sorted records */
-struct Records
-{
-    const uint64_t *keys;
-    uint64_t n;
-    uint64_t numVertices;
-    uint32_t b;
-
-    __device__ __forceinline__ uint64_t fromOf(uint64_t key) const { return key >> b; }
-    __device__ __forceinline__ uint32_t toOf(uint64_t key) const { return (uint32_t) (key & ((uint64_t(1) << b) - 1)); }
-    __device__ __forceinline__ bool head(uint64_t i, uint64_t key) const { return i == 0 || keys[i - 1] != key; }
-    /* the only record of its run: exactly one triangle side uses the edge */
-    __device__ __forceinline__ bool single(uint64_t i, uint64_t key) const
-    {
-        return head(i, key) && (i + 1 == n || keys[i + 1] != key);
-    }
-};
-
-/* step 2.  Both directions of every side are there, so each end of a boundary edge is marked by the record that leaves it; an
- * edge is counted by the direction that rises.  The plain byte stores race only with stores of the same value.  A workgroup
- * loops over the records (at most 2^32 / LOOP_BLOCKS of them: its counts fit 32 bits) and sends its three counts once. */
+/* step 2.  Both directions of every side are there, so a run of one is an edge that exactly one triangle side uses, and each
+ * end of such a boundary edge is marked by the record that leaves it; an edge is counted by the direction that rises.  The
+ * plain byte stores race only with stores of the same value.  A workgroup loops over the records (at most 2^32 / LOOP_BLOCKS
+ * of them: its counts fit 32 bits) and sends its three counts once. */
 __global__ __launch_bounds__(256) void markKernel(Records R, uint8_t *onBoundary, Counter *counters)
 {
-    __shared__ uint32_t sums[3];
-    if (threadIdx.x < 3)
-        sums[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t count[3] = {0, 0, 0};      /* edges, boundary edges, vertices with a segment: C_EDGES onwards */
+    __shared__ GroupCounts<3> sums;
+    sums.clear();
+    const int at[3] = {C_EDGES, C_BOUNDARY_EDGES, C_USED_VERTICES};
+    uint32_t count[3] = {0, 0, 0};
     for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < R.n; i += (uint64_t) gridDim.x * blockDim.x)
     {
         const uint64_t key = R.keys[i], from = R.fromOf(key);
@@ -155,18 +106,12 @@ __global__ __launch_bounds__(256) void markKernel(Records R, uint8_t *onBoundary
             onBoundary[from] = 1;
         count[0] += rises && R.head(i, key) ? 1u : 0u;
         count[1] += rises && single ? 1u : 0u;
-        count[2] += i == 0 || R.fromOf(R.keys[i - 1]) != from ? 1u : 0u;
+        count[2] += R.segmentStart(i, from) ? 1u : 0u;
     }
 #pragma unroll
     for (int k = 0; k < 3; k++)
-    {
-        const uint32_t ofWave = waveSum(count[k]);
-        if (laneId() == 0 && ofWave != 0)
-            atomicAdd(&sums[k], ofWave);
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 && sums[threadIdx.x] != 0)
-        atomicAdd(&counters[C_EDGES + threadIdx.x], (Counter) sums[threadIdx.x]);
+        sums.add(k, count[k]);
+    sums.flush(counters, at);
 }
 
 /* step 3: the heads of the runs that stay in the neighbour lists */
@@ -199,22 +144,15 @@ struct ListOut
             return;
         if (kept)
             neighbours[before] = R.toOf(key);
-        if (i == 0 || R.fromOf(R.keys[i - 1]) != from)
+        if (R.segmentStart(i, from))
             run[from].x = before;
-        if (i + 1 == R.n || R.fromOf(R.keys[i + 1]) != from)
+        if (R.segmentEnd(i, from))
             run[from].y = before + kept;
     }
 };
 
-/* Q of step 5: the multiplication by a power of two is ldexp (exact: a float times 2^(30 - e) is a normal double or zero);
- * rint rounds ties to even.  The clamp changes no value of a call that has not diverged (those are below 2^52) and makes the
- * conversion of every other one defined: fmax / fmin hand back the bound for a NaN. */
-__device__ __forceinline__ unsigned long long quantise(float x, double scale)
-{
-    return (unsigned long long) (long long) rint(fmin(fmax((double) x * scale, -CLAMP), CLAMP));
-}
-
-/* Step 5.  One aligned 16-byte load per neighbour; the sums are unsigned, so that they wrap.  Every lane stays to the end.
+/* Step 5, with meshpost.hpp's quantise as Q (a call that has not diverged stays below 2^52; one that has meets the clamp).
+ * One aligned 16-byte load per neighbour; the sums are unsigned, so that they wrap.  Every lane stays to the end.
  * BATCHED: four neighbours a round, their four index loads issued together and then their four rows, so that a list costs a
  * quarter of the dependent round trips (a slot past the end reads the list's last entry again and adds nothing); otherwise
  * one neighbour after the other.  The sums are integers: the same bits either way. */
@@ -251,25 +189,25 @@ __global__ __launch_bounds__(256) void passKernel(const float4 *in, float4 *out,
 #pragma unroll
                     for (int i = 0; i < 4; i++)
                     {
-                        S[0] += has[i] ? quantise(q[i].x, scale) : 0ull;
-                        S[1] += has[i] ? quantise(q[i].y, scale) : 0ull;
-                        S[2] += has[i] ? quantise(q[i].z, scale) : 0ull;
+                        S[0] += has[i] ? (unsigned long long) quantise(q[i].x, scale) : 0ull;
+                        S[1] += has[i] ? (unsigned long long) quantise(q[i].y, scale) : 0ull;
+                        S[2] += has[i] ? (unsigned long long) quantise(q[i].z, scale) : 0ull;
                     }
                 }
             else
                 for (uint32_t j = r.x; j < r.y; j++)
                 {
                     const float4 q = in[neighbours[j]];
-                    S[0] += quantise(q.x, scale);
-                    S[1] += quantise(q.y, scale);
-                    S[2] += quantise(q.z, scale);
+                    S[0] += (unsigned long long) quantise(q.x, scale);
+                    S[1] += (unsigned long long) quantise(q.y, scale);
+                    S[2] += (unsigned long long) quantise(q.z, scale);
                 }
             const float own[3] = {p.x, p.y, p.z};
             float moved[3];
 #pragma unroll
             for (int a = 0; a < 3; a++)
             {
-                const long long D = (long long) (S[a] - (unsigned long long) k * quantise(own[a], scale));
+                const long long D = (long long) (S[a] - (unsigned long long) k * (unsigned long long) quantise(own[a], scale));
                 const double d = ((double) D / (double) k) * invScale;
                 moved[a] = (float) ((double) own[a] + F * d);
             }
@@ -285,16 +223,14 @@ __global__ __launch_bounds__(256) void passKernel(const float4 *in, float4 *out,
 __global__ __launch_bounds__(256) void finishKernel(const float *vertices, const float4 *work, const uint8_t *onBoundary,
                                                     uint64_t numVertices, float *outVertices, Counter *counters)
 {
-    __shared__ uint32_t sBoundary;
+    __shared__ GroupCounts<1> sBoundary;
     __shared__ Counter sMove;
     if (threadIdx.x == 0)
-    {
-        sBoundary = 0;
         sMove = 0;
-    }
-    __syncthreads();
+    sBoundary.clear();
+    const int at[1] = {C_BOUNDARY_VERTICES};
     uint32_t boundary = 0;
-    uint64_t bits = 0;          /* of the largest move: non-negative doubles order as their bits, and a NaN above infinity */
+    uint64_t bits = 0;          /* of the largest move, a double */
     for (uint64_t v = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; v < numVertices; v += (uint64_t) gridDim.x * blockDim.x)
     {
         const float was[3] = {vertices[3 * v], vertices[3 * v + 1], vertices[3 * v + 2]};
@@ -308,35 +244,13 @@ __global__ __launch_bounds__(256) void finishKernel(const float *vertices, const
         }
         boundary += onBoundary[v] != 0 ? 1u : 0u;
     }
-    const uint32_t ofWave = waveSum(boundary);
-    /* the largest 64-bit pattern of the wave: the largest high word, then the largest low word among its holders */
-    const uint32_t hi = waveMax((uint32_t) (bits >> 32));
-    const uint32_t lo = waveMax((uint32_t) (bits >> 32) == hi ? (uint32_t) bits : 0u);
+    sBoundary.add(0, boundary);
+    const uint64_t most = waveMax64(bits);
     if (laneId() == 0)
-    {
-        if (ofWave != 0)
-            atomicAdd(&sBoundary, ofWave);
-        atomicMax(&sMove, (Counter) ((uint64_t) hi << 32 | lo));
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        if (sBoundary != 0)
-            atomicAdd(&counters[C_BOUNDARY_VERTICES], (Counter) sBoundary);
-        if (sMove != 0)
-            atomicMax(&counters[C_MAX_MOVE], sMove);
-    }
-}
-
-uint32_t bitLength(uint64_t v)
-{
-    uint32_t b = 0;
-    while (v != 0)
-    {
-        b++;
-        v >>= 1;
-    }
-    return b;
+        atomicMax(&sMove, (Counter) most);
+    sBoundary.flush(counters, at);      /* (a barrier: sMove is complete behind it) */
+    if (threadIdx.x == 0 && sMove != 0)
+        atomicMax(&counters[C_MAX_MOVE], sMove);
 }
 
 /* MLSGPU_HIP_SMOOTH_PASS=serial|batched picks the pass kernel (same bits either way) */
@@ -380,15 +294,15 @@ MLSGPU_API int mlsgpu_hip_mesh_smooth(mlsgpu_ctx *ctx, const float *dVertices, u
 
     HIP_CHECK(hipSetDevice(ctx->device));
     const uint64_t nv = numVertices, nt = numTriangles, n = 6 * nt;
-    const uint32_t b = bitLength(nv);           /* V itself fits: the key of the records that take no part */
+    const SideKeys K = SideKeys::of(nv);
     const dim3 B(256);
     DeviceArray<Counter> counters;
     DeviceArray<float4> workA, workB;
     DeviceArray<uint2> run;
     DeviceArray<uint8_t> onBoundary;
-    DeviceArray<uint64_t> keysA, keysB;
-    DeviceArray<uint32_t> valsA, valsB, hist, tileSums;
-    const uint64_t histElems = sortHistElems(n), tileElems = (uint64_t) scanTiles(n) + 1;
+    SortScratch sides;
+    DeviceArray<uint32_t> tileSums;
+    const uint64_t tileElems = (uint64_t) scanTiles(n) + 1;
     PROPAGATE(counters.alloc(C_WORDS));
     PROPAGATE(workA.alloc(nv));
     PROPAGATE(workB.alloc(nv));
@@ -397,13 +311,9 @@ MLSGPU_API int mlsgpu_hip_mesh_smooth(mlsgpu_ctx *ctx, const float *dVertices, u
     double scratch = (double) (counters.bytes(C_WORDS) + 2 * workA.bytes(nv) + run.bytes(nv) + onBoundary.bytes(nv));
     if (nt > 0)
     {
-        PROPAGATE(keysA.alloc(n));
-        PROPAGATE(keysB.alloc(n));
-        PROPAGATE(valsA.alloc(n));
-        PROPAGATE(valsB.alloc(n));
-        PROPAGATE(hist.alloc(histElems));
+        PROPAGATE(sides.alloc(n));
         PROPAGATE(tileSums.alloc(tileElems));
-        scratch += (double) (2 * keysA.bytes(n) + 2 * valsA.bytes(n) + hist.bytes(histElems) + tileSums.bytes(tileElems));
+        scratch += (double) (sides.bytes() + tileSums.bytes(tileElems));
     }
     if (ctx->timing)
         ctx->addValue("smooth.scratch.bytes", scratch);
@@ -415,13 +325,12 @@ MLSGPU_API int mlsgpu_hip_mesh_smooth(mlsgpu_ctx *ctx, const float *dVertices, u
     const uint32_t *neighbours = nullptr;
     if (nt > 0)
     {
-        LAUNCH(ctx, "kernel.smooth.records", recordsKernel, dim3(divUp(nt, 256)), B, dTriangles, nt, nv, b, keysA.get(), counters.get());
-        SortResult<uint64_t> sorted = {nullptr, nullptr};
-        PROPAGATE(radixSort<uint64_t>(ctx, "kernel.smooth.sort", keysA, valsA, keysB, valsB, n, 2 * b, true, hist, nullptr, &sorted));
-        /* the key side that does not hold the result is free again: the neighbour lists, at most one word per record */
-        uint32_t *const lists = reinterpret_cast<uint32_t *>(sorted.keys == keysA.get() ? keysB.get() : keysA.get());
+        LAUNCH(ctx, "kernel.smooth.records", recordsKernel, dim3(divUp(nt, 256)), B, dTriangles, nt, K, sides.keys(), counters.get());
+        Records R;
+        PROPAGATE(sides.sort(ctx, "kernel.smooth.sort", K, true, &R));
+        /* the neighbour lists, at most one word per record, in the key side that is free again */
+        uint32_t *const lists = reinterpret_cast<uint32_t *>(sides.freeKeys());
         neighbours = lists;
-        const Records R = {sorted.keys, n, nv, b};
         LAUNCH(ctx, "kernel.smooth.mark", markKernel, dim3(std::min(divUp(n, 256), LOOP_BLOCKS)), B, R, onBoundary.get(), counters.get());
         PROPAGATE((exclusiveScan<uint32_t>(ctx, "kernel.smooth.adjacency",
                                            KeepIn{R, onBoundary.get(), boundary == MLSGPU_SMOOTH_BOUNDARY_CURVE},
@@ -435,9 +344,7 @@ MLSGPU_API int mlsgpu_hip_mesh_smooth(mlsgpu_ctx *ctx, const float *dVertices, u
 
     /* step 4 */
     const float M = floatOfBits(h[C_INPUT_MAX]);
-    int e = 0;
-    if (M > 0.0f)
-        e = std::ilogb(M);              /* 2^e <= M < 2^(e + 1), a subnormal's true exponent */
+    const int e = exponentOfBits((uint32_t) h[C_INPUT_MAX]);
     float4 *from = workA.get(), *to = workB.get();
     if (M > 0.0f && nt > 0)
     {

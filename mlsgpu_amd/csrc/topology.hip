@@ -17,8 +17,7 @@
  * An index >= V is compared, counted and reported, never used as an address: the triangles of a record that reaches the
  * kernels behind classify have all three indices below V.
  */
-#include "common.hpp"
-#include "primitives.hpp"
+#include "meshpost.hpp"
 #include "unionfind.hpp"
 
 using namespace mlsgpu;
@@ -40,23 +39,6 @@ enum
 };
 
 const uint32_t NO_SEGMENT = 0xFFFFFFFFu;    /* 3 T < 2^32 - 1: never a record's index */
-/* findRootHalving's threshold: the meshes are surfaces (mesher.hip measured 3 as the best for them) */
-const uint32_t UNION_SHORTCUT = 3;
-
-typedef unsigned long long Counter;
-
-/* The lanes of the wave for which `hit` holds add their number to *count with ONE atomic (the ballot's lowest lane issues
- * it); that lane also holds the lowest `index` among them -- indices rise with the lane -- and lowers *first to it. */
-__device__ __forceinline__ void tally(bool hit, uint64_t index, Counter *count, Counter *first)
-{
-    const uint64_t mask = __ballot(hit);
-    if (hit && popcBelow(mask) == 0)
-    {
-        atomicAdd(count, (Counter) __popcll(mask));
-        if (first != nullptr)
-            atomicMin(first, (Counter) index);
-    }
-}
 
 __global__ __launch_bounds__(256) void initKernel(uint64_t numVertices, uint32_t *segStart, uint32_t *compParent, uint32_t *bndParent,
                                                   uint8_t *duplicated, uint8_t *onBoundary, Counter *counters)
@@ -74,14 +56,15 @@ __global__ __launch_bounds__(256) void initKernel(uint64_t numVertices, uint32_t
     }
 }
 
-/* a. The class of a triangle is the first check that fails in the reference's rotation order (test/manifold.h:117-132).
- *    A bad triangle's three records get from = V: they sort behind every good record and nothing looks at them again. */
-__global__ __launch_bounds__(256) void classifyKernel(const uint32_t *tri, uint64_t numTriangles, uint64_t numVertices, uint32_t b,
-                                                      uint64_t *keys, uint32_t *vals, Counter *counters)
+/* a. The class of a triangle is the first check that fails in the reference's rotation order (test/manifold.h:117-132): not
+ *    meshpost.hpp's defectOf, which looks at the range of all three indices first.  A bad triangle's three records are dead. */
+__global__ __launch_bounds__(256) void classifyKernel(const uint32_t *tri, uint64_t numTriangles, SideKeys K, uint64_t *keys,
+                                                      uint32_t *vals, Counter *counters)
 {
     const uint64_t t = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= numTriangles)
         return;
+    const uint64_t numVertices = K.numVertices;
     const uint64_t i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
     int cls = MLSGPU_TOPO_NONE;
     if (i0 >= numVertices) cls = MLSGPU_TOPO_OUT_OF_RANGE;
@@ -90,48 +73,24 @@ __global__ __launch_bounds__(256) void classifyKernel(const uint32_t *tri, uint6
     else if (i1 == i2) cls = MLSGPU_TOPO_DEGENERATE;
     else if (i2 >= numVertices) cls = MLSGPU_TOPO_OUT_OF_RANGE;
     else if (i2 == i0) cls = MLSGPU_TOPO_DEGENERATE;
-    tally(cls == MLSGPU_TOPO_OUT_OF_RANGE, t, &counters[C_COUNT + MLSGPU_TOPO_OUT_OF_RANGE], &counters[C_FIRST + MLSGPU_TOPO_OUT_OF_RANGE]);
-    tally(cls == MLSGPU_TOPO_DEGENERATE, t, &counters[C_COUNT + MLSGPU_TOPO_DEGENERATE], &counters[C_FIRST + MLSGPU_TOPO_DEGENERATE]);
+    tally(cls == MLSGPU_TOPO_OUT_OF_RANGE, &counters[C_COUNT + MLSGPU_TOPO_OUT_OF_RANGE], t, &counters[C_FIRST + MLSGPU_TOPO_OUT_OF_RANGE]);
+    tally(cls == MLSGPU_TOPO_DEGENERATE, &counters[C_COUNT + MLSGPU_TOPO_DEGENERATE], t, &counters[C_FIRST + MLSGPU_TOPO_DEGENERATE]);
     if (cls != MLSGPU_TOPO_NONE)
     {
         for (int k = 0; k < 3; k++)
         {
-            keys[3 * t + k] = numVertices << b;
+            keys[3 * t + k] = K.dead();
             vals[3 * t + k] = 0;
         }
         return;
     }
-    keys[3 * t + 0] = (i0 << b) | i1; vals[3 * t + 0] = (uint32_t) i2;
-    keys[3 * t + 1] = (i1 << b) | i2; vals[3 * t + 1] = (uint32_t) i0;
-    keys[3 * t + 2] = (i2 << b) | i0; vals[3 * t + 2] = (uint32_t) i1;
+    keys[3 * t + 0] = K.keyOf(i0, i1); vals[3 * t + 0] = (uint32_t) i2;
+    keys[3 * t + 1] = K.keyOf(i1, i2); vals[3 * t + 1] = (uint32_t) i0;
+    keys[3 * t + 2] = K.keyOf(i2, i0); vals[3 * t + 2] = (uint32_t) i1;
 }
 
-/* the sorted records and the vertices' segments in them */
-struct Records
-{
-    const uint64_t *keys;
-    const uint32_t *vals;       /* the third vertex of the record's triangle */
-    uint64_t n;
-    uint64_t numVertices;
-    uint32_t b;
-
-    __device__ __forceinline__ uint64_t fromOf(uint64_t key) const { return key >> b; }
-    __device__ __forceinline__ uint32_t toOf(uint64_t key) const { return (uint32_t) (key & ((uint64_t(1) << b) - 1)); }
-    __device__ __forceinline__ uint64_t keyOf(uint64_t from, uint64_t to) const { return (from << b) | to; }
-    /* the record with this key inside [lo, hi), or hi: at most 32 halvings, the segment is shorter than 2^32 */
-    __device__ __forceinline__ uint32_t find(uint32_t lo, uint32_t hi, uint64_t key) const
-    {
-        const uint32_t end = hi;
-        while (lo < hi)
-        {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (keys[mid] < key) lo = mid + 1; else hi = mid;
-        }
-        return lo < end && keys[lo] == key ? lo : end;
-    }
-};
-
-/* c, first half.  The plain byte stores race only with stores of the same value. */
+/* c, first half: the vertices' segments in the sorted records (R.vals: the third vertex of the record's triangle).  The plain
+ * byte stores race only with stores of the same value. */
 __global__ __launch_bounds__(256) void segmentsKernel(Records R, uint32_t *segStart, uint32_t *segEnd, uint8_t *duplicated, Counter *counters)
 {
     const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -140,17 +99,17 @@ __global__ __launch_bounds__(256) void segmentsKernel(Records R, uint32_t *segSt
     const uint64_t key = R.keys[i], from = R.fromOf(key);
     if (from >= R.numVertices)
         return;                 /* a bad triangle's record */
-    if (i == 0 || R.fromOf(R.keys[i - 1]) != from)
+    if (R.segmentStart(i, from))
         segStart[from] = (uint32_t) i;
-    if (i + 1 == R.n || R.fromOf(R.keys[i + 1]) != from)
+    if (R.segmentEnd(i, from))
         segEnd[from] = (uint32_t) (i + 1);
-    const bool repeat = i > 0 && R.keys[i - 1] == key;
+    const bool repeat = !R.head(i, key);
     if (repeat)
     {
         duplicated[from] = 1;
         duplicated[R.toOf(key)] = 1;
     }
-    tally(repeat, i, &counters[C_DUPLICATE_EDGES], nullptr);
+    tally(repeat, &counters[C_DUPLICATE_EDGES]);
 }
 
 /* c, second half: needs every segment, hence a launch of its own.  noTwin[i] = 1 if the half-edge opposite to record i is
@@ -174,9 +133,9 @@ __global__ __launch_bounds__(256) void twinsKernel(Records R, const uint32_t *se
         twin = R.find(lo, hi, R.keyOf(to, from)) != hi;
     }
     noTwin[i] = twin ? 0u : 1u;
-    const bool first = i == 0 || R.keys[i - 1] != key;
+    const bool first = R.head(i, key);
     const bool boundary = first && !twin;
-    tally(boundary, i, &counters[C_BOUNDARY_EDGES], nullptr);
+    tally(boundary, &counters[C_BOUNDARY_EDGES]);
     uint32_t *const failed = reinterpret_cast<uint32_t *>(&counters[C_FAILED]);
     if (boundary)
     {
@@ -252,7 +211,7 @@ __global__ __launch_bounds__(256) void linksKernel(Records R, const uint32_t *se
     }
 #pragma unroll
     for (int k = MLSGPU_TOPO_ISOLATED; k <= MLSGPU_TOPO_TUNNEL; k++)
-        tally(cls == k, v, &counters[C_COUNT + k], &counters[C_FIRST + k]);
+        tally(cls == k, &counters[C_COUNT + k], v, &counters[C_FIRST + k]);
 }
 
 /* e. Only for a mesh without defects (the counters of the kernels before are complete: a launch lies between).
@@ -270,19 +229,8 @@ __global__ __launch_bounds__(256) void rootsKernel(uint64_t numVertices, const u
         defects |= counters[C_COUNT + k];
     if (defects != 0 || v >= numVertices)
         return;
-    tally(compParent[v] == (uint32_t) v, v, &counters[C_COMPONENTS], nullptr);
-    tally(onBoundary[v] != 0 && bndParent[v] == (uint32_t) v, v, &counters[C_BOUNDARIES], nullptr);
-}
-
-uint32_t bitLength(uint64_t v)
-{
-    uint32_t b = 0;
-    while (v != 0)
-    {
-        b++;
-        v >>= 1;
-    }
-    return b;
+    tally(compParent[v] == (uint32_t) v, &counters[C_COMPONENTS]);
+    tally(onBoundary[v] != 0 && bndParent[v] == (uint32_t) v, &counters[C_BOUNDARIES]);
 }
 
 /* the verdict and what follows from the counts */
@@ -338,16 +286,12 @@ MLSGPU_API int mlsgpu_hip_mesh_topology(mlsgpu_ctx *ctx, const uint32_t *dTriang
 
     HIP_CHECK(hipSetDevice(ctx->device));
     const uint64_t n = 3 * numTriangles, nv = numVertices;
-    const uint32_t b = bitLength(numVertices);          /* V itself fits: the key of a bad triangle's records */
-    DeviceArray<uint64_t> keysA, keysB;
-    DeviceArray<uint32_t> valsA, valsB, hist, segStart, segEnd, compParent, bndParent;
+    const SideKeys K = SideKeys::of(nv);
+    SortScratch sides;
+    DeviceArray<uint32_t> segStart, segEnd, compParent, bndParent;
     DeviceArray<uint8_t> duplicated, onBoundary;
     DeviceArray<Counter> counters;
-    PROPAGATE(keysA.alloc(n));
-    PROPAGATE(keysB.alloc(n));
-    PROPAGATE(valsA.alloc(n));
-    PROPAGATE(valsB.alloc(n));
-    PROPAGATE(hist.alloc(sortHistElems(n)));
+    PROPAGATE(sides.alloc(n));
     PROPAGATE(segStart.alloc(nv));
     PROPAGATE(segEnd.alloc(nv));
     PROPAGATE(compParent.alloc(nv));
@@ -357,19 +301,16 @@ MLSGPU_API int mlsgpu_hip_mesh_topology(mlsgpu_ctx *ctx, const uint32_t *dTriang
     PROPAGATE(counters.alloc(C_WORDS));
     if (ctx->timing)
         ctx->addValue("topology.scratch.bytes",
-                      (double) (2 * keysA.bytes(n) + 2 * valsA.bytes(n) + hist.bytes(sortHistElems(n)) + 4 * segStart.bytes(nv)
-                                + 2 * duplicated.bytes(nv) + counters.bytes(C_WORDS)));
+                      (double) (sides.bytes() + 4 * segStart.bytes(nv) + 2 * duplicated.bytes(nv) + counters.bytes(C_WORDS)));
 
     const dim3 B(256);
     LAUNCH(ctx, "kernel.topology.init", initKernel, dim3(divUp(std::max<uint64_t>(nv, C_WORDS), 256)), B, nv, segStart.get(),
            compParent.get(), bndParent.get(), duplicated.get(), onBoundary.get(), counters.get());
-    LAUNCH(ctx, "kernel.topology.classify", classifyKernel, dim3(divUp(numTriangles, 256)), B, dTriangles, numTriangles, nv, b,
-           keysA.get(), valsA.get(), counters.get());
-    SortResult<uint64_t> sorted = {nullptr, nullptr};
-    PROPAGATE(radixSort<uint64_t>(ctx, "kernel.topology.sort", keysA, valsA, keysB, valsB, n, 2 * b, false, hist, nullptr, &sorted));
-    /* the side of the sort that does not hold the result is free again: one word per record for the twins pass */
-    uint32_t *const noTwin = sorted.vals == valsA.get() ? valsB.get() : valsA.get();
-    const Records R = {sorted.keys, sorted.vals, n, nv, b};
+    LAUNCH(ctx, "kernel.topology.classify", classifyKernel, dim3(divUp(numTriangles, 256)), B, dTriangles, numTriangles, K,
+           sides.keys(), sides.vals(), counters.get());
+    Records R;
+    PROPAGATE(sides.sort(ctx, "kernel.topology.sort", K, false, &R));
+    uint32_t *const noTwin = sides.freeVals();          /* one word per record for the twins pass */
     if (nv > 0)
     {
         LAUNCH(ctx, "kernel.topology.segments", segmentsKernel, dim3(divUp(n, 256)), B, R, segStart.get(), segEnd.get(), duplicated.get(),

@@ -1,6 +1,6 @@
 /*
- * Lock-free union-find on the device, shared by the mesh sink's components (mesher.hip) and the topology report
- * (topology.hip): parent[] starts as the identity, unite() hooks the larger root under the smaller with a CAS, and a
+ * Lock-free union-find on the device, shared by the mesh sink's components (mesher.hip), the topology report
+ * (topology.hip) and the hole filling (fill.hip): parent[] starts as the identity, unite() hooks the larger root under the smaller with a CAS, and a
  * finished component's root is its smallest id whatever the schedule.
  */
 #ifndef MLSGPU_AMD_UNIONFIND_HPP
@@ -56,6 +56,9 @@ __device__ __forceinline__ uint32_t findRootHalving(uint32_t *parent, uint32_t v
         __hip_atomic_store(&parent[start], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return v;
 }
+
+/* the `shortcut` of a mesh that is a surface: what the stages that work on one chunk pass (topology.hip, fill.hip) */
+const uint32_t UNION_SHORTCUT = 3;
 
 /* the sets of a and b become one; *failed is set (and the call gives up) if the retry bound is ever reached */
 __device__ __forceinline__ void unite(uint32_t *parent, uint32_t a, uint32_t b, uint32_t *failed, uint32_t shortcut)

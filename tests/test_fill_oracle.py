@@ -97,6 +97,17 @@ def test_defects_take_no_part_and_stay():
     assert st3["boundaryEdges"] == 0 and st3["loops"] == 0
 
 
+def test_classification_differs_from_the_topology_report():
+    p, tri = tc.classification_trap()
+    tc.assert_trap_report(tc.count_all(len(p), tri))                # there: one out of range, two degenerate
+    _, st = sc.smooth(p, tri, 1, 0.5, -0.53)
+    assert (st["outOfRangeTriangles"], st["degenerateTriangles"]) == (2, 1)         # smoothing: (1, 1, 7) is out of range
+    v, t, st = fc.fill(p, tri, 8)
+    assert (st["outOfRangeTriangles"], st["degenerateTriangles"]) == (2, 1)         # and so it is here
+    assert (st["boundaryEdges"], st["loops"], st["filledLoops"], st["filledEdges"]) == (4, 1, 1, 4)
+    assert t[:5].tolist() == tri.tolist() and v[4].tolist() == [0.5, 0.5, 0.0]      # the bad ones stay, and take no part
+
+
 def test_figure_eight_is_irregular():
     p, tri = fc.figure_eight()
     v, t, st = fc.fill(p, tri, 2 ** 20)

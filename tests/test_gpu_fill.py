@@ -53,6 +53,14 @@ def test_hand_cases_and_empty_meshes(ctx):
     assert check(ctx, tiny, tri, 12)[2]["scaleExponent"] == 1 - 140
 
 
+def test_classification_order(ctx):
+    """The hand case that the topology report classifies differently: here an index >= V wins over a vertex twice."""
+    p, tri = tc.classification_trap()
+    v, t, st = check(ctx, p, tri, 8)
+    assert (st["outOfRangeTriangles"], st["degenerateTriangles"], st["filledLoops"], st["filledEdges"]) == (2, 1, 1, 4)
+    assert t[:5].tolist() == tri.tolist() and v[4].tolist() == [0.5, 0.5, 0.0]
+
+
 # ---------------------------------------------------------------- many workgroups
 
 HOLES = [(10, 10, 1, 1), (50, 60, 2, 3), (100, 200, 8, 8), (200, 100, 1, 1), (201, 101, 1, 1)]

@@ -56,6 +56,15 @@ def test_hand_cases_and_empty_meshes(ctx):
     assert check(ctx, zeros, tri, 2, boundary=sc.CURVE)[0].tobytes() == zeros.tobytes()     # M = 0: the input's bits
 
 
+def test_classification_order(ctx):
+    """The hand case that the topology report classifies differently: here an index >= V wins over a vertex twice."""
+    import topology_cases as tc
+    p, tri = tc.classification_trap()
+    for mode in (sc.FIXED, sc.CURVE):
+        st = check(ctx, p, tri, 2, boundary=mode)[1]
+        assert (st["outOfRangeTriangles"], st["degenerateTriangles"], st["numEdges"], st["boundaryEdges"]) == (2, 1, 5, 4)
+
+
 # ---------------------------------------------------------------- many workgroups
 
 @pytest.fixture(scope="module")

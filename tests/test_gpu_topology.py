@@ -113,6 +113,14 @@ def test_untrusted_indices(ctx):
     assert (r["boundaryEdges"], r["duplicateEdges"]) == (good["boundaryEdges"], 0)
 
 
+def test_classification_order(ctx):
+    """The hand case on which smoothing and hole filling classify differently (their tests have the other half)."""
+    p, tri = tc.classification_trap()
+    r = report(ctx, len(p), tri)
+    tc.assert_trap_report(r)
+    assert r == tc.count_all(len(p), tri)
+
+
 # ---------------------------------------------------------------- edges of the API
 
 def test_api_edges(ctx):

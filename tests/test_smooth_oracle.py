@@ -49,6 +49,17 @@ def test_counts_of_a_mesh_with_defects():
     assert (st["numEdges"], st["boundaryEdges"], st["boundaryVertices"]) == (33, 0, 0)
 
 
+def test_classification_differs_from_the_topology_report():
+    import topology_cases as tc
+    p, tri = tc.classification_trap()
+    tc.assert_trap_report(tc.count_all(len(p), tri))                # there: one out of range, two degenerate
+    for mode in (sc.FIXED, sc.CURVE):
+        out, st = sc.smooth(p, tri, 2, 0.5, -0.53, mode)
+        assert (st["outOfRangeTriangles"], st["degenerateTriangles"]) == (2, 1)     # here: (1, 1, 7) is out of range
+        assert (st["numEdges"], st["boundaryEdges"], st["boundaryVertices"], st["isolatedVertices"]) == (5, 4, 4, 0)
+        assert out.tobytes() == sc.smooth(p, tri[:2], 2, 0.5, -0.53, mode)[0].tobytes()     # the bad ones take no part
+
+
 # ---------------------------------------------------------------- invariances
 
 @pytest.fixture(scope="module")

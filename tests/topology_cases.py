@@ -212,3 +212,18 @@ def random_mesh(rng):
             v = int(rng.integers(0, V))
             tri = tri[~(tri == v).any(axis=1)]
     return V, tri
+
+
+def classification_trap():
+    """(vertices, triangles): a unit square of two triangles and three bad ones on which the stages disagree BY CONTRACT.  The
+    topology report takes the first failing check of the reference's rotation order (i0 >= V, i0 == i1, i1 >= V, i1 == i2,
+    i2 >= V, i2 == i0); smoothing and hole filling look at the range of all three indices first.  So (1, 1, 7) is degenerate
+    for the one and out of range for the others; (7, 2, 2) is out of range and (3, 3, 3) degenerate for all of them."""
+    p = np.array([[0, 0, 0], [1, 0, 0], [1, 1, 0], [0, 1, 0]], np.float32)
+    return p, np.array([[0, 1, 2], [0, 2, 3], [1, 1, 7], [7, 2, 2], [3, 3, 3]], np.int64)
+
+
+def assert_trap_report(r):
+    """What the topology report says of classification_trap()."""
+    assert r["count"][:2] == [1, 2] and r["firstOf"][:2] == [3, 2] and (r["firstKind"], r["firstIndex"]) == (DEGENERATE, 2), r
+    assert (r["manifold"], r["boundaryEdges"], r["duplicateEdges"]) == (0, 4, 0), r

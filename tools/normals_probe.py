@@ -56,11 +56,13 @@ def main():
             _, stats = m.mesh_normals(ctx, verts, tris)
             wall_ms = (time.perf_counter() - t0) * 1e3      # includes the download of the normals
             ctx.set_timing(False)
-            st = {k: round(v[0], 4) for k, v in ctx.stats().items() if k.startswith("kernel.normals")}
+            raw = ctx.stats()
+            st = {k: round(v[0], 4) for k, v in raw.items() if k.startswith("kernel.normals")}
             kernels = sum(st.values())
             if best is None or kernels < best["kernels_ms"]:
                 acc = st.get("kernel.normals.accumulate", 0.0)
                 best = {"kernels_ms": round(kernels, 4), "wall_with_download_ms": round(wall_ms, 2), "stats": st,
+                        "scratch_bytes": raw["normals.scratch.bytes"][0],
                         "algorithmic_GBps": round(algorithmic / kernels / 1e6, 1) if kernels else None,
                         "accumulate_G_logical_adds_per_s": round(9 * T / acc / 1e6, 2) if acc else None}
         out[mode] = best
