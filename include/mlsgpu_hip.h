@@ -517,7 +517,9 @@ int mlsgpu_hip_bucket(mlsgpu_ctx *ctx, const mlsgpu_splat *dSplats, uint64_t num
                       const mlsgpu_bucket_params *params, mlsgpu_bucket_fn fn, void *user, uint64_t *cellSplats);
 /* FastBlobSet::makeBoundingGrid (src/splat_set_impl.h:770-811): the grid the reference reconstructs on -- reference 0,
  * extents floor(min(p - r) / spacing) rounded down to a multiple of bucketSize, and ceil(max(p + r) / spacing) -- from a
- * min / max reduction over the finite splats on the device. */
+ * min / max reduction over the finite splats on the device.  MLSGPU_ERR_LENGTH (the message names the axis, *out is not
+ * written) if an extent -- the lower one after the rounding -- does not fit int32, or is infinite because position -+ radius
+ * of a finite splat overflowed: the reference throws there (src/grid.h:59-70). */
 int mlsgpu_hip_bounding_grid(mlsgpu_ctx *ctx, const mlsgpu_splat *dSplats, uint64_t numSplats, float spacing,
                              uint32_t bucketSize, mlsgpu_grid *out);
 /* BucketLoader (src/bucket_loader.cpp:77-85, Grid::worldToVertex src/grid.cpp:99-106) on the device:
@@ -1074,7 +1076,8 @@ int mlsgpu_hip_fileset_load(mlsgpu_fileset *files, mlsgpu_ctx *ctx, uint64_t fir
  * stats (may be NULL): [0] passes over the files, [1] batches, [2] splats loaded into batches, [3] file chunks a pass did
  * not have to read (the first pass notes every chunk's bounding box; a batch skips the chunks that stay clear of its regions).
  * MLSGPU_ERR_LENGTH if one top-level region alone exceeds the budget. */
-/* FastBlobSet::makeBoundingGrid (src/splat_set_impl.h:770-811) for such a set: one pass over the files through a chunk buffer */
+/* FastBlobSet::makeBoundingGrid (src/splat_set_impl.h:770-811) for such a set: one pass over the files through a chunk buffer.
+ * MLSGPU_ERR_LENGTH, *out not written, if an extent does not fit int32 (as mlsgpu_hip_bounding_grid). */
 int mlsgpu_hip_fileset_bounding_grid(mlsgpu_fileset *files, mlsgpu_ctx *ctx, float spacing, uint32_t bucketSize,
                                      uint64_t chunkSplats, uint32_t readerThreads, mlsgpu_grid *out);
 int mlsgpu_hip_bucket_stream(mlsgpu_ctx *ctx, mlsgpu_fileset *files, const mlsgpu_grid *region,

@@ -104,7 +104,10 @@ struct RegionView
     }
 
     /* splatToBuckets (src/splat_set.cpp:52-72, Grid::worldToCell src/grid.cpp:108-129) + BucketStateSet's chunk
-     * bias (bucket_impl.h:318-323) + BucketState::clamp (src/bucket.cpp:176-194) */
+     * bias (bucket_impl.h:318-323) + BucketState::clamp (src/bucket.cpp:176-194).
+     * A box that reaches beyond 2^62 cells (a huge radius; position -+ radius overflowing to an infinity from finite fields) is
+     * taken to reach 2^62: the conversion to an integer is not defined for it, and the reference throws there (Grid::RoundDown
+     * converts with boost's def_overflow_handler).  No grid comes near, so such a splat covers or misses what it should. */
     __device__ __forceinline__ bool range(uint32_t id, uint32_t lo[3], uint32_t hi[3]) const
     {
         return rangeOf(splats[id], lo, hi);
@@ -133,8 +136,8 @@ struct RegionView
             }
             else
             {
-                const long long cl = (long long) fl - first[a];
-                const long long ch = (long long) fh - first[a];
+                const long long cl = (long long) fminf(fmaxf(fl, -0x1p62f), 0x1p62f) - first[a];
+                const long long ch = (long long) fminf(fmaxf(fh, -0x1p62f), 0x1p62f) - first[a];
                 const long long m = (long long) microSize;
                 l = (cl >= 0 ? cl / m : -((-cl + m - 1) / m)) - bias[a];      /* divDown */
                 h = (ch >= 0 ? ch / m : -((-ch + m - 1) / m)) - bias[a];
@@ -1403,16 +1406,28 @@ static int gridFromBbox(const float lo[3], const float hi[3], float spacing, uin
 {
     if (lo[0] > hi[0])
         return setError(MLSGPU_ERR_INVALID, "Must be at least one splat");        /* std::runtime_error, :773-774 */
+    /* Grid extents are 32 bits wide: a cloud that needs more is refused as the reference refuses it (Grid::RoundDown /
+     * RoundUp throw, src/grid.h:59-70 -- also for the infinite corner of a finite splat), before *out is touched */
+    int32_t ext[6];
     for (int a = 0; a < 3; a++)
     {
-        out->reference[a] = 0.0f;
-        int64_t l = (int64_t) std::floor(lo[a] / spacing);
-        const int64_t h = (int64_t) std::ceil(hi[a] / spacing);
+        const float fl = std::floor(lo[a] / spacing), fh = std::ceil(hi[a] / spacing);
+        if (!(std::fabs(fl) < 0x1p62f && std::fabs(fh) < 0x1p62f))
+            return setError(MLSGPU_ERR_LENGTH, "bounding grid: %c extents do not fit 32 bits", "xyz"[a]);
+        int64_t l = (int64_t) fl;
+        const int64_t h = (int64_t) fh;
         const int64_t b = (int64_t) bucketSize;
         l = (l >= 0 ? l / b : -((-l + b - 1) / b)) * b;       /* the lower extent is a multiple of the bucket size */
-        out->extents[2 * a] = (int32_t) l;
-        out->extents[2 * a + 1] = (int32_t) h;
+        if (l < INT32_MIN || l > INT32_MAX || h < INT32_MIN || h > INT32_MAX)
+            return setError(MLSGPU_ERR_LENGTH, "bounding grid: %c extents [%lld, %lld) do not fit 32 bits", "xyz"[a],
+                            (long long) l, (long long) h);
+        ext[2 * a] = (int32_t) l;
+        ext[2 * a + 1] = (int32_t) h;
     }
+    for (int a = 0; a < 3; a++)
+        out->reference[a] = 0.0f;
+    for (int i = 0; i < 6; i++)
+        out->extents[i] = ext[i];
     out->spacing = spacing;
     return MLSGPU_OK;
 }

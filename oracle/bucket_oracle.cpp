@@ -70,8 +70,11 @@ void splatToBuckets(const Splat &s, const Grid &g, uint32_t bucketSize, int64_t 
     for (int i = 0; i < 3; i++)
     {
         const float loWorld = s.position[i] - s.radius, hiWorld = s.position[i] + s.radius;
-        const int64_t lo = (int64_t) std::floor((loWorld - g.reference[i]) * inv) - g.lo[i];
-        const int64_t hi = (int64_t) std::floor((hiWorld - g.reference[i]) * inv) - g.lo[i];
+        /* a box beyond 2^62 cells is taken to reach 2^62 (the conversion is undefined from 2^63 on and for the infinities that
+         * position -+ radius of a finite splat can overflow to; the reference throws there): as bucket.hip's rangeOf */
+        const float fl = std::floor((loWorld - g.reference[i]) * inv), fh = std::floor((hiWorld - g.reference[i]) * inv);
+        const int64_t lo = (int64_t) std::fmin(std::fmax(fl, -0x1p62f), 0x1p62f) - g.lo[i];
+        const int64_t hi = (int64_t) std::fmin(std::fmax(fh, -0x1p62f), 0x1p62f) - g.lo[i];
         lower[i] = divDown(lo, bucketSize);
         upper[i] = divDown(hi, bucketSize);
     }
