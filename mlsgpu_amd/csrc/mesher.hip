@@ -148,37 +148,56 @@ __global__ void compressKernel(uint32_t *parent, const uint32_t *compRep, uint64
  * wave walks a contiguous span and keeps one pending (root, count) in registers; it only touches memory when the root
  * changes. */
 #define SIZE_SPAN 64        /* steps of 64 vertices per wave */
-__global__ __launch_bounds__(256) void componentSizeKernel(const uint32_t *compRep, const uint32_t *root, uint64_t n, uint32_t *size)
+
+/* The walk of the three counting kernels: a wave takes SIZE_SPAN steps of 64 items over [0, n); in a step the lanes whose item
+ * countsAt(i) load valueAt(i), and sink(value, lanes) is called, wave-uniformly and lowest lane first, once per equal value. */
+template<typename Counts, typename Value, typename Sink>
+__device__ __forceinline__ void forEachRun(uint64_t n, Counts countsAt, Value valueAt, Sink &sink)
 {
     const uint64_t wave = ((uint64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t first = wave * (64 * SIZE_SPAN);
-    uint32_t pendingRoot = 0, pendingCount = 0;         /* wave-uniform */
     for (uint32_t s = 0; s < SIZE_SPAN; s++)
     {
         const uint64_t i = first + (uint64_t) s * 64 + laneId();
         if (first + (uint64_t) s * 64 >= n)
             break;
-        const bool counts = i < n && compRep[i] == (uint32_t) i;
-        const uint32_t mine = counts ? root[i] : 0u;
+        const bool counts = i < n && countsAt(i);
+        const uint32_t mine = counts ? valueAt(i) : 0u;
         uint64_t todo = __ballot(counts);
         while (todo != 0)
         {
             const uint32_t r = readLane(mine, (int) __builtin_ctzll(todo));
             const uint64_t same = __ballot(counts && mine == r) & todo;
-            const uint32_t c = (uint32_t) __popcll(same);
-            if (pendingCount != 0 && r != pendingRoot)
-            {
-                if (laneId() == 0)
-                    atomicAdd(&size[pendingRoot], pendingCount);
-                pendingCount = 0;
-            }
-            pendingRoot = r;
-            pendingCount += c;
+            sink(r, (uint32_t) __popcll(same));
             todo &= ~same;
         }
     }
-    if (pendingCount != 0 && laneId() == 0)
-        atomicAdd(&size[pendingRoot], pendingCount);
+}
+
+struct PendingRun           /* the pending (root, count) of a wave; flush() once more at the end */
+{
+    uint32_t *total;
+    uint32_t root = 0, count = 0;
+    __device__ __forceinline__ void flush()
+    {
+        if (count != 0 && laneId() == 0)
+            atomicAdd(&total[root], count);
+        count = 0;
+    }
+    __device__ __forceinline__ void operator()(uint32_t r, uint32_t c)
+    {
+        if (r != root)
+            flush();
+        root = r;
+        count += c;
+    }
+};
+
+__global__ __launch_bounds__(256) void componentSizeKernel(const uint32_t *compRep, const uint32_t *root, uint64_t n, uint32_t *size)
+{
+    PendingRun pending{size};
+    forEachRun(n, [&](uint64_t i) { return compRep[i] == (uint32_t) i; }, [&](uint64_t i) { return root[i]; }, pending);
+    pending.flush();
 }
 
 /* [0] welded vertices, [1] components, [2] kept components, [3] kept vertices */
@@ -312,34 +331,9 @@ struct RootOut
 __global__ __launch_bounds__(256) void componentTrianglesKernel(const uint32_t *tri, const uint32_t *root, const uint32_t *denseOf,
                                                                 uint64_t nt, uint32_t *count)
 {
-    const uint64_t wave = ((uint64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t first = wave * (64 * SIZE_SPAN);
-    uint32_t pendingRoot = 0, pendingCount = 0;
-    for (uint32_t s = 0; s < SIZE_SPAN; s++)
-    {
-        const uint64_t t = first + (uint64_t) s * 64 + laneId();
-        if (first + (uint64_t) s * 64 >= nt)
-            break;
-        const bool counts = t < nt;
-        const uint32_t mine = counts ? denseOf[root[tri[3 * t]]] : 0u;
-        uint64_t todo = __ballot(counts);
-        while (todo != 0)
-        {
-            const uint32_t r = readLane(mine, (int) __builtin_ctzll(todo));
-            const uint64_t same = __ballot(counts && mine == r) & todo;
-            if (pendingCount != 0 && r != pendingRoot)
-            {
-                if (laneId() == 0)
-                    atomicAdd(&count[pendingRoot], pendingCount);
-                pendingCount = 0;
-            }
-            pendingRoot = r;
-            pendingCount += (uint32_t) __popcll(same);
-            todo &= ~same;
-        }
-    }
-    if (pendingCount != 0 && laneId() == 0)
-        atomicAdd(&count[pendingRoot], pendingCount);
+    PendingRun pending{count};
+    forEachRun(nt, [](uint64_t) { return true; }, [&](uint64_t t) { return denseOf[root[tri[3 * t]]]; }, pending);
+    pending.flush();
 }
 
 /* The same count for FEW components (surface-like data: a handful of sheets whose triangles alternate along every row of
@@ -353,25 +347,8 @@ __global__ __launch_bounds__(256) void componentTrianglesFewKernel(const uint32_
     for (uint32_t d = threadIdx.x; d < numRoots; d += 256)
         bins[d] = 0;
     __syncthreads();
-    const uint64_t wave = ((uint64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint64_t first = wave * (64 * SIZE_SPAN);
-    for (uint32_t s = 0; s < SIZE_SPAN; s++)
-    {
-        const uint64_t t = first + (uint64_t) s * 64 + laneId();
-        if (first + (uint64_t) s * 64 >= nt)
-            break;
-        const bool counts = t < nt;
-        const uint32_t mine = counts ? denseOf[root[tri[3 * t]]] : 0u;
-        uint64_t todo = __ballot(counts);
-        while (todo != 0)
-        {
-            const uint32_t r = readLane(mine, (int) __builtin_ctzll(todo));
-            const uint64_t same = __ballot(counts && mine == r) & todo;
-            if (laneId() == 0)
-                atomicAdd(&bins[r], (uint32_t) __popcll(same));
-            todo &= ~same;
-        }
-    }
+    auto toBin = [&](uint32_t r, uint32_t c) { if (laneId() == 0) atomicAdd(&bins[r], c); };
+    forEachRun(nt, [](uint64_t) { return true; }, [&](uint64_t t) { return denseOf[root[tri[3 * t]]]; }, toBin);
     __syncthreads();
     for (uint32_t d = threadIdx.x; d < numRoots; d += 256)
         if (bins[d] != 0)
@@ -442,41 +419,111 @@ struct Arena
     }
 };
 
-} // namespace
+const dim3 B(256);          /* every launch of the stages below */
 
-namespace
-{
 /* bump allocator over a slab the mesher keeps between calls: allocating and freeing tens of GB of scratch costs
- * several times the kernels that use it */
+ * several times the kernels that use it.  Without a base it only measures: nothing is handed out, `used` adds up. */
 struct Scratch
 {
     char *base;
     uint64_t cap, used = 0;
-    Scratch(void *base, uint64_t cap) : base(static_cast<char *>(base)), cap(cap) {}
+    explicit Scratch(void *base = nullptr, uint64_t cap = ~uint64_t(0)) : base(static_cast<char *>(base)), cap(cap) {}
     template<typename T> int get(T **p, uint64_t n)
     {
         const uint64_t bytes = (std::max<uint64_t>(n, 1) * sizeof(T) + 255) & ~uint64_t(255);
-        if (used + bytes > cap)
+        if (bytes > cap - used)
             return setError(MLSGPU_ERR_NOMEM, "mesher: scratch slab too small (%llu of %llu bytes used, %llu more wanted)",
                             (unsigned long long) used, (unsigned long long) cap, (unsigned long long) bytes);
-        *p = reinterpret_cast<T *>(base + used);
+        *p = base != nullptr ? reinterpret_cast<T *>(base + used) : nullptr;
         used += bytes;
         return MLSGPU_OK;
     }
 };
 
-uint64_t scratchBytes(uint64_t nv, uint64_t nt, uint64_t ne, uint64_t nb, uint64_t nc)
+struct SinkSizes
 {
-    auto al = [](uint64_t b) { return (std::max<uint64_t>(b, 1) + 255) & ~uint64_t(255); };
-    uint64_t total = 6 * al(nv * 4) + al(nt * 4);                                   /* per-vertex arrays, tIndex */
-    total += 2 * al(ne * 8) + 2 * al(ne * 4) + al(sortHistElems(ne) * 4)            /* key sort */
-        + al(scanTiles(std::max<uint64_t>(sortHistElems(ne), ne)) * 4);
-    total += al(scanTiles(std::max(nv, nt)) * 4);                                   /* scans */
-    total += 2 * al((nb + 1) * 8) + 2 * al((nb + 1) * 4) + 3 * al((nc + 1) * 8) + 8 * 256;
-    total += 2 * al(scanTiles(nv) * 4) + al(scanTiles(ne) * 4) + al(nv);            /* boundary export / verdict */
-    total += 2 * al(nv * 4);                                                        /* ... vertices and triangles per component */
-    return total + (1 << 20);
+    uint64_t nv, nt, ne;        /* vertices, triangles and external vertices in the arenas */
+    uint32_t nb, nc;            /* blocks, chunks */
+    bool empty() const { return nv == 0 || nt == 0; }
+};
+
+/* Every array that finalize, boundary and finalize_with take from the slab, for all of them at once: where an array lies
+ * depends on the five sizes alone.  That is what lets a call start from what an earlier one left behind (SinkCache). */
+struct SinkScratch
+{
+    /* per vertex: the first of its key run and of its (key, chunk) run, the forest, its root, a root's vertices, its output index */
+    uint32_t *compRep, *outRep, *parent, *root, *size, *vIndex;
+    uint64_t *keysA, *keysB;                    /* the key sort's two halves ... */
+    uint32_t *slotsA, *slotsB, *hist, *sortTileSums;
+    bool sortedInA;                             /* ... and which of them holds the sorted keys (weld, or the cache) */
+    uint32_t *dFailed, *dRootTotal, *rootTiles; /* the union did not converge; numberRoots */
+    uint32_t *tcount, *vcount, *dKeyTotal, *keyTiles;   /* exportBoundary: triangles and vertices per root ([nv]: its bound) */
+    uint8_t *dKeep;                             /* applyVerdict ([nv] likewise) */
+    unsigned long long *dStats;                 /* writeOutput */
+    uint64_t *dTBase, *dAt;
+    uint32_t *dVBase, *dChunkOf, *dChunkVStart, *dChunkTStart, *dTotals, *tileSums, *tIndex;
+
+    /* overlays.  From numberRoots on: root d's vertex, over the forest, which nothing reads once `root` is written ... */
+    uint32_t *rootId() const { return parent; }
+    /* ... and a root vertex's dense number, until writeOutput puts the output indices there */
+    uint32_t *denseOf() const { return vIndex; }
+    uint64_t *sortedKeys() const { return sortedInA ? keysA : keysB; }
+    uint32_t *sortedSlots() const { return sortedInA ? slotsA : slotsB; }
+    /* in exportBoundary: the distinct keys and their roots, over the halves the sort left free */
+    uint64_t *keyOut() const { return sortedInA ? keysB : keysA; }
+    uint32_t *rootOut() const { return sortedInA ? slotsB : slotsA; }
+
+    int lay(Scratch &S, const SinkSizes &z)
+    {
+        for (uint32_t **p : {&compRep, &outRep, &parent, &root, &size, &vIndex, &tcount, &vcount})
+            PROPAGATE(S.get(p, z.nv));
+        PROPAGATE(S.get(&dKeep, z.nv));
+        for (uint64_t **p : {&keysA, &keysB})
+            PROPAGATE(S.get(p, z.ne));
+        for (uint32_t **p : {&slotsA, &slotsB})
+            PROPAGATE(S.get(p, z.ne));
+        PROPAGATE(S.get(&hist, sortHistElems(z.ne)));
+        PROPAGATE(S.get(&sortTileSums, scanTiles(std::max<uint64_t>(sortHistElems(z.ne), z.ne))));
+        for (uint32_t **p : {&dFailed, &dRootTotal, &dKeyTotal})
+            PROPAGATE(S.get(p, 1));
+        PROPAGATE(S.get(&rootTiles, scanTiles(z.nv)));
+        PROPAGATE(S.get(&keyTiles, scanTiles(z.ne)));
+        PROPAGATE(S.get(&dStats, 4));
+        PROPAGATE(S.get(&dTBase, z.nb + 1));
+        PROPAGATE(S.get(&dVBase, z.nb + 1));
+        PROPAGATE(S.get(&dChunkOf, z.nb));
+        for (uint32_t **p : {&dChunkVStart, &dChunkTStart})
+            PROPAGATE(S.get(p, z.nc + 1));
+        PROPAGATE(S.get(&dAt, z.nc + 1));
+        PROPAGATE(S.get(&dTotals, 2));
+        PROPAGATE(S.get(&tileSums, scanTiles(std::max(z.nv, z.nt))));
+        return S.get(&tIndex, z.nt);
+    }
+};
+
+/* what the layout takes, and 1 MiB */
+uint64_t scratchBytes(const SinkSizes &z)
+{
+    Scratch measure;
+    SinkScratch L;
+    (void) L.lay(measure, z);
+    return measure.used + (1 << 20);
 }
+
+/* What the last analysis left in the slab, valid while nothing is added (same arenas) and the slab stays where it is.
+ * AfterExport: boundary()'s weld and components (representatives, roots, sizes) AND the dense root numbering -- a
+ * finalize_with() right behind it starts from them instead of sorting and uniting again (once: the verdict overwrites the
+ * sizes).  AfterFinalize: finalize()'s weld and components (the output pass only rewrote the vertex index array) -- a
+ * boundary() behind it numbers the roots and exports, without the key sort and the union-find. */
+struct SinkCache
+{
+    enum Kind { None, AfterExport, AfterFinalize } kind = None;
+    bool sortedInA = false;
+    uint64_t nv = 0, nt = 0, ne = 0;
+    uint32_t rootCount = 0;
+    bool matches(uint64_t v, uint64_t t, uint64_t e) const { return kind != None && nv == v && nt == t && ne == e; }
+    void drop() { kind = None; }
+};
 } // namespace
 
 struct mlsgpu_mesher
@@ -493,17 +540,7 @@ struct mlsgpu_mesher
     std::vector<uint64_t> chunkIds;             /* dense index -> caller's id, arrival order */
     bool finalized = false;
     bool peerEnabled[16] = {};                  /* peer access towards the GPUs whose workers have appended */
-    /* What the last analysis left in the slab, valid while nothing is added (same arenas):
-     *   1  after boundary(): the weld and the components (representatives, roots, sizes) AND the dense root numbering -- a
-     *      finalize_with() right behind it starts from them instead of sorting and uniting again (one use: the verdict
-     *      overwrites the sizes);
-     *   2  after a plain finalize(): the weld and the components (the output pass only rewrote the vertex index array) -- a
-     *      boundary() behind it numbers the roots and exports, without the key sort and the union-find;
-     *   0  nothing. */
-    int cacheKind = 0;
-    bool cacheSortedInA = false;                /* which of the sort's two buffers holds the sorted external keys */
-    uint64_t cacheDims[3] = {0, 0, 0};
-    uint32_t cacheRootCount = 0;
+    SinkCache cache;                            /* what the last analysis left in the slab */
     /* results */
     DeviceArray<float> outVertices;             /* 3 per vertex */
     DeviceArray<uint32_t> outTriangles;         /* 3 per triangle */
@@ -530,7 +567,7 @@ struct mlsgpu_mesher
     {
         if (bytes <= slab.capacity())
             return MLSGPU_OK;
-        cacheKind = 0;          /* whatever an analysis left in the old slab is gone */
+        cache.drop();           /* whatever an analysis left in the old slab is gone */
         return slab.reserve(bytes);
     }
     int ensureOutputs(uint64_t nv, uint64_t nt)
@@ -581,10 +618,46 @@ struct mlsgpu_mesher
         return MLSGPU_OK;
     }
     int regroupByChunk();
+    struct Span { uint64_t v0, t0, nv, nt; };
+    Span span(size_t c) const           /* dense chunk c of the results: first vertex and triangle, how many of each */
+    {
+        return {chunkVStart[c], chunkTStart[c], chunkVStart[c + 1] - chunkVStart[c], chunkTStart[c + 1] - chunkTStart[c]};
+    }
     void dropNormals() { normalsReady.clear(); }
     void dropResults() { finalized = false; dropNormals(); }
     int chunkNormals(uint32_t c, const float **dNormals, mlsgpu_normals_stats *out);
-    int finalizeImpl(uint32_t *numChunks, bool analyzeOnly, const uint8_t *keepRoots, uint64_t numRoots);
+    /* finalize, boundary and finalize_with: a shared start, then their stages in this order */
+    int begin(SinkSizes &z, SinkScratch &L, SinkCache &had);
+    int weld(SinkScratch &L, const SinkSizes &z);
+    int components(const SinkScratch &L, const SinkSizes &z);
+    /* weld and components, unless the slab still holds them; the union's failure flag is cleared either way */
+    int analyse(SinkScratch &L, const SinkSizes &z, bool cached)
+    {
+        if (!cached)
+            PROPAGATE(weld(L, z));
+        HIP_CHECK(hipMemsetAsync(L.dFailed, 0, 4, ctx->stream));
+        return cached ? MLSGPU_OK : components(L, z);
+    }
+    int checkUnion(const SinkScratch &L)        /* the union's failure flag, behind whatever is on the stream: synchronises */
+    {
+        uint32_t hFailed = 0;
+        HIP_CHECK(hipMemcpyAsync(&hFailed, L.dFailed, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (hFailed != 0)
+            return setError(MLSGPU_ERR_HIP, "mesher: component union did not converge");
+        return MLSGPU_OK;
+    }
+    int numberRoots(const SinkScratch &L, const SinkSizes &z, uint32_t *rootCount);
+    int exportBoundary(const SinkScratch &L, const SinkSizes &z, uint32_t rootCount);
+    int applyVerdict(const SinkScratch &L, uint32_t rootCount, const uint8_t *keepRoots, uint64_t numRoots);
+    int writeOutput(const SinkScratch &L, const SinkSizes &z, double fraction, uint64_t minSize);
+    int finish(uint32_t *numChunks)             /* finalized, with the chunks writeOutput left (none for an empty sink) */
+    {
+        finalized = true;
+        if (numChunks)
+            *numChunks = (uint32_t) outChunks.size();
+        return MLSGPU_OK;
+    }
     ~mlsgpu_mesher()
     {
         if (addStream) hipStreamDestroy(addStream);
@@ -641,7 +714,7 @@ MLSGPU_API int mlsgpu_hip_mesher_reserve(mlsgpu_mesher *m, uint64_t numVertices,
     PROPAGATE(m->extGid.reserve(m->addStream, numExternal));
     PROPAGATE(m->extChunk.reserve(m->addStream, numExternal));
     /* finalize's scratch and outputs too (a few hundred blocks and chunks are assumed; finalize grows it otherwise) */
-    PROPAGATE(m->ensureSlab(scratchBytes(numVertices, numTriangles, numExternal, 4096, 4096)));
+    PROPAGATE(m->ensureSlab(scratchBytes(SinkSizes{numVertices, numTriangles, numExternal, 4096, 4096})));
     PROPAGATE(m->ensureOutputs(numVertices, numTriangles));
     return MLSGPU_OK;
 }
@@ -774,7 +847,7 @@ MLSGPU_API int mlsgpu_hip_mesher_add(mlsgpu_mesher *m, mlsgpu_ctx *from, uint64_
         m->chunkIds.push_back(chunkId);
     m->blocks.push_back(r);
     m->analyzed = false;
-    m->cacheKind = 0;
+    m->cache.drop();
     return MLSGPU_OK;
 }
 
@@ -798,7 +871,7 @@ MLSGPU_API int mlsgpu_hip_mesher_reset(mlsgpu_mesher *m)
     m->outChunks.clear();
     m->dropResults();
     m->analyzed = false;
-    m->cacheKind = 0;
+    m->cache.drop();
     return MLSGPU_OK;
 }
 
@@ -869,240 +942,153 @@ int mlsgpu_mesher::regroupByChunk()
     return MLSGPU_OK;
 }
 
-
-/* MesherBase::write's finalisation (src/mesher.cpp:763-852) up to the point where files are written */
-MLSGPU_API int mlsgpu_hip_mesher_finalize(mlsgpu_mesher *m, uint32_t *numChunks)
+/* What finalize, boundary and finalize_with start with: appends landed, blocks grouped by chunk, results emptied, slab and
+ * outputs large enough and laid out.  `had`: what the slab holds of THESE arenas; a call that succeeds records its own. */
+int mlsgpu_mesher::begin(SinkSizes &z, SinkScratch &L, SinkCache &had)
 {
-    REQUIRE(m != nullptr, MLSGPU_ERR_INVALID);
-    std::lock_guard<std::mutex> lock(m->mutex);
-    return m->finalizeImpl(numChunks, false, nullptr, 0);
+    PROPAGATE(drainPending());
+    HIP_CHECK(hipSetDevice(ctx->device));
+    dropResults();
+    PROPAGATE(regroupByChunk());
+    z = SinkSizes{vertices.used / 3, triangles.used / 3, extKeys.used, (uint32_t) blocks.size(), (uint32_t) chunkIds.size()};
+    had = cache.matches(z.nv, z.nt, z.ne) ? cache : SinkCache();
+    cache.drop();
+    chunkVStart.assign(z.nc + 1, 0);
+    chunkTStart.assign(z.nc + 1, 0);
+    outChunks.clear();
+    std::fill(stats, stats + 8, 0);
+    if (z.empty())
+        return MLSGPU_OK;
+    const uint64_t slabBefore = slab.capacity();
+    PROPAGATE(ensureSlab(scratchBytes(z)));
+    if (slab.capacity() != slabBefore)
+        had.drop();             /* (cannot happen for unchanged arenas; the cached analysis lived there) */
+    PROPAGATE(ensureOutputs(z.nv, z.nt));
+    Scratch S(slab, slab.capacity());
+    PROPAGATE(L.lay(S, z));
+    L.sortedInA = had.sortedInA;
+    return MLSGPU_OK;
 }
 
-/* analyzeOnly: weld + components, then the boundary export instead of any output.  keepRoots: the caller's verdict per
- * dense root (the numbering of the last export; the union-find hooks larger roots under smaller ones, so a component's
- * root is its smallest welded vertex whatever the schedule and the numbering is reproducible) replaces the prune rule. */
-int mlsgpu_mesher::finalizeImpl(uint32_t *numChunks, bool analyzeOnly, const uint8_t *keepRoots, uint64_t numRoots)
+/* 1. every vertex its own representative, then the externals' from the sorted keys */
+int mlsgpu_mesher::weld(SinkScratch &L, const SinkSizes &z)
 {
-    mlsgpu_mesher *const m = this;
-    mlsgpu_ctx *ctx = m->ctx;
-    PROPAGATE(m->drainPending());
-    HIP_CHECK(hipSetDevice(ctx->device));
-    m->dropResults();
-    PROPAGATE(m->regroupByChunk());
-    const uint64_t nv = m->vertices.used / 3, nt = m->triangles.used / 3, ne = m->extKeys.used;
-    const uint32_t nb = (uint32_t) m->blocks.size(), nc = (uint32_t) m->chunkIds.size();
-    /* the verdict pass right behind an export: weld, components and root numbering are still in the slab */
-    const bool sameArenas = m->cacheDims[0] == nv && m->cacheDims[1] == nt && m->cacheDims[2] == ne;
-    bool reuseDense = keepRoots != nullptr && !analyzeOnly && m->cacheKind == 1 && sameArenas;
-    /* the weld and the components are in the slab: after an export (for the verdict pass, or for another export) or after a
-     * plain finalize (for an export) */
-    bool reuse = reuseDense || (analyzeOnly && m->cacheKind != 0 && sameArenas);
-    m->cacheKind = 0;
-    m->chunkVStart.assign(nc + 1, 0);
-    m->chunkTStart.assign(nc + 1, 0);
-    m->outChunks.clear();
-    std::fill(m->stats, m->stats + 8, 0);
-    if (analyzeOnly)
-    {
-        m->bKeys.clear();
-        m->bKeyRoot.clear();
-        m->bRootVertices.clear();
-        m->bRootTriangles.clear();
-        m->analyzed = true;
-    }
-    if (nv == 0 || nt == 0)
-    {
-        m->finalized = !analyzeOnly;
-        if (numChunks)
-            *numChunks = 0;
+    for (uint32_t *ids : {L.compRep, L.outRep, L.parent})       /* three launches */
+        LAUNCH(ctx, "mesher.weld.time", iotaKernel, dim3(divUp(z.nv, 256)), B, ids, z.nv);
+    HIP_CHECK(hipMemsetAsync(L.size, 0, z.nv * 4, ctx->stream));
+    if (z.ne == 0)
         return MLSGPU_OK;
-    }
-    {
-        const uint64_t slabBefore = m->slab.capacity();
-        PROPAGATE(m->ensureSlab(scratchBytes(nv, nt, ne, nb, nc)));
-        if (m->slab.capacity() != slabBefore)
-            reuse = reuseDense = false;         /* (cannot happen for unchanged arenas; the cached analysis lived there) */
-    }
-    PROPAGATE(m->ensureOutputs(nv, nt));
-    Scratch S(m->slab, m->slab.capacity());
-    uint32_t *compRep, *outRep, *parent, *root, *size, *vIndex;
-    PROPAGATE(S.get(&compRep, nv));
-    PROPAGATE(S.get(&outRep, nv));
-    PROPAGATE(S.get(&parent, nv));
-    PROPAGATE(S.get(&root, nv));
-    PROPAGATE(S.get(&size, nv));
-    PROPAGATE(S.get(&vIndex, nv));
-    const dim3 B(256);
-    if (!reuse)
-    {
-        LAUNCH(ctx, "mesher.weld.time", iotaKernel, dim3(divUp(nv, 256)), B, compRep, nv);
-        LAUNCH(ctx, "mesher.weld.time", iotaKernel, dim3(divUp(nv, 256)), B, outRep, nv);
-        LAUNCH(ctx, "mesher.weld.time", iotaKernel, dim3(divUp(nv, 256)), B, parent, nv);
-        HIP_CHECK(hipMemsetAsync(size, 0, nv * 4, ctx->stream));
-    }
-
-    /* 1. weld */
     SortResult<uint64_t> sorted = {nullptr, nullptr};
-    uint64_t *keysA = nullptr, *keysB = nullptr;
-    uint32_t *slotsA = nullptr, *slotsB = nullptr;
-    if (ne > 0)
-    {
-        uint32_t *hist, *tileSums;
-        PROPAGATE(S.get(&keysA, ne));
-        PROPAGATE(S.get(&keysB, ne));
-        PROPAGATE(S.get(&slotsA, ne));
-        PROPAGATE(S.get(&slotsB, ne));
-        PROPAGATE(S.get(&hist, sortHistElems(ne)));
-        PROPAGATE(S.get(&tileSums, scanTiles(std::max<uint64_t>(sortHistElems(ne), ne))));
-        if (!reuse)
-        {
-            HIP_CHECK(hipMemcpyAsync(keysA, m->extKeys.ptr, ne * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            PROPAGATE(radixSort<uint64_t>(ctx, "mesher.weld.time", keysA, slotsA, keysB, slotsB, ne, 64, true, hist, tileSums, &sorted));
-            m->cacheSortedInA = sorted.keys == keysA;
-            LAUNCH(ctx, "mesher.weld.time", externalRepsKernel, dim3(divUp(ne, 256)), B, (const uint64_t *) sorted.keys,
-                   (const uint32_t *) sorted.vals, (const uint32_t *) m->extGid.ptr, (const uint32_t *) m->extChunk.ptr, ne, compRep, outRep);
-        }
-        else
-        {
-            sorted.keys = m->cacheSortedInA ? keysA : keysB;
-            sorted.vals = m->cacheSortedInA ? slotsA : slotsB;
-        }
-    }
+    HIP_CHECK(hipMemcpyAsync(L.keysA, extKeys.ptr, z.ne * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    PROPAGATE(radixSort<uint64_t>(ctx, "mesher.weld.time", L.keysA, L.slotsA, L.keysB, L.slotsB, z.ne, 64, true, L.hist,
+                                  L.sortTileSums, &sorted));
+    L.sortedInA = sorted.keys == L.keysA;
+    LAUNCH(ctx, "mesher.weld.time", externalRepsKernel, dim3(divUp(z.ne, 256)), B, (const uint64_t *) sorted.keys,
+           (const uint32_t *) sorted.vals, (const uint32_t *) extGid.ptr, (const uint32_t *) extChunk.ptr, z.ne, L.compRep, L.outRep);
+    return MLSGPU_OK;
+}
 
-    /* 2. components */
-    uint32_t *dFailed;
-    PROPAGATE(S.get(&dFailed, 1));
-    HIP_CHECK(hipMemsetAsync(dFailed, 0, 4, ctx->stream));
-    if (!reuse)
-    {
-        /* measured in round 3 (ms per finalize, shortcut beyond 1 / 3 / 8 steps): shells cloud (17.8 M vertices) 13.3 / 12.8 /
-         * 14.1, noise cloud (378 M) 113.9 / 103.9 / 96.3 */
-        static const int forced = getenv("MLSGPU_HIP_UF_SHORTCUT") ? atoi(getenv("MLSGPU_HIP_UF_SHORTCUT")) : -1;
-        const uint32_t unionShortcut = forced >= 0 ? (uint32_t) forced : (nv < (uint64_t(100) << 20) ? 3u : 8u);
-        /* background (mlsgpu_hip_mesher_set_background): dynamic LDS the kernel never touches leaves it four workgroups per
-         * CU.  The pass waits on L2 atomics, not on wave slots -- a surface-like mesh takes as long either way -- but at full
-         * occupancy it slows the kernels of the job that is streaming in behind it. */
-        const uint32_t ufPad = m->background && nv < (uint64_t(100) << 20) ? 40000u : 0u;     /* (a mesh of hundreds of millions
-                                                                                                * of vertices does need the slots) */
-        LAUNCH_LDS(ctx, "mesher.components.time", unionKernel, dim3(divUp(nt, 256)), B, ufPad, (const uint32_t *) m->triangles.ptr, nt,
-                   (const uint32_t *) compRep, parent, dFailed, unionShortcut);
-        LAUNCH(ctx, "mesher.components.time", compressKernel, dim3(divUp(nv, 256)), B, parent, (const uint32_t *) compRep, nv, root);
-        LAUNCH(ctx, "mesher.components.time", componentSizeKernel, dim3(divUp(divUp(nv, 64 * SIZE_SPAN), 4)), B,
-               (const uint32_t *) compRep, (const uint32_t *) root, nv, size);
-    }
+/* 2. union, roots, vertices per root */
+int mlsgpu_mesher::components(const SinkScratch &L, const SinkSizes &z)
+{
+    /* measured in round 3 (ms per finalize, shortcut beyond 1 / 3 / 8 steps): shells cloud (17.8 M vertices) 13.3 / 12.8 /
+     * 14.1, noise cloud (378 M) 113.9 / 103.9 / 96.3 */
+    static const int forced = getenv("MLSGPU_HIP_UF_SHORTCUT") ? atoi(getenv("MLSGPU_HIP_UF_SHORTCUT")) : -1;
+    const uint32_t unionShortcut = forced >= 0 ? (uint32_t) forced : (z.nv < (uint64_t(100) << 20) ? 3u : 8u);
+    /* background (mlsgpu_hip_mesher_set_background): dynamic LDS the kernel never touches leaves it four workgroups per
+     * CU.  The pass waits on L2 atomics, not on wave slots -- a surface-like mesh takes as long either way -- but at full
+     * occupancy it slows the kernels of the job that is streaming in behind it. */
+    const uint32_t ufPad = background && z.nv < (uint64_t(100) << 20) ? 40000u : 0u;        /* (a mesh of hundreds of millions
+                                                                                             * of vertices does need the slots) */
+    LAUNCH_LDS(ctx, "mesher.components.time", unionKernel, dim3(divUp(z.nt, 256)), B, ufPad, (const uint32_t *) triangles.ptr, z.nt,
+               (const uint32_t *) L.compRep, L.parent, L.dFailed, unionShortcut);
+    LAUNCH(ctx, "mesher.components.time", compressKernel, dim3(divUp(z.nv, 256)), B, L.parent, (const uint32_t *) L.compRep, z.nv, L.root);
+    LAUNCH(ctx, "mesher.components.time", componentSizeKernel, dim3(divUp(divUp(z.nv, 64 * SIZE_SPAN), 4)), B,
+           (const uint32_t *) L.compRep, (const uint32_t *) L.root, z.nv, L.size);
+    return MLSGPU_OK;
+}
 
-    /* 2b. several meshers, one job: the dense roots (needed by both the export and the verdict) */
-    uint32_t rootCount = 0;
-    uint32_t *const rootId = parent;            /* the union-find forest is not needed any more */
-    uint32_t *const denseOf = vIndex;           /* the output pass rewrites it later */
-    if (analyzeOnly || keepRoots != nullptr)
-    {
-        uint32_t *dRootTotal, *rootTiles;
-        PROPAGATE(S.get(&dRootTotal, 1));
-        PROPAGATE(S.get(&rootTiles, scanTiles(nv)));
-        if (reuseDense)
-            rootCount = m->cacheRootCount;
-        else
-        {
-            PROPAGATE((exclusiveScan<uint32_t>(ctx, "mesher.components.time", IsRootIn{compRep, root}, RootOut{rootId, denseOf}, nv, 0u,
-                                               rootTiles, dRootTotal)));
-            HIP_CHECK(hipMemcpyAsync(&rootCount, dRootTotal, 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        }
-    }
-    if (analyzeOnly)
-    {
-        uint32_t hFailed = 0;
-        HIP_CHECK(hipMemcpyAsync(&hFailed, dFailed, 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (hFailed != 0)
-            return setError(MLSGPU_ERR_HIP, "mesher: component union did not converge");
-        /* vertices and triangles per root, in buffers of their own: representatives, roots and sizes stay intact for the
-         * verdict pass (finalize_with) that follows an export */
-        uint32_t *tcount, *vcount;
-        PROPAGATE(S.get(&tcount, std::max<uint64_t>(rootCount, 1)));
-        PROPAGATE(S.get(&vcount, std::max<uint64_t>(rootCount, 1)));
-        HIP_CHECK(hipMemsetAsync(tcount, 0, (size_t) rootCount * 4, ctx->stream));
-        if (rootCount <= FEW_COMPONENTS)
-            LAUNCH(ctx, "mesher.components.time", componentTrianglesFewKernel, dim3(divUp(divUp(nt, 64 * SIZE_SPAN), 4)), B,
-                   (const uint32_t *) m->triangles.ptr, (const uint32_t *) root, (const uint32_t *) denseOf, nt, rootCount, tcount);
-        else
-            LAUNCH(ctx, "mesher.components.time", componentTrianglesKernel, dim3(divUp(divUp(nt, 64 * SIZE_SPAN), 4)), B,
-                   (const uint32_t *) m->triangles.ptr, (const uint32_t *) root, (const uint32_t *) denseOf, nt, tcount);
-        LAUNCH(ctx, "mesher.components.time", gatherSizesKernel, dim3(divUp(rootCount, 256)), B, (const uint32_t *) rootId,
-               (const uint32_t *) size, rootCount, vcount);
-        std::vector<uint32_t> hv(rootCount), ht(rootCount);
-        HIP_CHECK(hipMemcpyAsync(hv.data(), vcount, (size_t) rootCount * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipMemcpyAsync(ht.data(), tcount, (size_t) rootCount * 4, hipMemcpyDeviceToHost, ctx->stream));
-        uint32_t keyCount = 0;
-        if (ne > 0)
-        {
-            /* the distinct keys with their roots, into the sort's spare buffers */
-            uint64_t *keyOut = sorted.keys == keysA ? keysB : keysA;
-            uint32_t *rootOut = sorted.vals == slotsA ? slotsB : slotsA;
-            uint32_t *dKeyTotal, *keyTiles;
-            PROPAGATE(S.get(&dKeyTotal, 1));
-            PROPAGATE(S.get(&keyTiles, scanTiles(ne)));
-            PROPAGATE((exclusiveScan<uint32_t>(ctx, "mesher.weld.time", FirstOfRunIn{sorted.keys},
-                                               KeyRootOut{sorted.keys, sorted.vals, m->extGid.ptr, root, denseOf, keyOut, rootOut},
-                                               ne, 0u, keyTiles, dKeyTotal)));
-            HIP_CHECK(hipMemcpyAsync(&keyCount, dKeyTotal, 4, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            PROPAGATE(m->bKeys.resize(keyCount));
-            PROPAGATE(m->bKeyRoot.resize(keyCount));
-            HIP_CHECK(hipMemcpyAsync(m->bKeys.data(), keyOut, (size_t) keyCount * 8, hipMemcpyDeviceToHost, ctx->stream));
-            HIP_CHECK(hipMemcpyAsync(m->bKeyRoot.data(), rootOut, (size_t) keyCount * 4, hipMemcpyDeviceToHost, ctx->stream));
-        }
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        m->bRootVertices.assign(hv.begin(), hv.end());
-        m->bRootTriangles.assign(ht.begin(), ht.end());
-        m->cacheKind = 1;
-        m->cacheDims[0] = nv; m->cacheDims[1] = nt; m->cacheDims[2] = ne;
-        m->cacheRootCount = rootCount;
-        if (numChunks)
-            *numChunks = 0;
-        return MLSGPU_OK;
-    }
-    if (keepRoots != nullptr)
-    {
-        if (numRoots != rootCount || !m->analyzed || m->bRootVertices.size() != rootCount)
-            return setError(MLSGPU_ERR_LENGTH, "mesher: %llu verdicts for %u components (call boundary first, no add in between)",
-                            (unsigned long long) numRoots, rootCount);
-        uint8_t *dKeep;
-        PROPAGATE(S.get(&dKeep, rootCount));
-        HIP_CHECK(hipMemcpyAsync(dKeep, keepRoots, rootCount, hipMemcpyHostToDevice, ctx->stream));
-        LAUNCH(ctx, "mesher.components.time", applyVerdictKernel, dim3(divUp(rootCount, 256)), B, (const uint32_t *) rootId,
-               (const uint8_t *) dKeep, rootCount, size);
-    }
-
-    /* 3. prune threshold, src/mesher.cpp:498-527 */
-    unsigned long long *dStats;
-    PROPAGATE(S.get(&dStats, 4));
-    HIP_CHECK(hipMemsetAsync(dStats, 0, 32, ctx->stream));
-    const dim3 statsGrid((uint32_t) std::min<uint64_t>(divUp(nv, 256), 8192));
-    LAUNCH(ctx, "mesher.components.time", componentStatsKernel, statsGrid, B, (const uint32_t *) compRep,
-           (const uint32_t *) root, (const uint32_t *) size, nv, (uint64_t) 0, dStats, 0);
-    unsigned long long hStats[4];
-    uint32_t hFailed = 0;
-    HIP_CHECK(hipMemcpyAsync(hStats, dStats, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipMemcpyAsync(&hFailed, dFailed, 4, hipMemcpyDeviceToHost, ctx->stream));
+/* 2b. several meshers, one job: the roots numbered densely in vertex order (the union-find hooks larger roots under smaller
+ * ones, so a component's root is its smallest welded vertex whatever the schedule, and the numbering is reproducible) */
+int mlsgpu_mesher::numberRoots(const SinkScratch &L, const SinkSizes &z, uint32_t *rootCount)
+{
+    PROPAGATE((exclusiveScan<uint32_t>(ctx, "mesher.components.time", IsRootIn{L.compRep, L.root}, RootOut{L.rootId(), L.denseOf()},
+                                       z.nv, 0u, L.rootTiles, L.dRootTotal)));
+    HIP_CHECK(hipMemcpyAsync(rootCount, L.dRootTotal, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (hFailed != 0)
-        return setError(MLSGPU_ERR_HIP, "mesher: component union did not converge");
-    const uint64_t totalVertices = hStats[0];
-    /* with a verdict the "sizes" are all-or-nothing and the threshold is 1 */
-    const uint64_t threshold = keepRoots != nullptr ? 1 : (uint64_t) ((double) totalVertices * m->pruneThreshold);
-    LAUNCH(ctx, "mesher.components.time", componentStatsKernel, statsGrid, B, (const uint32_t *) compRep,
-           (const uint32_t *) root, (const uint32_t *) size, nv, threshold, dStats, 1);
+    return MLSGPU_OK;
+}
 
-    /* 4. output */
+/* vertices and triangles per root, in buffers of their own: representatives, roots and sizes stay intact for the verdict
+ * pass (finalize_with) that follows an export; then the distinct keys with their roots */
+int mlsgpu_mesher::exportBoundary(const SinkScratch &L, const SinkSizes &z, uint32_t rootCount)
+{
+    HIP_CHECK(hipMemsetAsync(L.tcount, 0, (size_t) rootCount * 4, ctx->stream));
+    if (rootCount <= FEW_COMPONENTS)
+        LAUNCH(ctx, "mesher.components.time", componentTrianglesFewKernel, dim3(divUp(divUp(z.nt, 64 * SIZE_SPAN), 4)), B,
+               (const uint32_t *) triangles.ptr, (const uint32_t *) L.root, (const uint32_t *) L.denseOf(), z.nt, rootCount, L.tcount);
+    else
+        LAUNCH(ctx, "mesher.components.time", componentTrianglesKernel, dim3(divUp(divUp(z.nt, 64 * SIZE_SPAN), 4)), B,
+               (const uint32_t *) triangles.ptr, (const uint32_t *) L.root, (const uint32_t *) L.denseOf(), z.nt, L.tcount);
+    LAUNCH(ctx, "mesher.components.time", gatherSizesKernel, dim3(divUp(rootCount, 256)), B, (const uint32_t *) L.rootId(),
+           (const uint32_t *) L.size, rootCount, L.vcount);
+    std::vector<uint32_t> hv(rootCount), ht(rootCount);
+    HIP_CHECK(hipMemcpyAsync(hv.data(), L.vcount, (size_t) rootCount * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(ht.data(), L.tcount, (size_t) rootCount * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (z.ne > 0)
+    {
+        uint32_t keyCount = 0;
+        const KeyRootOut out{L.sortedKeys(), L.sortedSlots(), extGid.ptr, L.root, L.denseOf(), L.keyOut(), L.rootOut()};
+        PROPAGATE((exclusiveScan<uint32_t>(ctx, "mesher.weld.time", FirstOfRunIn{L.sortedKeys()}, out, z.ne, 0u, L.keyTiles, L.dKeyTotal)));
+        HIP_CHECK(hipMemcpyAsync(&keyCount, L.dKeyTotal, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        PROPAGATE(bKeys.resize(keyCount));
+        PROPAGATE(bKeyRoot.resize(keyCount));
+        HIP_CHECK(hipMemcpyAsync(bKeys.data(), L.keyOut(), (size_t) keyCount * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(bKeyRoot.data(), L.rootOut(), (size_t) keyCount * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    bRootVertices.assign(hv.begin(), hv.end());
+    bRootTriangles.assign(ht.begin(), ht.end());
+    return MLSGPU_OK;
+}
+
+/* the caller's verdict per dense root (the numbering of the last export) over the component sizes: all or nothing */
+int mlsgpu_mesher::applyVerdict(const SinkScratch &L, uint32_t rootCount, const uint8_t *keepRoots, uint64_t numRoots)
+{
+    if (numRoots != rootCount || !analyzed || bRootVertices.size() != rootCount)
+        return setError(MLSGPU_ERR_LENGTH, "mesher: %llu verdicts for %u components (call boundary first, no add in between)",
+                        (unsigned long long) numRoots, rootCount);
+    HIP_CHECK(hipMemcpyAsync(L.dKeep, keepRoots, rootCount, hipMemcpyHostToDevice, ctx->stream));
+    LAUNCH(ctx, "mesher.components.time", applyVerdictKernel, dim3(divUp(rootCount, 256)), dim3(256), (const uint32_t *) L.rootId(),
+           (const uint8_t *) L.dKeep, rootCount, L.size);
+    return MLSGPU_OK;
+}
+
+/* 3. the prune threshold (src/mesher.cpp:498-527): a component stays with at least max(minSize, uint64(welded vertices *
+ * fraction)) vertices.  4. the output: two scans compact the kept vertices and triangles. */
+int mlsgpu_mesher::writeOutput(const SinkScratch &L, const SinkSizes &z, double fraction, uint64_t minSize)
+{
+    const auto [nv, nt, ne, nb, nc] = z;
+    HIP_CHECK(hipMemsetAsync(L.dStats, 0, 32, ctx->stream));
+    const dim3 statsGrid((uint32_t) std::min<uint64_t>(divUp(nv, 256), 8192));
+    LAUNCH(ctx, "mesher.components.time", componentStatsKernel, statsGrid, B, (const uint32_t *) L.compRep,
+           (const uint32_t *) L.root, (const uint32_t *) L.size, nv, (uint64_t) 0, L.dStats, 0);
+    unsigned long long hStats[4];
+    HIP_CHECK(hipMemcpyAsync(hStats, L.dStats, 8, hipMemcpyDeviceToHost, ctx->stream));
+    PROPAGATE(checkUnion(L));
+    const uint64_t totalVertices = hStats[0];
+    const uint64_t threshold = std::max(minSize, (uint64_t) ((double) totalVertices * fraction));
+    LAUNCH(ctx, "mesher.components.time", componentStatsKernel, statsGrid, B, (const uint32_t *) L.compRep,
+           (const uint32_t *) L.root, (const uint32_t *) L.size, nv, threshold, L.dStats, 1);
+
     std::vector<uint64_t> tBase(nb + 1), chunkFirstV(nc + 1), chunkFirstT(nc + 1);
     std::vector<uint32_t> vBase(nb + 1), chunkOf(nb);
     for (uint32_t b = 0; b < nb; b++)
     {
-        tBase[b] = m->blocks[b].tBase;
-        vBase[b] = m->blocks[b].vBase;
-        chunkOf[b] = (uint32_t) m->blocks[b].chunk;
+        tBase[b] = blocks[b].tBase;
+        vBase[b] = blocks[b].vBase;
+        chunkOf[b] = (uint32_t) blocks[b].chunk;
     }
     tBase[nb] = nt;
     vBase[nb] = (uint32_t) nv;
@@ -1113,89 +1099,69 @@ int mlsgpu_mesher::finalizeImpl(uint32_t *numChunks, bool analyzeOnly, const uin
         chunkFirstV[c] = b < nb ? vBase[b] : nv;
         chunkFirstT[c] = b < nb ? tBase[b] : nt;
     }
-    uint64_t *dTBase, *dAt;
-    uint32_t *dVBase, *dChunkOf, *dChunkVStart, *dChunkTStart, *dTotals, *tileSums;
-    PROPAGATE(S.get(&dTBase, nb + 1));
-    PROPAGATE(S.get(&dVBase, nb + 1));
-    PROPAGATE(S.get(&dChunkOf, nb));
-    PROPAGATE(S.get(&dChunkVStart, nc + 1));
-    PROPAGATE(S.get(&dChunkTStart, nc + 1));
-    PROPAGATE(S.get(&dAt, nc + 1));
-    PROPAGATE(S.get(&dTotals, 2));
-    PROPAGATE(S.get(&tileSums, scanTiles(std::max(nv, nt))));
-    HIP_CHECK(hipMemcpyAsync(dTBase, tBase.data(), (nb + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(hipMemcpyAsync(dVBase, vBase.data(), (nb + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_CHECK(hipMemcpyAsync(dChunkOf, chunkOf.data(), nb * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(L.dTBase, tBase.data(), (nb + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(L.dVBase, vBase.data(), (nb + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(L.dChunkOf, chunkOf.data(), nb * 4, hipMemcpyHostToDevice, ctx->stream));
 
     /* vertices: the scan's size is not known before it ran; the output is sized for every vertex and trimmed by count */
-    const KeepVertexIn keepV{outRep, root, size, threshold};
-    PROPAGATE((exclusiveScan<uint32_t>(ctx, "mesher.output.time", keepV, VertexOut{m->vertices.ptr, m->outVertices, vIndex},
-                                       nv, 0u, tileSums, dTotals)));
-    HIP_CHECK(hipMemcpyAsync(dAt, chunkFirstV.data(), (nc + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    LAUNCH(ctx, "mesher.output.time", gatherU32Kernel, dim3(divUp(nc + 1, 256)), B, (const uint32_t *) vIndex,
-           (const uint64_t *) dAt, nc + 1, nv, 0u, dChunkVStart);
+    const KeepVertexIn keepV{L.outRep, L.root, L.size, threshold};
+    PROPAGATE((exclusiveScan<uint32_t>(ctx, "mesher.output.time", keepV, VertexOut{vertices.ptr, outVertices, L.vIndex},
+                                       nv, 0u, L.tileSums, L.dTotals)));
+    HIP_CHECK(hipMemcpyAsync(L.dAt, chunkFirstV.data(), (nc + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    LAUNCH(ctx, "mesher.output.time", gatherU32Kernel, dim3(divUp(nc + 1, 256)), B, (const uint32_t *) L.vIndex,
+           (const uint64_t *) L.dAt, nc + 1, nv, 0u, L.dChunkVStart);
     /* the entry for "one past the last vertex" is the scan total */
     std::vector<uint32_t> hV(nc + 1), hT(nc + 1);
     uint32_t totals[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(hV.data(), dChunkVStart, (nc + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipMemcpyAsync(&totals[0], dTotals, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(hV.data(), L.dChunkVStart, (nc + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(&totals[0], L.dTotals, 4, hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (uint32_t c = 0; c <= nc; c++)
         if (chunkFirstV[c] >= nv)
             hV[c] = totals[0];
-    HIP_CHECK(hipMemcpyAsync(dChunkVStart, hV.data(), (nc + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(L.dChunkVStart, hV.data(), (nc + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
 
     /* triangles */
-    uint32_t *tIndex;
-    PROPAGATE(S.get(&tIndex, nt));
-    const BlockTable T{dTBase, dVBase, dChunkOf, dChunkVStart, nb};
-    const KeepTriangleIn keepT{m->triangles.ptr, root, size, threshold};
+    const BlockTable T{L.dTBase, L.dVBase, L.dChunkOf, L.dChunkVStart, nb};
+    const KeepTriangleIn keepT{triangles.ptr, L.root, L.size, threshold};
     PROPAGATE((exclusiveScan<uint32_t>(ctx, "mesher.output.time", keepT,
-                                       TriangleOutIdx{TriangleOut{m->triangles.ptr, outRep, vIndex, T, m->outTriangles}, tIndex},
-                                       nt, 0u, tileSums, dTotals + 1)));
-    HIP_CHECK(hipMemcpyAsync(dAt, chunkFirstT.data(), (nc + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    LAUNCH(ctx, "mesher.output.time", gatherU32Kernel, dim3(divUp(nc + 1, 256)), B, (const uint32_t *) tIndex,
-           (const uint64_t *) dAt, nc + 1, nt, 0u, dChunkTStart);
-    HIP_CHECK(hipMemcpyAsync(hT.data(), dChunkTStart, (nc + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipMemcpyAsync(&totals[1], dTotals + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_CHECK(hipMemcpyAsync(hStats, dStats, 32, hipMemcpyDeviceToHost, ctx->stream));
+                                       TriangleOutIdx{TriangleOut{triangles.ptr, L.outRep, L.vIndex, T, outTriangles}, L.tIndex},
+                                       nt, 0u, L.tileSums, L.dTotals + 1)));
+    HIP_CHECK(hipMemcpyAsync(L.dAt, chunkFirstT.data(), (nc + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    LAUNCH(ctx, "mesher.output.time", gatherU32Kernel, dim3(divUp(nc + 1, 256)), B, (const uint32_t *) L.tIndex,
+           (const uint64_t *) L.dAt, nc + 1, nt, 0u, L.dChunkTStart);
+    HIP_CHECK(hipMemcpyAsync(hT.data(), L.dChunkTStart, (nc + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(&totals[1], L.dTotals + 1, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipMemcpyAsync(hStats, L.dStats, 32, hipMemcpyDeviceToHost, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (uint32_t c = 0; c <= nc; c++)
     {
-        if (chunkFirstT[c] >= nt)
-            hT[c] = totals[1];
-        m->chunkVStart[c] = hV[c];
-        m->chunkTStart[c] = hT[c];
+        chunkVStart[c] = hV[c];
+        chunkTStart[c] = chunkFirstT[c] >= nt ? totals[1] : hT[c];
     }
     for (uint32_t c = 0; c < nc; c++)
-        if (m->chunkTStart[c + 1] > m->chunkTStart[c])      /* no output for a chunk without triangles, :820 */
-            m->outChunks.push_back(c);
-    m->stats[0] = totalVertices;
-    m->stats[1] = threshold;
-    m->stats[2] = hStats[1];
-    m->stats[3] = hStats[2];
-    m->stats[4] = hStats[3];
-    if (keepRoots != nullptr)
-    {
-        /* this mesher's own part of the job: kept components and their welded vertices from the export */
-        m->stats[4] = 0;
-        for (uint64_t r = 0; r < numRoots; r++)
-            if (keepRoots[r])
-                m->stats[4] += m->bRootVertices[r];
-    }
-    m->stats[5] = totals[1];
-    m->stats[6] = nv;
-    m->stats[7] = nt;
-    if (keepRoots == nullptr)
-    {
-        /* the weld and the components stay in the slab for an export that may follow (boundary) */
-        m->cacheKind = 2;
-        m->cacheDims[0] = nv; m->cacheDims[1] = nt; m->cacheDims[2] = ne;
-    }
-    m->finalized = true;
-    if (numChunks)
-        *numChunks = (uint32_t) m->outChunks.size();
+        if (chunkTStart[c + 1] > chunkTStart[c])      /* no output for a chunk without triangles, :820 */
+            outChunks.push_back(c);
+    const uint64_t all[8] = {totalVertices, threshold, hStats[1], hStats[2], hStats[3], totals[1], nv, nt};
+    std::copy(all, all + 8, stats);
     return MLSGPU_OK;
+}
+
+/* MesherBase::write's finalisation (src/mesher.cpp:763-852) up to the point where files are written */
+MLSGPU_API int mlsgpu_hip_mesher_finalize(mlsgpu_mesher *m, uint32_t *numChunks)
+{
+    REQUIRE(m != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    SinkSizes z;
+    SinkScratch L;
+    SinkCache had;
+    PROPAGATE(m->begin(z, L, had));
+    if (z.empty())
+        return m->finish(numChunks);
+    PROPAGATE(m->analyse(L, z, false));
+    PROPAGATE(m->writeOutput(L, z, m->pruneThreshold, 0));
+    m->cache = SinkCache{SinkCache::AfterFinalize, L.sortedInA, z.nv, z.nt, z.ne, 0};
+    return m->finish(numChunks);
 }
 
 MLSGPU_API int mlsgpu_hip_mesher_chunk(mlsgpu_mesher *m, uint32_t i, uint64_t *chunkId, uint64_t *numVertices,
@@ -1203,12 +1169,12 @@ MLSGPU_API int mlsgpu_hip_mesher_chunk(mlsgpu_mesher *m, uint32_t i, uint64_t *c
 {
     REQUIRE(m != nullptr, MLSGPU_ERR_INVALID);
     REQUIRE(m->finalized && i < m->outChunks.size(), MLSGPU_ERR_INVALID);
-    const uint32_t c = m->outChunks[i];
-    if (chunkId) *chunkId = m->chunkIds[c];
-    if (numVertices) *numVertices = m->chunkVStart[c + 1] - m->chunkVStart[c];
-    if (numTriangles) *numTriangles = m->chunkTStart[c + 1] - m->chunkTStart[c];
-    if (dVertices) *dVertices = m->outVertices + 3 * m->chunkVStart[c];
-    if (dTriangles) *dTriangles = m->outTriangles + 3 * m->chunkTStart[c];
+    const mlsgpu_mesher::Span s = m->span(m->outChunks[i]);
+    if (chunkId) *chunkId = m->chunkIds[m->outChunks[i]];
+    if (numVertices) *numVertices = s.nv;
+    if (numTriangles) *numTriangles = s.nt;
+    if (dVertices) *dVertices = m->outVertices + 3 * s.v0;
+    if (dTriangles) *dTriangles = m->outTriangles + 3 * s.t0;
     return MLSGPU_OK;
 }
 
@@ -1218,9 +1184,8 @@ MLSGPU_API int mlsgpu_hip_mesher_chunk_topology(mlsgpu_mesher *m, uint32_t i, ml
     REQUIRE(m != nullptr && out != nullptr, MLSGPU_ERR_INVALID);
     std::lock_guard<std::mutex> lock(m->mutex);
     REQUIRE(m->finalized && i < m->outChunks.size(), MLSGPU_ERR_INVALID);
-    const uint32_t c = m->outChunks[i];
-    return mlsgpu_hip_mesh_topology(m->ctx, m->outTriangles + 3 * m->chunkTStart[c], m->chunkTStart[c + 1] - m->chunkTStart[c],
-                                    m->chunkVStart[c + 1] - m->chunkVStart[c], out);
+    const mlsgpu_mesher::Span s = m->span(m->outChunks[i]);
+    return mlsgpu_hip_mesh_topology(m->ctx, m->outTriangles + 3 * s.t0, s.nt, s.nv, out);
 }
 
 /* Every output chunk through mlsgpu_hip_mesh_simplify (simplify.hip), into buffers of the chunk's size and from there to the
@@ -1239,8 +1204,8 @@ MLSGPU_API int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *m, const float origin[3
     uint64_t maxV = 0, maxT = 0;
     for (size_t c = 0; c < nc; c++)
     {
-        maxV = std::max(maxV, m->chunkVStart[c + 1] - m->chunkVStart[c]);
-        maxT = std::max(maxT, m->chunkTStart[c + 1] - m->chunkTStart[c]);
+        maxV = std::max(maxV, m->span(c).nv);
+        maxT = std::max(maxT, m->span(c).nt);
     }
     DeviceArray<float> tmpV;
     DeviceArray<uint32_t> tmpT;
@@ -1249,8 +1214,7 @@ MLSGPU_API int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *m, const float origin[3
     uint64_t vAt = 0, tAt = 0;
     for (size_t c = 0; c < nc; c++)
     {
-        const uint64_t v0 = m->chunkVStart[c], t0 = m->chunkTStart[c];
-        const uint64_t nv = m->chunkVStart[c + 1] - v0, nt = m->chunkTStart[c + 1] - t0;
+        const auto [v0, t0, nv, nt] = m->span(c);
         mlsgpu_simplify_stats one;
         std::memset(&one, 0, sizeof(one));
         int rc = MLSGPU_OK;
@@ -1303,8 +1267,7 @@ MLSGPU_API int mlsgpu_hip_mesher_smooth(mlsgpu_mesher *m, uint32_t iterations, f
     bool first = true;
     for (size_t c = 0; c < nc; c++)
     {
-        const uint64_t v0 = m->chunkVStart[c], t0 = m->chunkTStart[c];
-        const uint64_t nv = m->chunkVStart[c + 1] - v0, nt = m->chunkTStart[c + 1] - t0;
+        const auto [v0, t0, nv, nt] = m->span(c);
         if (nt == 0)
             continue;           /* a chunk without triangles has no output (finalize) */
         mlsgpu_smooth_stats one;
@@ -1357,8 +1320,7 @@ MLSGPU_API int mlsgpu_hip_mesher_fill_holes(mlsgpu_mesher *m, uint32_t maxEdges,
     std::vector<uint64_t> vStart(nc + 1, 0), tStart(nc + 1, 0);
     for (size_t c = 0; c < nc; c++)
     {
-        const uint64_t v0 = m->chunkVStart[c], t0 = m->chunkTStart[c];
-        const uint64_t nv = m->chunkVStart[c + 1] - v0, nt = m->chunkTStart[c + 1] - t0;
+        const auto [v0, t0, nv, nt] = m->span(c);
         std::memset(&one[c], 0, sizeof(one[c]));
         if (nt > 0)     /* a chunk without triangles has no output (finalize), and keeps none */
         {
@@ -1378,8 +1340,7 @@ MLSGPU_API int mlsgpu_hip_mesher_fill_holes(mlsgpu_mesher *m, uint32_t maxEdges,
     bool first = true;
     for (size_t c = 0; c < nc; c++)
     {
-        const uint64_t v0 = m->chunkVStart[c], t0 = m->chunkTStart[c];
-        const uint64_t nv = m->chunkVStart[c + 1] - v0, nt = m->chunkTStart[c + 1] - t0;
+        const auto [v0, t0, nv, nt] = m->span(c);
         if (nt == 0)
             continue;
         PROPAGATE(mlsgpu_hip_mesh_fill_holes(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, maxEdges,
@@ -1429,14 +1390,14 @@ int mlsgpu_mesher::chunkNormals(uint32_t c, const float **dNormals, mlsgpu_norma
         normalsReady.assign(nc, 0);
         normalsOf.assign(nc, mlsgpu_normals_stats());
     }
-    const uint64_t v0 = chunkVStart[c], t0 = chunkTStart[c];
+    const Span s = span(c);
     if (!normalsReady[c])
     {
-        PROPAGATE(mlsgpu_hip_mesh_normals(ctx, outVertices + 3 * v0, chunkVStart[c + 1] - v0, outTriangles + 3 * t0,
-                                          chunkTStart[c + 1] - t0, outNormals + 3 * v0, &normalsOf[c]));
+        PROPAGATE(mlsgpu_hip_mesh_normals(ctx, outVertices + 3 * s.v0, s.nv, outTriangles + 3 * s.t0, s.nt, outNormals + 3 * s.v0,
+                                          &normalsOf[c]));
         normalsReady[c] = 1;
     }
-    if (dNormals) *dNormals = outNormals + 3 * v0;
+    if (dNormals) *dNormals = outNormals + 3 * s.v0;
     if (out) *out = normalsOf[c];
     return MLSGPU_OK;
 }
@@ -1461,7 +1422,25 @@ MLSGPU_API int mlsgpu_hip_mesher_boundary(mlsgpu_mesher *m, uint64_t *numKeys, u
 {
     REQUIRE(m != nullptr && numKeys != nullptr && numRoots != nullptr, MLSGPU_ERR_INVALID);
     std::lock_guard<std::mutex> lock(m->mutex);
-    PROPAGATE(m->finalizeImpl(nullptr, true, nullptr, 0));
+    m->bKeys.clear();
+    m->bKeyRoot.clear();
+    m->bRootVertices.clear();
+    m->bRootTriangles.clear();
+    m->analyzed = true;
+    SinkSizes z;
+    SinkScratch L;
+    SinkCache had;
+    PROPAGATE(m->begin(z, L, had));
+    if (!z.empty())
+    {
+        /* behind an export or a plain finalize over the same arenas, the weld and the components are in the slab */
+        uint32_t rootCount = 0;
+        PROPAGATE(m->analyse(L, z, had.kind != SinkCache::None));
+        PROPAGATE(m->numberRoots(L, z, &rootCount));
+        PROPAGATE(m->checkUnion(L));
+        PROPAGATE(m->exportBoundary(L, z, rootCount));
+        m->cache = SinkCache{SinkCache::AfterExport, L.sortedInA, z.nv, z.nt, z.ne, rootCount};
+    }
     *numKeys = m->bKeys.size();
     *numRoots = m->bRootVertices.size();
     return MLSGPU_OK;
@@ -1487,8 +1466,26 @@ MLSGPU_API int mlsgpu_hip_mesher_finalize_with(mlsgpu_mesher *m, const uint8_t *
     REQUIRE(m != nullptr && (numRoots == 0 || keepRoot != nullptr), MLSGPU_ERR_INVALID);
     std::lock_guard<std::mutex> lock(m->mutex);
     REQUIRE(m->analyzed, MLSGPU_ERR_INVALID);
-    static const uint8_t none = 0;
-    return m->finalizeImpl(numChunks, false, numRoots ? keepRoot : &none, numRoots);
+    SinkSizes z;
+    SinkScratch L;
+    SinkCache had;
+    PROPAGATE(m->begin(z, L, had));
+    if (z.empty())
+        return m->finish(numChunks);
+    /* right behind an export, weld, components and root numbering are still in the slab; this call leaves no record */
+    const bool cached = had.kind == SinkCache::AfterExport;
+    uint32_t rootCount = had.rootCount;
+    PROPAGATE(m->analyse(L, z, cached));
+    if (!cached)
+        PROPAGATE(m->numberRoots(L, z, &rootCount));
+    PROPAGATE(m->applyVerdict(L, rootCount, keepRoot, numRoots));
+    PROPAGATE(m->writeOutput(L, z, 0.0, 1));        /* the "sizes" are all or nothing now */
+    /* this mesher's own part of the job: kept components and their welded vertices from the export */
+    m->stats[4] = 0;
+    for (uint64_t r = 0; r < numRoots; r++)
+        if (keepRoot[r])
+            m->stats[4] += m->bRootVertices[r];
+    return m->finish(numChunks);
 }
 
 namespace
@@ -1570,9 +1567,9 @@ int writeChunkPly(mlsgpu_mesher *m, uint32_t i, const char *path, const char *co
     if (withNormals)
         PROPAGATE(m->chunkNormals(c, &dN, nullptr));
     const uint64_t rowBytes = withNormals ? 24 : 12;
-    const uint64_t nv = m->chunkVStart[c + 1] - m->chunkVStart[c], nt = m->chunkTStart[c + 1] - m->chunkTStart[c];
-    const uint8_t *dV = reinterpret_cast<const uint8_t *>(m->outVertices + 3 * (uint64_t) m->chunkVStart[c]);
-    const uint32_t *dT = m->outTriangles + 3 * (uint64_t) m->chunkTStart[c];
+    const uint64_t nv = m->span(c).nv, nt = m->span(c).nt;
+    const uint8_t *dV = reinterpret_cast<const uint8_t *>(m->outVertices + 3 * m->span(c).v0);
+    const uint32_t *dT = m->outTriangles + 3 * m->span(c).t0;
     if (bufferBytes == 0)
         bufferBytes = uint64_t(64) << 20;
     /* a piece holds whole 12-byte (with normals 24-byte) vertices and whole 13-byte faces */

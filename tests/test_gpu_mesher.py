@@ -284,6 +284,46 @@ def test_boundary_after_finalize_reuses_the_analysis(seed, prune):
     ctx.close()
 
 
+def test_scratch_layout_depends_on_the_sizes_alone():
+    """Where an array of the sink's scratch lies depends on the job's sizes, not on the calls before or on how large the slab
+    is: boundary() -> finalize_with() gives the same export element for element and the same chunks bit for bit (the output
+    order is deterministic) in a fresh sink, in one whose reserve() made the slab far larger than the layout, and in one
+    whose boundary() starts from what a plain finalize() left.  Strip sheets of about 3 000 vertices, two chunks that share
+    keys."""
+    import mlsgpu_amd as m
+    meshes = random_meshes(8, blocks=12, chunks=2)
+    assert sum(len(mesh["vertices"]) for mesh in meshes) > 3000
+    assert set(meshes[5]["keys"]) & set(meshes[6]["keys"]) and meshes[5]["chunk"] != meshes[6]["chunk"]
+    ctx = m.Context(0)
+
+    def run(reserve=False, finalize_first=False):
+        sink = m.Mesher(ctx, 0.02)
+        if reserve:
+            sink.reserve(1 << 20, 1 << 21, 1 << 18)             # the job: 3 360 vertices at the most
+        seen = {}
+        for mesh in meshes:
+            sink.add(chunk_number(mesh["chunk"], seen), mesh["vertices"], mesh["num_internal"], mesh["keys"], mesh["triangles"])
+        if finalize_first:
+            assert sink.finalize() == 2
+        boundary = sink.boundary()
+        keep = (boundary[2] >= 3).astype(np.uint8)              # some verdict: components of at least three vertices
+        chunks = [sink.chunk(i) for i in range(sink.finalize_with(keep))]
+        sink.close()
+        return boundary, keep, chunks
+
+    exp_boundary, exp_keep, exp_chunks = run()
+    assert len(exp_boundary[0]) > 0 and 0 < exp_keep.sum() and len(exp_chunks) == 2
+    for kwargs in (dict(reserve=True), dict(finalize_first=True)):
+        boundary, _, chunks = run(**kwargs)
+        for a, b in zip(exp_boundary, boundary):
+            np.testing.assert_array_equal(a, b)
+        assert [c["chunk"] for c in chunks] == [c["chunk"] for c in exp_chunks]
+        for e, g in zip(exp_chunks, chunks):
+            np.testing.assert_array_equal(e["vertices"].view(np.uint32), g["vertices"].view(np.uint32))
+            np.testing.assert_array_equal(e["triangles"], g["triangles"])
+    ctx.close()
+
+
 def test_one_sink_regrows_between_jobs():
     """Jobs of very different sizes through ONE sink, reset() in between: a small one, one large enough that the slab, both
     outputs and the arenas are reallocated while the sink holds the small job's buffers, and the small one again in the
