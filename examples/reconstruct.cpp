@@ -12,7 +12,7 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N] [--repair [pinches]] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
  * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
@@ -21,6 +21,10 @@
  *   and --normals; the loops on a seam between two chunks stay open; one line with the statistics.
  * --simplify N (device weld only, N > 0): before the write, every output chunk is vertex-clustered where it lies, in cells of
  *   N grid spacings counted from one cell below the bounding grid's low corner; one line with the statistics.
+ * --repair, --repair pinches (device weld only): before the write, every output chunk is repaired where it lies: triangles
+ *   with a repeated directed side are dropped and pinched vertices split (with `pinches`: every umbrella of a vertex becomes a
+ *   vertex of its own), so that --check says `manifold yes` -- after --simplify, which can make a chunk non-manifold, and
+ *   before --smooth, --normals and --check; one line with the statistics.
  * --smooth N (device weld only, N > 0): before the write, every output chunk gets N Taubin iterations (lambda 0.5, mu -0.53)
  *   where it lies, the vertices on a chunk's boundary held fixed -- after --simplify when both are given; one line with the
  *   statistics.
@@ -46,7 +50,8 @@ int main(int argc, char **argv)
     bool hostWeld = false, checkTopology = false, writeNormals = false;
     std::uint64_t bufferBytes = 0, hbmSplats = 0;
     float simplifyCells = 0.0f;
-    bool simplifyGiven = false, smoothGiven = false, fillGiven = false;
+    bool simplifyGiven = false, smoothGiven = false, fillGiven = false, repairGiven = false;
+    std::uint32_t repairFlags = 0;
     long smoothIterations = 0, fillEdges = 0;
     std::string tmpDir;
     std::vector<std::string> plys, rest;
@@ -82,6 +87,15 @@ int main(int argc, char **argv)
             fillEdges = atol(argv[++i]);
             fillGiven = true;
         }
+        else if (a == "--repair")
+        {
+            repairGiven = true;
+            if (i + 1 < argc && std::string(argv[i + 1]) == "pinches")
+            {
+                repairFlags = MLSGPU_REPAIR_SPLIT_PINCHES;
+                i++;
+            }
+        }
         else if (a == "--buffer" && i + 1 < argc)
             bufferBytes = strtoull(argv[++i], NULL, 10);
         else if (a == "--tmp-dir" && i + 1 < argc)             // --weld host: the welder's blocks in temporary files there (src/mlsgpu_core.cpp --tmp-dir)
@@ -95,7 +109,7 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N] [--repair [pinches]] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
         return 2;
     }
@@ -127,6 +141,11 @@ int main(int argc, char **argv)
     if (fillGiven && hostWeld)
     {
         std::cerr << "--fill-holes needs --weld device: the host welder's output is not on the device\n";
+        return 2;
+    }
+    if (repairGiven && hostWeld)
+    {
+        std::cerr << "--repair needs --weld device: the host welder's output is not on the device\n";
         return 2;
     }
     if (writeNormals && hostWeld)
@@ -198,6 +217,8 @@ int main(int argc, char **argv)
         std::size_t smoothedChunks = 0;
         mlsgpu_fill_stats filled = mlsgpu_fill_stats();
         std::size_t filledChunks = 0;
+        mlsgpu_repair_stats repaired = mlsgpu_repair_stats();
+        std::size_t repairedChunks = 0;
         {
             BucketFarm farm(devices, cfg, 4 /* --device-threads */, 1, hostWeld ? NULL : &deviceMesher);
             if (hostWeld)
@@ -240,6 +261,11 @@ int main(int argc, char **argv)
                     simplifyOrigin[i] = cfg.gridOrigin[i] - simplifyCell;
                 simplified = deviceMesher.simplify(simplifyOrigin, simplifyCell);
             }
+            if (repairGiven)
+            {
+                repaired = deviceMesher.repair(repairFlags);
+                repairedChunks = chunks;
+            }
             if (smoothGiven)
             {
                 smoothed = deviceMesher.smooth((std::uint32_t) smoothIterations, 0.5f, -0.53f, MLSGPU_SMOOTH_BOUNDARY_FIXED);
@@ -269,6 +295,14 @@ int main(int argc, char **argv)
                         (unsigned long long) simplified.inVertices, (unsigned long long) simplified.outVertices,
                         (unsigned long long) simplified.inTriangles, (unsigned long long) simplified.outTriangles,
                         (unsigned long long) simplified.collapsedTriangles, (unsigned long long) simplified.duplicateTriangles);
+        if (repairGiven)
+            std::printf("repair chunks %zu out-of-range %llu degenerate %llu repeated-sides %llu dropped %llu unused %llu split %llu "
+                        "vertices %llu -> %llu triangles %llu -> %llu\n",
+                        repairedChunks, (unsigned long long) repaired.outOfRangeTriangles, (unsigned long long) repaired.degenerateTriangles,
+                        (unsigned long long) repaired.repeatedSides, (unsigned long long) repaired.droppedTriangles,
+                        (unsigned long long) repaired.unusedVertices, (unsigned long long) repaired.splitVertices,
+                        (unsigned long long) repaired.numVertices, (unsigned long long) repaired.outVertices,
+                        (unsigned long long) repaired.numTriangles, (unsigned long long) repaired.outTriangles);
         if (smoothGiven)
             std::printf("smooth chunks %zu vertices %llu edges %llu boundary-vertices %llu isolated %llu passes %llu max-move %.9g\n",
                         smoothedChunks, (unsigned long long) smoothed.numVertices, (unsigned long long) smoothed.numEdges,

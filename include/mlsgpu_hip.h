@@ -674,7 +674,8 @@ uint64_t mlsgpu_hip_topology_reason(const mlsgpu_topology *t, char *buf, uint64_
  *         (first, second, third) and of a run of equal triples one is kept -- (a, b, c) and (a, c, b) both stay.
  *      5. The output vertices are the clusters a kept triangle uses, numbered densely in key order; clusters nothing uses
  *         (and input vertices no triangle used) disappear.
- *      Clustering can make a mesh non-manifold: mlsgpu_hip_mesh_topology says whether it did. ---- */
+ *      Clustering can make a mesh non-manifold: mlsgpu_hip_mesh_topology says whether it did, and mlsgpu_hip_mesh_repair
+ *      makes it manifold again. ---- */
 typedef struct mlsgpu_simplify_stats
 {
     uint64_t inVertices, inTriangles;
@@ -929,6 +930,92 @@ int mlsgpu_hip_mesh_fill_holes(mlsgpu_ctx *ctx, const float *dVertices, uint64_t
  * outside its range; may be called again (on the filled chunks).  The new arrays take the old ones' place only when every chunk
  * is done: an error leaves the sink's results as they were. */
 int mlsgpu_hip_mesher_fill_holes(mlsgpu_mesher *mesher, uint32_t maxEdges, mlsgpu_fill_stats *stats);
+
+/* ---- repair of a device-resident mesh: triangles with a repeated directed side are dropped and pinched vertices are split,
+ *      so that a mesh which mlsgpu_hip_mesh_topology calls non-manifold (a simplify can make one) is an oriented manifold
+ *      with boundary again before it crosses the link -- what the reference guarantees for everything it writes
+ *      (Manifold::isManifold, test/manifold.h:98-232).  Every result is a count, a minimum or a scan: the output depends
+ *      neither on the schedule nor, beyond step 6, on the order of the triangles.
+ *      1. A triangle with an index >= V is counted in outOfRangeTriangles (the index is compared, never used as an address);
+ *         otherwise a triangle with two equal indices is counted in degenerateTriangles -- the rule of the smoothing and the
+ *         hole filling, not the topology report's rotation order.  Both kinds are dropped.
+ *      2. Every other triangle (a, b, c) gives the directed sides a -> b, b -> c, c -> a.  A directed side that occurs more
+ *         than once is REPEATED; repeatedSides counts the occurrences of repeated sides.  Every triangle with a repeated side
+ *         is dropped (droppedTriangles) -- all of them, not all but one, so that the result does not depend on the triangles'
+ *         order.  An undirected edge of three or more triangles always has a repeated direction, so every edge of the KEPT
+ *         triangles has at most two of them, with opposite winding.  Dropping only removes sides: one pass suffices.
+ *      3. Among the kept triangles, two corners at one vertex v belong together when one triangle has v -> w and the other
+ *         w -> v; the transitive closure gives v's UMBRELLAS.  An umbrella is a RING if every side at v in it has its
+ *         opposite among the kept triangles, else a CHAIN.
+ *      4. Without flags a vertex is split only where the reference's check fails: where it has at least one ring and more
+ *         than one umbrella (MIXED or TUNNEL of the topology report).  Each ring is a GROUP of its own then and all chains
+ *         together are one group; every other vertex is one group (the reference allows a vertex on several boundary runs).
+ *         Under MLSGPU_REPAIR_SPLIT_PINCHES every umbrella is a group of its own: a topological 2-manifold with boundary,
+ *         whose boundary vertices are all regular for the hole filling.
+ *      5. A group's key is the smallest `to` over its sides v -> to; the kept sides are unique, so the keys of a vertex
+ *         differ.  The output vertices are the groups, numbered densely in ascending (v, key) order; each carries v's 12
+ *         position bytes bit for bit.  A vertex that no kept triangle uses disappears (unusedVertices): the reference calls
+ *         an isolated vertex non-manifold.  splitVertices counts the input vertices with more than one group, addedVertices
+ *         the groups beyond each vertex's first: outVertices = numVertices - unusedVertices + addedVertices.
+ *      6. The output triangles are the kept triangles in the input's order, every corner mapped to its group:
+ *         outTriangles = numTriangles - outOfRangeTriangles - degenerateTriangles - droppedTriangles.
+ *      The topology report of the output has all six counts zero whenever the input has a kept triangle or V = 0 (with
+ *      vertices and nothing kept the output is empty).  An input that the report calls manifold comes back bit for bit
+ *      without flags.  Permuting the triangles permutes only the output triangles; renumbering the vertices leaves the
+ *      output the same as a set of triangles over position triples.  Repairing a repaired mesh changes nothing.
+ *      Out of scope: the holes that dropped triangles leave are not re-triangulated (mlsgpu_hip_mesh_fill_holes does). ---- */
+#define MLSGPU_REPAIR_SPLIT_PINCHES 1u
+typedef struct mlsgpu_repair_stats
+{
+    uint64_t numVertices, numTriangles;
+    uint64_t outOfRangeTriangles;   /* an index >= numVertices */
+    uint64_t degenerateTriangles;   /* in range, two indices equal */
+    uint64_t repeatedSides;         /* step 2: side records in runs longer than one */
+    uint64_t droppedTriangles;      /* step 2: triangles with such a side */
+    uint64_t unusedVertices;        /* on no kept triangle */
+    uint64_t splitVertices;         /* input vertices with more than one group */
+    uint64_t addedVertices;         /* groups beyond the first of their vertex */
+    uint64_t outVertices;           /* numVertices - unusedVertices + addedVertices */
+    uint64_t outTriangles;          /* numTriangles - outOfRangeTriangles - degenerateTriangles - droppedTriangles */
+} mlsgpu_repair_stats;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_repair_stats) == 88, "mlsgpu_repair_stats is part of the ABI");
+#else
+typedef char mlsgpu_repair_stats_size_is_88[sizeof(mlsgpu_repair_stats) == 88 ? 1 : -1];
+#endif
+/* numVertices packed float xyz and numTriangles uint32 index triples on ctx's device -> dOutVertices with room for
+ * capVertices vertices and dOutTriangles with room for capTriangles triangles, which must not overlap the inputs.  dOutSource
+ * is NULL or has room for capVertices uint32: it receives the input index of every output vertex, so that a caller can carry
+ * attributes along.  MLSGPU_ERR_INVALID, before anything touches the device, for a NULL ctx or stats and for a flag bit other
+ * than MLSGPU_REPAIR_SPLIT_PINCHES; MLSGPU_ERR_LENGTH, before anything is allocated, unless numVertices < 2^32 and
+ * 3 * numTriangles < 2^32.  MLSGPU_ERR_LENGTH if capVertices < outVertices or capTriangles < outTriangles: *stats is complete
+ * then and the outputs are untouched, which is how a caller asks for the sizes -- NULL outputs with zero capacities (a result
+ * that is empty fits them, and the call returns MLSGPU_OK).  Positions are copied, never computed with: a coordinate that is
+ * not finite is not an error.  No vertices or no triangles is not an error.  Scratch is allocated for the call and freed on
+ * return: 97 bytes per triangle (three directed side records: the two sides of the sort's 64-bit keys and 32-bit values, of
+ * which the side the sort leaves free holds the umbrellas' keys, the groups' numbers and the records' flags; the corner
+ * forest's parent 12, the chain flags 12, the triangle's state 1), 24 bytes per vertex (its segment's start and end, ring and
+ * chain count, smallest chain key, smallest key), the sort's histogram and the scan's tile sums; MLSGPU_ERR_NOMEM if the
+ * device does not have it.  Blocks until the statistics are there: one stream synchronisation behind the counts (they size
+ * the result), and, if the capacities suffice and the result is not empty, one at the end. */
+int mlsgpu_hip_mesh_repair(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices, const uint32_t *dTriangles,
+                           uint64_t numTriangles, uint32_t flags, float *dOutVertices, uint64_t capVertices,
+                           uint32_t *dOutTriangles, uint64_t capTriangles, uint32_t *dOutSource, mlsgpu_repair_stats *stats);
+/* The same for every output chunk of a finalized device sink that has triangles, on the mesher's context.  A chunk can GROW
+ * in vertices, so the route is that of mlsgpu_hip_mesher_fill_holes: every chunk is sized once and then written once into new
+ * output arrays of the summed sizes, each repaired chunk behind the one before, and the new generation takes the old one's
+ * place only when every chunk is done -- an error leaves the sink's results as they were.  While both generations exist the
+ * sink holds 12 bytes per vertex and per triangle of the old AND of the new meshes, plus one chunk's scratch as above.  The
+ * chunks' normals are dropped, so normals requested afterwards are those of the repaired chunk.  Chunks without triangles, and
+ * chunks that keep none, stay in the list, empty; mlsgpu_hip_mesher_chunk, _chunk_topology, _chunk_normals and _write_ply
+ * then serve the repaired chunks, _simplify, _smooth and _fill_holes work on them, a finalize brings the originals back, and
+ * mlsgpu_hip_mesher_stats keeps reporting the finalize's numbers.  *stats is the sum over the chunks.
+ * SEAMS: chunks are repaired INDEPENDENTLY, as for simplify and normals.  A vertex two chunks share is split, or not, by
+ * each chunk's own triangles; every copy keeps the position bits, so the seam stays closed geometrically and the hole
+ * filling's seam matching (equal position bits in another chunk) still sees it.
+ * MLSGPU_ERR_INVALID before finalize and for an unknown flag bit; may be called again (on the repaired chunks, which it
+ * leaves as they are). */
+int mlsgpu_hip_mesher_repair(mlsgpu_mesher *mesher, uint32_t flags, mlsgpu_repair_stats *stats);
 
 /* ---- host mesh sink: OOCMesher's weld as the reference runs it, on the host (src/mesher.cpp:220-469, north_star:
  *      "welding stays on host").  add() is MesherBase::InputFunctor: local components of the block by union-find over

@@ -166,6 +166,22 @@ class FillStats(C.Structure):
         return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
 
 
+class RepairStats(C.Structure):
+    """mlsgpu_repair_stats: what took no part, the repeated sides and the triangles dropped for them, the vertices that went,
+    split and came, the sizes of the result."""
+    _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
+                ("degenerateTriangles", C.c_uint64), ("repeatedSides", C.c_uint64), ("droppedTriangles", C.c_uint64),
+                ("unusedVertices", C.c_uint64), ("splitVertices", C.c_uint64), ("addedVertices", C.c_uint64),
+                ("outVertices", C.c_uint64), ("outTriangles", C.c_uint64)]
+
+    def as_dict(self):
+        return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
+
+
+# MLSGPU_REPAIR_SPLIT_PINCHES: every umbrella of a vertex becomes a vertex of its own
+REPAIR_SPLIT_PINCHES = 1
+
+
 # MLSGPU_FILL_MAX_EDGES: the longest loop that max_edges may admit
 FILL_MAX_EDGES = 1 << 20
 
@@ -375,6 +391,8 @@ def lib():
     sig("mlsgpu_hip_mesher_smooth", C.c_int, vp, u32, C.c_float, C.c_float, u32, P(SmoothStats))
     sig("mlsgpu_hip_mesh_fill_holes", C.c_int, vp, vp, u64, vp, u64, u32, vp, vp, u64, vp, u64, P(FillStats))
     sig("mlsgpu_hip_mesher_fill_holes", C.c_int, vp, u32, P(FillStats))
+    sig("mlsgpu_hip_mesh_repair", C.c_int, vp, vp, u64, vp, u64, u32, vp, u64, vp, u64, vp, P(RepairStats))
+    sig("mlsgpu_hip_mesher_repair", C.c_int, vp, u32, P(RepairStats))
     sig("mlsgpu_hip_write_ply_normals", C.c_int, C.c_char_p, vp, vp, u64, vp, u64, vp, u32)
     sig("mlsgpu_hip_mesher_write_ply_normals", C.c_int, vp, C.c_uint32, C.c_char_p, vp, C.c_uint32, u64)
     sig("mlsgpu_hip_bucket", C.c_int, vp, vp, u64, P(GridStruct), P(BucketParams), BUCKET_FN, vp, P(u64))
@@ -924,6 +942,15 @@ class Mesher:
         check(lib().mlsgpu_hip_mesher_fill_holes(self.h, int(max_edges), C.byref(st)))
         return st.as_dict()
 
+    def repair(self, flags=0):
+        """Every output chunk of the finalized sink repaired (mesh_repair): triangles with a repeated directed side dropped,
+        pinched vertices split (flags: 0 or REPAIR_SPLIT_PINCHES), so that chunk_topology() calls the chunks manifold again,
+        after a simplify for instance.  The chunks move into new arrays: addresses from an earlier chunk() are gone.  Returns
+        the statistics summed over the chunks."""
+        st = RepairStats()
+        check(lib().mlsgpu_hip_mesher_repair(self.h, int(flags), C.byref(st)))
+        return st.as_dict()
+
     def write_ply(self, i, path, comments=(), buffer_bytes=0):
         """Output chunk i straight from HBM into FastPly::Writer's file through a bounded pinned buffer."""
         arr = (C.c_char_p * max(len(comments), 1))(*[c.encode("ascii") for c in comments])
@@ -1133,6 +1160,53 @@ def mesh_fill_holes(ctx, vertices, triangles, max_edges, pinned=None, num_vertic
         for buf in own:
             buf.free()
     return out_v, out_t, st.as_dict()
+
+
+def mesh_repair(ctx, vertices, triangles, flags=0, num_vertices=None, num_triangles=None, with_source=False):
+    """Repair on the device (mlsgpu_hip_mesh_repair): bad triangles and every triangle with a repeated directed side are
+    dropped, pinched vertices are split (flags: 0 or REPAIR_SPLIT_PINCHES) and unused ones go, so that mesh_topology calls the
+    result manifold; the same bits whatever the schedule.  `vertices` / `triangles` are numpy arrays (uploaded for the call)
+    or DeviceBuffers of packed float32 xyz / uint32 triples.  One call asks for the sizes, a second one writes.  Returns
+    (vertices float32 [V', 3], triangles uint32 [T', 3], statistics as a dict), the arrays downloaded, and with with_source a
+    fourth: the input index of every output vertex, uint32 [V']."""
+    own = []
+
+    def on_device(a, dtype, count):
+        if isinstance(a, DeviceBuffer):
+            return a, (a.nbytes // 12 if count is None else count)
+        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
+        buf = DeviceBuffer(ctx, array=a) if a.size else None
+        if buf is not None:
+            own.append(buf)
+        return buf, (len(a) if count is None else count)
+
+    st = RepairStats()
+    try:
+        dv, nv = on_device(vertices, np.float32, num_vertices)
+        dt, nt = on_device(triangles, np.uint32, num_triangles)
+        args = (ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, int(flags))
+        rc = lib().mlsgpu_hip_mesh_repair(*args, None, 0, None, 0, None, C.byref(st))
+        if rc != 0 and not (rc == _LENGTH and st.outVertices + st.outTriangles > 0):
+            check(rc)
+        ov = DeviceBuffer(ctx, nbytes=12 * st.outVertices) if st.outVertices else None
+        ot = DeviceBuffer(ctx, nbytes=12 * st.outTriangles) if st.outTriangles else None
+        os_ = DeviceBuffer(ctx, nbytes=4 * st.outVertices) if st.outVertices and with_source else None
+        own.extend(x for x in (ov, ot, os_) if x is not None)
+        if rc != 0:
+            check(lib().mlsgpu_hip_mesh_repair(*args, ov.ptr if ov else None, st.outVertices, ot.ptr if ot else None,
+                                               st.outTriangles, os_.ptr if os_ else None, C.byref(st)))
+        out_v = ov.download(np.float32, 3 * st.outVertices).reshape(-1, 3) if ov else np.zeros((0, 3), np.float32)
+        out_t = ot.download(np.uint32, 3 * st.outTriangles).reshape(-1, 3) if ot else np.zeros((0, 3), np.uint32)
+        out_s = os_.download(np.uint32, st.outVertices) if os_ else np.zeros(0, np.uint32)
+    finally:
+        for buf in own:
+            buf.free()
+    return (out_v, out_t, st.as_dict(), out_s) if with_source else (out_v, out_t, st.as_dict())
+
+
+def mesher_repair(mesher, flags=0):
+    """Mesher.repair as a function, beside mesh_repair."""
+    return mesher.repair(flags)
 
 
 def mesher_fill_holes(mesher, max_edges):

@@ -1373,6 +1373,71 @@ MLSGPU_API int mlsgpu_hip_mesher_fill_holes(mlsgpu_mesher *m, uint32_t maxEdges,
     return MLSGPU_OK;
 }
 
+/* Every output chunk that has triangles through mlsgpu_hip_mesh_repair (repair.hip), by the route of the hole filling above: a
+ * chunk can grow in vertices, so a first round asks every chunk for its sizes and a second repairs it into new arrays, behind
+ * the chunk before.  Nothing of the sink changes before the last chunk is done: an error leaves the results as they were. */
+MLSGPU_API int mlsgpu_hip_mesher_repair(mlsgpu_mesher *m, uint32_t flags, mlsgpu_repair_stats *stats)
+{
+    REQUIRE(m != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
+    /* mlsgpu_hip_mesh_repair's own check, here so that a refused parameter does no work */
+    REQUIRE((flags & ~(uint32_t) MLSGPU_REPAIR_SPLIT_PINCHES) == 0, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
+    mlsgpu_ctx *const ctx = m->ctx;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    std::memset(stats, 0, sizeof(*stats));
+    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
+    std::vector<mlsgpu_repair_stats> one(nc);
+    std::vector<uint64_t> vStart(nc + 1, 0), tStart(nc + 1, 0);
+    for (size_t c = 0; c < nc; c++)
+    {
+        const auto [v0, t0, nv, nt] = m->span(c);
+        std::memset(&one[c], 0, sizeof(one[c]));
+        if (nt > 0)     /* a chunk without triangles has no output (finalize), and keeps none */
+        {
+            /* no room at all: the call stops at its capacity check, with the sizes (or keeps nothing, and is done) */
+            const int rc = mlsgpu_hip_mesh_repair(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, flags, nullptr, 0, nullptr, 0,
+                                                  nullptr, &one[c]);
+            if (rc != MLSGPU_ERR_LENGTH && rc != MLSGPU_OK)
+                return rc;
+        }
+        vStart[c + 1] = vStart[c] + one[c].outVertices;
+        tStart[c + 1] = tStart[c] + one[c].outTriangles;
+    }
+    DeviceArray<float> newVertices;
+    DeviceArray<uint32_t> newTriangles;
+    PROPAGATE(newVertices.alloc(std::max<uint64_t>(3 * vStart[nc], 1)));
+    PROPAGATE(newTriangles.alloc(std::max<uint64_t>(3 * tStart[nc], 1)));
+    for (size_t c = 0; c < nc; c++)
+    {
+        const auto [v0, t0, nv, nt] = m->span(c);
+        if (nt == 0)
+            continue;
+        if (one[c].outTriangles > 0)
+            PROPAGATE(mlsgpu_hip_mesh_repair(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, flags, newVertices + 3 * vStart[c],
+                                             one[c].outVertices, newTriangles + 3 * tStart[c], one[c].outTriangles, nullptr, &one[c]));
+        const mlsgpu_repair_stats &s = one[c];
+        stats->numVertices += s.numVertices;
+        stats->numTriangles += s.numTriangles;
+        stats->outOfRangeTriangles += s.outOfRangeTriangles;
+        stats->degenerateTriangles += s.degenerateTriangles;
+        stats->repeatedSides += s.repeatedSides;
+        stats->droppedTriangles += s.droppedTriangles;
+        stats->unusedVertices += s.unusedVertices;
+        stats->splitVertices += s.splitVertices;
+        stats->addedVertices += s.addedVertices;
+        stats->outVertices += s.outVertices;
+        stats->outTriangles += s.outTriangles;
+    }
+    /* the new generation takes the old one's place (which goes with this call) */
+    m->outVertices = std::move(newVertices);
+    m->outTriangles = std::move(newTriangles);
+    m->chunkVStart = vStart;
+    m->chunkTStart = tStart;
+    m->dropNormals();           /* the chunks have changed and moved */
+    return MLSGPU_OK;
+}
+
 /* The normals (normals.hip) of dense chunk c of a finalized sink, computed where the chunk lies at the first request.  Under
  * the mutex. */
 int mlsgpu_mesher::chunkNormals(uint32_t c, const float **dNormals, mlsgpu_normals_stats *out)

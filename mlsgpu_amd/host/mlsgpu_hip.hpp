@@ -161,6 +161,23 @@ inline mlsgpu_fill_stats fillHoles(const Context &ctx, const Buffer<float> &vert
     return *s;
 }
 
+/// Repair of a mesh in device memory (mlsgpu_hip_mesh_repair): triangles with a repeated directed side are dropped and pinched
+/// vertices split (flags: 0 or MLSGPU_REPAIR_SPLIT_PINCHES), so that the topology report calls the result manifold.
+/// outVertices / outTriangles have room for capVertices / capTriangles and do not overlap the inputs; outSource is NULL or gets
+/// the input index of every output vertex.  With too little room (NULL and 0 ask for the sizes) nothing is written, *st is
+/// complete and std::length_error is thrown.
+inline mlsgpu_repair_stats repair(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
+                                  const Buffer<std::uint32_t> &triangles, std::uint64_t numTriangles, std::uint32_t flags,
+                                  float *outVertices, std::uint64_t capVertices, std::uint32_t *outTriangles,
+                                  std::uint64_t capTriangles, std::uint32_t *outSource = NULL, mlsgpu_repair_stats *st = NULL)
+{
+    mlsgpu_repair_stats own;
+    mlsgpu_repair_stats *const s = st != NULL ? st : &own;
+    check(mlsgpu_hip_mesh_repair(ctx.get(), vertices.get(), numVertices, triangles.get(), numTriangles, flags, outVertices,
+                                 capVertices, outTriangles, capTriangles, outSource, s));
+    return *s;
+}
+
 /// Taubin lambda|mu smoothing of a mesh in device memory (mlsgpu_hip_mesh_smooth): outVertices has room for 3 floats per
 /// vertex and is either `vertices` itself (in place) or does not overlap the inputs.
 inline mlsgpu_smooth_stats smooth(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
@@ -680,6 +697,15 @@ public:
     {
         mlsgpu_fill_stats st;
         check(mlsgpu_hip_mesher_fill_holes(h, maxEdges, &st));
+        return st;
+    }
+    /// Every output chunk of the finalized mesher repaired (mlsgpu_hip_mesher_repair): triangles with a repeated side dropped,
+    /// pinched vertices split, so that chunk topology reports are manifold again; behind simplify(), before smooth() and
+    /// writeChunks().  flags: 0 or MLSGPU_REPAIR_SPLIT_PINCHES.  The statistics are summed over the chunks.
+    mlsgpu_repair_stats repair(std::uint32_t flags = 0)
+    {
+        mlsgpu_repair_stats st;
+        check(mlsgpu_hip_mesher_repair(h, flags, &st));
         return st;
     }
     /// Every output chunk of the finalized mesher smoothed in place (mlsgpu_hip_mesher_smooth); between finalize() -- or
