@@ -12,7 +12,7 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N] [--repair [pinches]] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
  * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
@@ -21,6 +21,9 @@
  *   and --normals; the loops on a seam between two chunks stay open; one line with the statistics.
  * --simplify N (device weld only, N > 0): before the write, every output chunk is vertex-clustered where it lies, in cells of
  *   N grid spacings counted from one cell below the bounding grid's low corner; one line with the statistics.
+ * --simplify-quadric N (device weld only, N > 0, not with --simplify): the same clustering in the same place, with every
+ *   cluster's vertex at the minimiser of its triangles' plane quadrics, which keeps the creases that the mean chamfers; one
+ *   line with the statistics.
  * --repair, --repair pinches (device weld only): before the write, every output chunk is repaired where it lies: triangles
  *   with a repeated directed side are dropped and pinched vertices split (with `pinches`: every umbrella of a vertex becomes a
  *   vertex of its own), so that --check says `manifold yes` -- after --simplify, which can make a chunk non-manifold, and
@@ -50,7 +53,7 @@ int main(int argc, char **argv)
     bool hostWeld = false, checkTopology = false, writeNormals = false;
     std::uint64_t bufferBytes = 0, hbmSplats = 0;
     float simplifyCells = 0.0f;
-    bool simplifyGiven = false, smoothGiven = false, fillGiven = false, repairGiven = false;
+    bool simplifyGiven = false, quadricGiven = false, smoothGiven = false, fillGiven = false, repairGiven = false;
     std::uint32_t repairFlags = 0;
     long smoothIterations = 0, fillEdges = 0;
     std::string tmpDir;
@@ -76,6 +79,11 @@ int main(int argc, char **argv)
         {
             simplifyCells = (float) atof(argv[++i]);
             simplifyGiven = true;
+        }
+        else if (a == "--simplify-quadric" && i + 1 < argc)
+        {
+            simplifyCells = (float) atof(argv[++i]);
+            quadricGiven = true;
         }
         else if (a == "--smooth" && i + 1 < argc)
         {
@@ -109,8 +117,23 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N] [--repair [pinches]] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
+        return 2;
+    }
+    if (simplifyGiven && quadricGiven)
+    {
+        std::cerr << "--simplify and --simplify-quadric exclude each other: a chunk is clustered once\n";
+        return 2;
+    }
+    if (quadricGiven && !(simplifyCells > 0.0f && simplifyCells <= std::numeric_limits<float>::max()))
+    {
+        std::cerr << "--simplify-quadric takes a number of grid spacings > 0\n";
+        return 2;
+    }
+    if (quadricGiven && hostWeld)
+    {
+        std::cerr << "--simplify-quadric needs --weld device: the host welder's output is not on the device\n";
         return 2;
     }
     if (simplifyGiven && !(simplifyCells > 0.0f && simplifyCells <= std::numeric_limits<float>::max()))
@@ -212,6 +235,7 @@ int main(int argc, char **argv)
         std::size_t bins = 0, written = 0;
         std::uint64_t st[8];
         mlsgpu_simplify_stats simplified = mlsgpu_simplify_stats();
+        mlsgpu_simplify_quadric_stats placed = mlsgpu_simplify_quadric_stats();
         float simplifyCell = 0.0f, simplifyOrigin[3] = {0.0f, 0.0f, 0.0f};
         mlsgpu_smooth_stats smoothed = mlsgpu_smooth_stats();
         std::size_t smoothedChunks = 0;
@@ -254,12 +278,15 @@ int main(int argc, char **argv)
                 filled = deviceMesher.fillHoles((std::uint32_t) fillEdges);
                 filledChunks = chunks;
             }
-            if (simplifyGiven)
+            if (simplifyGiven || quadricGiven)
             {
                 simplifyCell = simplifyCells * spacing;
                 for (int i = 0; i < 3; i++)
                     simplifyOrigin[i] = cfg.gridOrigin[i] - simplifyCell;
-                simplified = deviceMesher.simplify(simplifyOrigin, simplifyCell);
+                if (quadricGiven)
+                    placed = deviceMesher.simplifyQuadric(simplifyOrigin, simplifyCell);
+                else
+                    simplified = deviceMesher.simplify(simplifyOrigin, simplifyCell);
             }
             if (repairGiven)
             {
@@ -295,6 +322,15 @@ int main(int argc, char **argv)
                         (unsigned long long) simplified.inVertices, (unsigned long long) simplified.outVertices,
                         (unsigned long long) simplified.inTriangles, (unsigned long long) simplified.outTriangles,
                         (unsigned long long) simplified.collapsedTriangles, (unsigned long long) simplified.duplicateTriangles);
+        if (quadricGiven)
+            std::printf("simplify-quadric cell %.9g origin %.9g %.9g %.9g vertices %llu -> %llu triangles %llu -> %llu collapsed %llu "
+                        "duplicate %llu solved %llu flat %llu escaped %llu scale-exponent %lld\n",
+                        simplifyCell, simplifyOrigin[0], simplifyOrigin[1], simplifyOrigin[2],
+                        (unsigned long long) placed.inVertices, (unsigned long long) placed.outVertices,
+                        (unsigned long long) placed.inTriangles, (unsigned long long) placed.outTriangles,
+                        (unsigned long long) placed.collapsedTriangles, (unsigned long long) placed.duplicateTriangles,
+                        (unsigned long long) placed.solvedVertices, (unsigned long long) placed.flatVertices,
+                        (unsigned long long) placed.escapedVertices, (long long) placed.scaleExponent);
         if (repairGiven)
             std::printf("repair chunks %zu out-of-range %llu degenerate %llu repeated-sides %llu dropped %llu unused %llu split %llu "
                         "vertices %llu -> %llu triangles %llu -> %llu\n",

@@ -708,6 +708,77 @@ int mlsgpu_hip_mesh_simplify(mlsgpu_ctx *ctx, const float *dVertices, uint64_t n
  * simplified chunks).  After an error the sink's results are dropped: finalize again. */
 int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *mesher, const float origin[3], float cellSize, mlsgpu_simplify_stats *stats);
 
+/* ---- the same clustering with every cluster's vertex at the minimiser of the plane-distance quadrics of the triangles that
+ *      touch the cluster (Lindstrom's out-of-core simplification) instead of the mean, which chamfers every crease by a large
+ *      fraction of a cell.  Steps 1, 2, 4 and 5 above apply word for word: on one input the output triangles, outVertices and
+ *      the six statistics are mlsgpu_hip_mesh_simplify's.  Step 3 becomes the steps below.  Deterministic: every float and
+ *      double operation is ONE correctly rounded IEEE operation (no contraction), and every sum is an int64 sum.
+ *      3a. A cluster of one member keeps that member's position bit for bit.
+ *      3b. Cell coordinates, per vertex and axis in double: g = ((double) p - (double) origin) / (double) cellSize; the
+ *          centred offset of a vertex in its own cell is w = (g - (double) c) - 0.5, c of step 1.
+ *      3c. The face vector of a triangle: n = (g1 - g0) x (g2 - g0), each component two products and one subtraction in the
+ *          operation order of the normals' step 2.  Every vertex is valid, so |g| < 2^21 and n is finite.
+ *      3d. M = the largest |component| of n over all triangles.  M == 0: no cluster has a quadric, every cluster of several
+ *          members is `flat` (3f) and scaleExponent = 0.  Otherwise e is the integer with 2^e <= M < 2^(e + 1) (a subnormal M
+ *          has its true exponent), E = 2 e + 1, so that every |n_i n_j| < 2^(E + 1); s = 60 - bitLength(numTriangles), the
+ *          number of bits numTriangles takes; scaleExponent = E.
+ *      3e. A triangle adds to the cluster of each of its corners, once per distinct cluster: corner k adds iff its cluster
+ *          differs from the clusters of all corners j < k.  For the cluster of corner k, d = -((n.x*w.x + n.y*w.y) + n.z*w.z)
+ *          with w the centred offset of corner k in its own cell (|d| <= 1.5 M, to the float cell's rounding); the six
+ *          products n.x*n.x, n.x*n.y, n.x*n.z, n.y*n.y, n.y*n.z, n.z*n.z and the three d*n.x, d*n.y, d*n.z are each quantised
+ *          as q = llrint(ldexp(x, s - E)) with ties to even and added to the cluster's int64 sums A[6] and b[3].
+ *          |q| < 2^(s + 2), and fewer than 2^bitLength(numTriangles) triangles add to a cluster: every |sum| < 2^62, no input
+ *          overflows.  The sums S[3] of step 3 are taken as they are there.
+ *      3f. Per cluster of n > 1 members, in double: a_ij = (double) A_ij, b_i = (double) b_i, tr = (a00 + a11) + a22,
+ *          m_k = (S_k / n) * 2^-30 - 0.5 (step 3's mean, centred).  tr == 0: the cluster is `flat`.  Otherwise
+ *          mu = tr * 2^-10 -- a pull towards the mean that makes the system positive definite and leaves a plane's or a
+ *          straight crease's vertex (rank 1 or 2) where the mean is along the free directions -- r_k = mu * m_k - b_k, and
+ *          (A + mu I) x = r is solved by LDL^T without pivoting in exactly this order:
+ *            d0 = a00 + mu; l10 = a01 / d0; l20 = a02 / d0;
+ *            d1 = (a11 + mu) - l10 * a01; t = a12 - l20 * a01; l21 = t / d1;
+ *            d2 = ((a22 + mu) - l20 * a02) - l21 * t;
+ *            y0 = r0; y1 = r1 - l10 * y0; y2 = (r2 - l20 * y0) - l21 * y1;   z_k = y_k / d_k;
+ *            x2 = z2; x1 = z1 - l21 * x2; x0 = (z0 - l10 * x1) - l20 * x2.
+ *      3g. If an x_k is not finite or |x_k| > 0.5 the minimiser left the cluster's cell: the cluster is `escaped`.  Otherwise
+ *          it is `solved`.
+ *      3h. solved: out = (float) ((double) origin + (((double) c + 0.5) + x) * (double) cellSize) per axis.  flat and escaped:
+ *          step 3's formula unchanged, (float) (origin + (c + mean) * cellSize) -- a mesh on which every cluster falls back
+ *          is mlsgpu_hip_mesh_simplify's output bit for bit.
+ *      The result depends neither on the schedule nor on the order of the triangles nor on the numbering of the vertices.  It
+ *      does depend on which corner a triangle lists first, through the rounding of n and d only.  Scaling every coordinate, the
+ *      origin and cellSize by one power of two scales the output exactly.  Limit: a triangle whose n_i n_j lie below
+ *      2^-(s + 1) of the scale 2^(E + 1) quantises to nothing -- for a million triangles, 2^-41 of the largest squared face
+ *      vector. ---- */
+typedef struct mlsgpu_simplify_quadric_stats
+{
+    uint64_t inVertices, inTriangles;       /* these six: mlsgpu_simplify_stats, in its order */
+    uint64_t outVertices, outTriangles;
+    uint64_t collapsedTriangles;
+    uint64_t duplicateTriangles;
+    uint64_t solvedVertices;        /* output vertices at their quadric's minimiser */
+    uint64_t flatVertices;          /* of several members, at the mean: no quadric (tr == 0) */
+    uint64_t escapedVertices;       /* of several members, at the mean: the minimiser left the cell; outVertices = the */
+                                    /* clusters of one member + solved + flat + escaped */
+    int64_t scaleExponent;          /* E of step 3d */
+} mlsgpu_simplify_quadric_stats;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_simplify_quadric_stats) == 80, "mlsgpu_simplify_quadric_stats is part of the ABI");
+#else
+typedef char mlsgpu_simplify_quadric_stats_size_is_80[sizeof(mlsgpu_simplify_quadric_stats) == 80 ? 1 : -1];
+#endif
+/* Arguments, capacities (room for the INPUT's sizes), error codes and blocking as for mlsgpu_hip_mesh_simplify; the largest
+ * face vector comes back with that call's one read-back in the middle, so there is no further synchronisation.  Scratch: 72
+ * bytes per vertex more (nine int64 sums per possible cluster).  MLSGPU_HIP_SIMPLIFY_ACCUMULATE=plain takes the sums with up
+ * to 27 atomics per triangle instead of combining the lanes of a wave that share a cluster first; the result is the same bit
+ * for bit. */
+int mlsgpu_hip_mesh_simplify_quadric(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices, const uint32_t *dTriangles,
+                                     uint64_t numTriangles, const float origin[3], float cellSize, float *dOutVertices,
+                                     uint32_t *dOutTriangles, mlsgpu_simplify_quadric_stats *stats);
+/* mlsgpu_hip_mesher_simplify with this placement: chunks INDEPENDENT, packed and served in the same way, the chunks' normals
+ * dropped.  *stats is the sum over the chunks, scaleExponent the largest among the chunks that have one. */
+int mlsgpu_hip_mesher_simplify_quadric(mlsgpu_mesher *mesher, const float origin[3], float cellSize,
+                                       mlsgpu_simplify_quadric_stats *stats);
+
 /* ---- area-weighted vertex normals of a device-resident mesh, so that what leaves the device can be shaded as it is.  The
  *      reference has no counterpart: its files carry positions and faces (src/fast_ply.cpp:443-521).  Computed from the
  *      FINISHED mesh (after prune, after a simplify, whose cluster means no MLS fit belongs to).  Deterministic: every float

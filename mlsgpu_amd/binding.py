@@ -134,6 +134,16 @@ class SimplifyStats(C.Structure):
         return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
 
 
+class SimplifyQuadricStats(C.Structure):
+    """mlsgpu_simplify_quadric_stats: SimplifyStats' six, how the output vertices of several members were placed, and the
+    exponent of the quadrics' scale."""
+    _fields_ = SimplifyStats._fields_ + [("solvedVertices", C.c_uint64), ("flatVertices", C.c_uint64),
+                                         ("escapedVertices", C.c_uint64), ("scaleExponent", C.c_int64)]
+
+    def as_dict(self):
+        return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
+
+
 class NormalsStats(C.Structure):
     """mlsgpu_normals_stats: what took no part, the vertices left without a normal, and the scale's exponent."""
     _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
@@ -384,6 +394,8 @@ def lib():
     sig("mlsgpu_hip_topology_reason", u64, P(Topology), C.c_char_p, u64)
     sig("mlsgpu_hip_mesh_simplify", C.c_int, vp, vp, u64, vp, u64, P(f32), f32, vp, vp, P(SimplifyStats))
     sig("mlsgpu_hip_mesher_simplify", C.c_int, vp, P(f32), f32, P(SimplifyStats))
+    sig("mlsgpu_hip_mesh_simplify_quadric", C.c_int, vp, vp, u64, vp, u64, P(f32), f32, vp, vp, P(SimplifyQuadricStats))
+    sig("mlsgpu_hip_mesher_simplify_quadric", C.c_int, vp, P(f32), f32, P(SimplifyQuadricStats))
     sig("mlsgpu_hip_write_ply", C.c_int, C.c_char_p, vp, u64, vp, u64, vp, u32)
     sig("mlsgpu_hip_mesh_normals", C.c_int, vp, vp, u64, vp, u64, vp, P(NormalsStats))
     sig("mlsgpu_hip_mesher_chunk_normals", C.c_int, vp, u32, P(vp), P(NormalsStats))
@@ -926,6 +938,15 @@ class Mesher:
         check(lib().mlsgpu_hip_mesher_simplify(self.h, (C.c_float * 3)(*[float(x) for x in origin]), float(cell_size), C.byref(st)))
         return st.as_dict()
 
+    def simplify_quadric(self, origin, cell_size):
+        """simplify() with every cluster's vertex at the minimiser of its triangles' plane quadrics (mesh_simplify_quadric):
+        the same chunks, triangles and numbering, other positions.  Returns the ten statistics, counts summed over the
+        chunks and scaleExponent the largest."""
+        st = SimplifyQuadricStats()
+        check(lib().mlsgpu_hip_mesher_simplify_quadric(self.h, (C.c_float * 3)(*[float(x) for x in origin]), float(cell_size),
+                                                       C.byref(st)))
+        return st.as_dict()
+
     def smooth(self, iterations, lam=0.5, mu=-0.53, boundary=SMOOTH_BOUNDARY_FIXED):
         """Every output chunk of the finalized sink smoothed in place (mesh_smooth): positions only, the triangles and the
         chunk layout stay.  Returns the statistics: counts summed over the chunks, exponent and maxima the largest."""
@@ -1021,6 +1042,19 @@ def mesh_simplify(ctx, vertices, triangles, origin, cell_size, num_vertices=None
     `origin`) become one vertex at their mean, collapsed and repeated triangles go.  `vertices` / `triangles` are numpy
     arrays (uploaded for the call) or DeviceBuffers of packed float32 xyz / uint32 triples.  Returns (vertices, triangles,
     statistics as a dict), the arrays downloaded."""
+    return _mesh_simplify(lib().mlsgpu_hip_mesh_simplify, SimplifyStats(), ctx, vertices, triangles, origin, cell_size,
+                          num_vertices, num_triangles)
+
+
+def mesh_simplify_quadric(ctx, vertices, triangles, origin, cell_size, num_vertices=None, num_triangles=None):
+    """mesh_simplify with every cluster's vertex at the minimiser of the plane quadrics of the triangles that touch the cluster
+    (mlsgpu_hip_mesh_simplify_quadric), which keeps creases that the mean chamfers: the same triangles and numbering, other
+    positions, ten statistics."""
+    return _mesh_simplify(lib().mlsgpu_hip_mesh_simplify_quadric, SimplifyQuadricStats(), ctx, vertices, triangles, origin,
+                          cell_size, num_vertices, num_triangles)
+
+
+def _mesh_simplify(entry, st, ctx, vertices, triangles, origin, cell_size, num_vertices, num_triangles):
     own = []
 
     def on_device(a, dtype, count):
@@ -1032,16 +1066,14 @@ def mesh_simplify(ctx, vertices, triangles, origin, cell_size, num_vertices=None
             own.append(buf)
         return buf, (len(a) if count is None else count)
 
-    st = SimplifyStats()
     try:
         dv, nv = on_device(vertices, np.float32, num_vertices)
         dt, nt = on_device(triangles, np.uint32, num_triangles)
         ov = DeviceBuffer(ctx, nbytes=12 * nv) if nv and dv is not None else None
         ot = DeviceBuffer(ctx, nbytes=12 * nt) if nt and dt is not None else None
         own.extend(x for x in (ov, ot) if x is not None)
-        check(lib().mlsgpu_hip_mesh_simplify(ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt,
-                                             (C.c_float * 3)(*[float(x) for x in origin]), float(cell_size),
-                                             ov.ptr if ov else None, ot.ptr if ot else None, C.byref(st)))
+        check(entry(ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, (C.c_float * 3)(*[float(x) for x in origin]),
+                    float(cell_size), ov.ptr if ov else None, ot.ptr if ot else None, C.byref(st)))
         out_v = ov.download(np.float32, 3 * st.outVertices).reshape(-1, 3) if st.outVertices else np.zeros((0, 3), np.float32)
         out_t = ot.download(np.uint32, 3 * st.outTriangles).reshape(-1, 3) if st.outTriangles else np.zeros((0, 3), np.uint32)
     finally:

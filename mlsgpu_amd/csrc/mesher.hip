@@ -1188,18 +1188,20 @@ MLSGPU_API int mlsgpu_hip_mesher_chunk_topology(mlsgpu_mesher *m, uint32_t i, ml
     return mlsgpu_hip_mesh_topology(m->ctx, m->outTriangles + 3 * s.t0, s.nt, s.nv, out);
 }
 
-/* Every output chunk through mlsgpu_hip_mesh_simplify (simplify.hip), into buffers of the chunk's size and from there to the
- * front of the output arrays: a result is never larger than its chunk, so chunk c's lands at or before where chunk c began and
- * never on a chunk that is still to be read. */
-MLSGPU_API int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *m, const float origin[3], float cellSize, mlsgpu_simplify_stats *stats)
+/* Every output chunk through mlsgpu_hip_mesh_simplify or, where `quadric` is given, mlsgpu_hip_mesh_simplify_quadric
+ * (simplify.hip), into buffers of the chunk's size and from there to the front of the output arrays: a result is never larger
+ * than its chunk, so chunk c's lands at or before where chunk c began and never on a chunk that is still to be read.  The
+ * caller holds the lock of a finalized sink.  *stats and the last four fields of *quadric: the chunks added up, scaleExponent
+ * the largest among the chunks that have one. */
+static int simplifyChunks(mlsgpu_mesher *m, const float origin[3], float cellSize, mlsgpu_simplify_stats *stats,
+                          mlsgpu_simplify_quadric_stats *quadric)
 {
-    REQUIRE(m != nullptr && origin != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
-    std::lock_guard<std::mutex> lock(m->mutex);
-    REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
     mlsgpu_ctx *const ctx = m->ctx;
     HIP_CHECK(hipSetDevice(ctx->device));
     m->dropNormals();           /* the chunks change and move */
     std::memset(stats, 0, sizeof(*stats));
+    if (quadric != nullptr)
+        std::memset(quadric, 0, sizeof(*quadric));
     const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
     uint64_t maxV = 0, maxT = 0;
     for (size_t c = 0; c < nc; c++)
@@ -1212,14 +1214,24 @@ MLSGPU_API int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *m, const float origin[3
     PROPAGATE(tmpV.alloc(3 * maxV));
     PROPAGATE(tmpT.alloc(3 * maxT));
     uint64_t vAt = 0, tAt = 0;
+    bool scaled = false;        /* a chunk before this one had a scale */
     for (size_t c = 0; c < nc; c++)
     {
         const auto [v0, t0, nv, nt] = m->span(c);
         mlsgpu_simplify_stats one;
+        mlsgpu_simplify_quadric_stats oneQuadric;
         std::memset(&one, 0, sizeof(one));
+        std::memset(&oneQuadric, 0, sizeof(oneQuadric));
         int rc = MLSGPU_OK;
-        if (nt > 0)     /* a chunk without triangles has no output (finalize), and keeps none */
+        if (nt > 0 && quadric == nullptr)       /* a chunk without triangles has no output (finalize), and keeps none */
             rc = mlsgpu_hip_mesh_simplify(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, origin, cellSize, tmpV, tmpT, &one);
+        else if (nt > 0)
+        {
+            rc = mlsgpu_hip_mesh_simplify_quadric(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, origin, cellSize, tmpV,
+                                                  tmpT, &oneQuadric);
+            one = mlsgpu_simplify_stats{oneQuadric.inVertices, oneQuadric.inTriangles, oneQuadric.outVertices, oneQuadric.outTriangles,
+                                        oneQuadric.collapsedTriangles, oneQuadric.duplicateTriangles};
+        }
         if (rc == MLSGPU_OK && one.outVertices > 0
             && hipMemcpyAsync(m->outVertices + 3 * vAt, tmpV, one.outVertices * 12, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
             rc = setError(MLSGPU_ERR_HIP, "mesher simplify: the copy of a chunk's vertices failed");
@@ -1242,11 +1254,47 @@ MLSGPU_API int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *m, const float origin[3
         stats->outTriangles += one.outTriangles;
         stats->collapsedTriangles += one.collapsedTriangles;
         stats->duplicateTriangles += one.duplicateTriangles;
+        if (quadric != nullptr)
+        {
+            quadric->solvedVertices += oneQuadric.solvedVertices;
+            quadric->flatVertices += oneQuadric.flatVertices;
+            quadric->escapedVertices += oneQuadric.escapedVertices;
+            if (oneQuadric.solvedVertices + oneQuadric.escapedVertices > 0)     /* this chunk has a scale: M != 0 */
+            {
+                quadric->scaleExponent = scaled ? std::max(quadric->scaleExponent, oneQuadric.scaleExponent) : oneQuadric.scaleExponent;
+                scaled = true;
+            }
+        }
     }
     m->chunkVStart[nc] = vAt;
     m->chunkTStart[nc] = tAt;
     HIP_CHECK(hipStreamSynchronize(ctx->stream));       /* the temporaries go with the call */
     return MLSGPU_OK;
+}
+
+MLSGPU_API int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *m, const float origin[3], float cellSize, mlsgpu_simplify_stats *stats)
+{
+    REQUIRE(m != nullptr && origin != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
+    return simplifyChunks(m, origin, cellSize, stats, nullptr);
+}
+
+MLSGPU_API int mlsgpu_hip_mesher_simplify_quadric(mlsgpu_mesher *m, const float origin[3], float cellSize,
+                                                  mlsgpu_simplify_quadric_stats *stats)
+{
+    REQUIRE(m != nullptr && origin != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
+    mlsgpu_simplify_stats shared = mlsgpu_simplify_stats();
+    const int rc = simplifyChunks(m, origin, cellSize, &shared, stats);
+    stats->inVertices = shared.inVertices;
+    stats->inTriangles = shared.inTriangles;
+    stats->outVertices = shared.outVertices;
+    stats->outTriangles = shared.outTriangles;
+    stats->collapsedTriangles = shared.collapsedTriangles;
+    stats->duplicateTriangles = shared.duplicateTriangles;
+    return rc;
 }
 
 /* Every output chunk through mlsgpu_hip_mesh_smooth (smooth.hip), in place: only the positions change. */

@@ -145,6 +145,19 @@ inline mlsgpu_simplify_stats simplify(const Context &ctx, const Buffer<float> &v
     return st;
 }
 
+/// simplify() with every cluster's vertex at the minimiser of its triangles' plane quadrics, which keeps the creases the mean
+/// chamfers (mlsgpu_hip_mesh_simplify_quadric): the same triangles and numbering, other positions.
+inline mlsgpu_simplify_quadric_stats simplifyQuadric(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
+                                                     const Buffer<std::uint32_t> &triangles, std::uint64_t numTriangles,
+                                                     const float origin[3], float cellSize, Buffer<float> &outVertices,
+                                                     Buffer<std::uint32_t> &outTriangles)
+{
+    mlsgpu_simplify_quadric_stats st;
+    check(mlsgpu_hip_mesh_simplify_quadric(ctx.get(), vertices.get(), numVertices, triangles.get(), numTriangles, origin, cellSize,
+                                           outVertices.get(), outTriangles.get(), &st));
+    return st;
+}
+
 /// Hole filling of a mesh in device memory (mlsgpu_hip_mesh_fill_holes): every boundary loop of at most maxEdges sides, none of
 /// whose vertices `pinned` (NULL, or one byte per vertex) marks, gets a fan to the mean of its vertices.  outVertices /
 /// outTriangles have room for capVertices / capTriangles and do not overlap the inputs; with too little room (NULL and 0 ask for
@@ -688,6 +701,14 @@ public:
     {
         mlsgpu_simplify_stats st;
         check(mlsgpu_hip_mesher_simplify(h, origin, cellSize, &st));
+        return st;
+    }
+    /// simplify() with quadric-error vertex placement (mlsgpu_hip_mesher_simplify_quadric); counts summed over the chunks, the
+    /// scale's exponent the largest.
+    mlsgpu_simplify_quadric_stats simplifyQuadric(const float origin[3], float cellSize)
+    {
+        mlsgpu_simplify_quadric_stats st;
+        check(mlsgpu_hip_mesher_simplify_quadric(h, origin, cellSize, &st));
         return st;
     }
     /// Every output chunk of the finalized mesher with its boundary loops of at most maxEdges sides capped
