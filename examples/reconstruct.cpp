@@ -12,7 +12,7 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--deviation D] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
  * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
@@ -31,9 +31,15 @@
  * --smooth N (device weld only, N > 0): before the write, every output chunk gets N Taubin iterations (lambda 0.5, mu -0.53)
  *   where it lies, the vertices on a chunk's boundary held fixed -- after --simplify when both are given; one line with the
  *   statistics.
+ * --deviation D (device weld only, D > 0 in world units): the chunks are kept as the weld left them, and after the last of
+ *   --fill-holes, --simplify, --repair and --smooth two lines say how far the output lies from them: `moved`, the output's
+ *   vertices against the kept surface, and `lost`, the kept vertices against the output's surface -- the points within and
+ *   beyond D, the largest and the RMS distance, and the distances that 50 % and 90 % of the points within stay under, read
+ *   off a histogram of 16 bins.  Without such a stage `moved` is all zeros.
  * --normals (device weld only): every output chunk is written with its area-weighted vertex normals (nx ny nz after z),
  *   computed where the chunk lies -- after --simplify and --smooth when they are given; one line per chunk.
  */
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -44,6 +50,27 @@
 #include "../mlsgpu_amd/host/mlsgpu_hip.hpp"
 
 using namespace mlsgpu::hip;
+
+// the distance that `share` of the points within stay under: the upper edge of the histogram bin where their count is reached
+static double quantileOf(const mlsgpu_deviation &d, double share)
+{
+    std::uint64_t seen = 0;
+    for (int k = 0; k < 16; k++)
+    {
+        seen += d.histogram[k];
+        if (d.within > 0 && (double) seen >= share * (double) d.within)
+            return std::sqrt(d.limit2) * (k + 1) / 16.0;
+    }
+    return 0.0;
+}
+
+static void printDeviation(const char *name, const mlsgpu_deviation &d)
+{
+    const double meanSquare = d.within > 0 ? std::ldexp((double) d.sumQ, (int) d.scaleExponent - 30) / (double) d.within : 0.0;
+    std::printf("deviation %s points %llu within %llu beyond %llu max %.9g rms %.9g p50 %.9g p90 %.9g\n", name,
+                (unsigned long long) d.numPoints, (unsigned long long) d.within, (unsigned long long) d.beyond,
+                std::sqrt(d.maxDistance2), std::sqrt(meanSquare), quantileOf(d, 0.5), quantileOf(d, 0.9));
+}
 
 static bool isPly(const std::string &a) { return a.size() > 4 && a.compare(a.size() - 4, 4, ".ply") == 0; }
 
@@ -56,6 +83,8 @@ int main(int argc, char **argv)
     bool simplifyGiven = false, quadricGiven = false, smoothGiven = false, fillGiven = false, repairGiven = false;
     std::uint32_t repairFlags = 0;
     long smoothIterations = 0, fillEdges = 0;
+    float deviationDistance = 0.0f;
+    bool deviationGiven = false;
     std::string tmpDir;
     std::vector<std::string> plys, rest;
     for (int i = 1; i < argc; i++)
@@ -95,6 +124,11 @@ int main(int argc, char **argv)
             fillEdges = atol(argv[++i]);
             fillGiven = true;
         }
+        else if (a == "--deviation" && i + 1 < argc)
+        {
+            deviationDistance = (float) atof(argv[++i]);
+            deviationGiven = true;
+        }
         else if (a == "--repair")
         {
             repairGiven = true;
@@ -117,7 +151,7 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--deviation D] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
         return 2;
     }
@@ -164,6 +198,16 @@ int main(int argc, char **argv)
     if (fillGiven && hostWeld)
     {
         std::cerr << "--fill-holes needs --weld device: the host welder's output is not on the device\n";
+        return 2;
+    }
+    if (deviationGiven && !(deviationDistance > 0.0f && deviationDistance <= std::numeric_limits<float>::max()))
+    {
+        std::cerr << "--deviation takes a search distance > 0\n";
+        return 2;
+    }
+    if (deviationGiven && hostWeld)
+    {
+        std::cerr << "--deviation needs --weld device: the host welder's output is not on the device\n";
         return 2;
     }
     if (repairGiven && hostWeld)
@@ -243,6 +287,7 @@ int main(int argc, char **argv)
         std::size_t filledChunks = 0;
         mlsgpu_repair_stats repaired = mlsgpu_repair_stats();
         std::size_t repairedChunks = 0;
+        std::pair<mlsgpu_deviation, mlsgpu_deviation> deviated;
         {
             BucketFarm farm(devices, cfg, 4 /* --device-threads */, 1, hostWeld ? NULL : &deviceMesher);
             if (hostWeld)
@@ -273,6 +318,8 @@ int main(int argc, char **argv)
         else
         {
             const std::size_t chunks = deviceMesher.finalize();
+            if (deviationGiven)
+                deviceMesher.keepReference();       // directly behind the weld: what every later stage is measured against
             if (fillGiven)
             {
                 filled = deviceMesher.fillHoles((std::uint32_t) fillEdges);
@@ -298,6 +345,8 @@ int main(int argc, char **argv)
                 smoothed = deviceMesher.smooth((std::uint32_t) smoothIterations, 0.5f, -0.53f, MLSGPU_SMOOTH_BOUNDARY_FIXED);
                 smoothedChunks = chunks;
             }
+            if (deviationGiven)
+                deviated = deviceMesher.deviation(deviationDistance);
             written = deviceMesher.writeChunks(chunks, [&](std::uint64_t) { return outName; }, comments, writeNormals);
             deviceMesher.getStatistics(st);
         }
@@ -344,6 +393,11 @@ int main(int argc, char **argv)
                         smoothedChunks, (unsigned long long) smoothed.numVertices, (unsigned long long) smoothed.numEdges,
                         (unsigned long long) smoothed.boundaryVertices, (unsigned long long) smoothed.isolatedVertices,
                         (unsigned long long) smoothed.passes, smoothed.maxMove);
+        if (deviationGiven)
+        {
+            printDeviation("moved", deviated.first);
+            printDeviation("lost", deviated.second);
+        }
         if (writeNormals)
             for (std::uint32_t i = 0; i < written; i++)
             {

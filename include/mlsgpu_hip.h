@@ -1088,6 +1088,88 @@ int mlsgpu_hip_mesh_repair(mlsgpu_ctx *ctx, const float *dVertices, uint64_t num
  * leaves as they are). */
 int mlsgpu_hip_mesher_repair(mlsgpu_mesher *mesher, uint32_t flags, mlsgpu_repair_stats *stats);
 
+/* ---- deviation report of a device-resident mesh: for a set of points (normally the vertices of one mesh) the squared
+ *      distance to the surface of another mesh, exact up to a search distance D, with its maximum, a fixed-point mean square,
+ *      a histogram and the farthest point.  mlsgpu_hip_mesh_topology says whether a simplified, smoothed or filled mesh is
+ *      still a manifold; this says how far it has moved.  The reference has no counterpart.  Deterministic: all arithmetic is
+ *      in double on the floats converted exactly, every + - * / below is ONE correctly rounded IEEE operation (no
+ *      contraction), dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z, cross(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z,
+ *      u.x*v.y - u.y*v.x), and every field of the report is a count, a minimum, a maximum or an integer sum -- the output
+ *      depends neither on the schedule nor on the order of the triangles (but for which of several equal triangles is named).
+ *      1. A triangle with an index >= V is counted in outOfRangeTriangles (the index is compared, never used as an address);
+ *         otherwise a triangle that names a vertex twice is counted in degenerateTriangles.  Neither takes part.
+ *      2. Per axis, lo / hi are the smallest / largest of a triangle's three corner coordinates.  A (point, triangle) pair
+ *         is a CANDIDATE iff, on every axis, lo - D <= p and p <= hi + D, each side one double operation.  This belongs to
+ *         the contract, not to the implementation: any conservative spatial cull is then exact, since it only has to hand
+ *         the kernel a superset of the candidates -- the kernel applies this test before step 3.
+ *      3. The squared distance of a candidate pair with corners a, b, c:
+ *         seg(p, a, b): u = b - a, w = p - a, L = dot(u, u); s = (L == 0) ? 0 : dot(w, u) / L, then s = fmin(fmax(s, 0), 1);
+ *            r = w - s*u (per axis one multiply, one subtract); the value is dot(r, r).
+ *         face(p, a, b, c): n = cross(b - a, c - a), nn = dot(n, n); i0 = dot(cross(b - a, p - a), n), i1 = dot(cross(c - b,
+ *            p - b), n), i2 = dot(cross(a - c, p - c), n).  If nn > 0 && i0 >= 0 && i1 >= 0 && i2 >= 0, then h = dot(p - a, n)
+ *            and the value is (h*h) / nn; otherwise it is +infinity.
+ *         d2(p, t) = fmin(fmin(fmin(seg(p,a,b), seg(p,b,c)), seg(p,c,a)), face(p,a,b,c)).
+ *         (No data-dependent branch, defined for zero-area triangles and coincident corners, no NaN from finite floats.)
+ *      4. D2 = (double) D * (double) D.  best(p) is the smallest d2(p, t) over the point's candidates.  The point is WITHIN if
+ *         it has a candidate and best <= D2: its squared distance is best, and its nearest triangle is the LOWEST triangle
+ *         index that attains it bit for bit.  Any other point is BEYOND: +infinity, and 0xFFFFFFFF.
+ *      5. The report.  farthestPoint: the lowest point index whose squared distance equals maxDistance2, UINT64_MAX if
+ *         within == 0.  histogram: a within point goes to the largest k in 0..15 with best >= (D2 * (double)(k*k)) / 256.0
+ *         (edges at d = kD/16; best == D2 lands in bin 15).  e = the exponent of D2 (2^e <= D2 < 2^(e + 1)); scaleExponent =
+ *         e; q = llrint(best * 2^(30 - e)) <= 2^31; sumQ = the int64 sum of q over the within points (P < 2^32: it fits).
+ *         The mean square is sumQ * 2^(e - 30) / within.  maxDistance2: the largest best of a within point, 0 if none.
+ *      No points: every field is zero but numVertices, numTriangles, limit2, the triangle counts of step 1 and farthestPoint
+ *      (UINT64_MAX).  No triangle that takes part: every point is beyond.  Scaling every coordinate and D by 2^s scales the
+ *      distances by 4^s exactly and moves scaleExponent by 2 s (away from overflow and the subnormals). ---- */
+typedef struct mlsgpu_deviation
+{
+    uint64_t numPoints, numVertices, numTriangles;
+    uint64_t outOfRangeTriangles;   /* an index >= numVertices */
+    uint64_t degenerateTriangles;   /* in range, a vertex twice */
+    uint64_t within, beyond;        /* step 4: within + beyond = numPoints */
+    uint64_t farthestPoint;         /* step 5 */
+    uint64_t farthestChunk;         /* 0; mlsgpu_hip_mesher_deviation: the dense chunk of farthestPoint */
+    uint64_t histogram[16];
+    int64_t sumQ, scaleExponent;
+    double maxDistance2;
+    double limit2;                  /* D2 */
+} mlsgpu_deviation;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_deviation) == 232, "mlsgpu_deviation is part of the ABI");
+#else
+typedef char mlsgpu_deviation_size_is_232[sizeof(mlsgpu_deviation) == 232 ? 1 : -1];
+#endif
+/* numPoints packed float xyz against the mesh of numVertices packed float xyz and numTriangles uint32 index triples, all on
+ * ctx's device and none modified.  dDistance2 and dNearest are NULL or hold one entry per point, in the caller's point order
+ * (step 4).  MLSGPU_ERR_INVALID, before anything touches the device, for a NULL ctx or out and for a maxDistance that is not
+ * finite or is <= 0; MLSGPU_ERR_LENGTH, before anything is allocated, unless numPoints < 2^32, numVertices < 2^32 and
+ * 3 * numTriangles < 2^32.  MLSGPU_ERR_INVALID for a point or target coordinate that is not finite (counted on the device).
+ * MLSGPU_ERR_LENGTH if the grid's pair count cannot be brought under 2^32.  No points, no vertices or no triangles is not an
+ * error.  The cull is a sparse uniform grid over the target's box: a triangle is paired with every cell that its box, inflated
+ * by D, touches, and a point is tested against the pairs of its own cell; the cell size is doubled until the pairs number at
+ * most max(2^20, 8 per triangle).  Scratch is allocated for the call and freed on return: 24 bytes per point (the two sides of
+ * a sort's 64-bit keys and 32-bit values) and 8 more where dDistance2 is NULL, 8 bytes per triangle (its cell count and where
+ * its pairs begin), 24 bytes per grid pair, the sorts' histograms and the scan's tile sums; MLSGPU_ERR_NOMEM if the device
+ * does not have it.  Blocks until the report is there. */
+int mlsgpu_hip_mesh_deviation(mlsgpu_ctx *ctx, const float *dPoints, uint64_t numPoints, const float *dVertices,
+                              uint64_t numVertices, const uint32_t *dTriangles, uint64_t numTriangles, float maxDistance,
+                              double *dDistance2, uint32_t *dNearest, mlsgpu_deviation *out);
+/* The reference that mlsgpu_hip_mesher_deviation measures against: on a finalized device sink, copies every chunk's current
+ * vertices and triangles, and the chunk spans, into device arrays that the mesher holds (12 bytes per vertex and per
+ * triangle).  Call it directly behind finalize, before a stage that moves vertices.  MLSGPU_ERR_INVALID before finalize;
+ * calling it again replaces the copy.  mlsgpu_hip_mesher_reset and _destroy free it; a new finalize keeps it only if the chunk
+ * list has the same length, and drops it otherwise.  _drop_reference frees it (no reference is not an error). */
+int mlsgpu_hip_mesher_keep_reference(mlsgpu_mesher *mesher);
+int mlsgpu_hip_mesher_drop_reference(mlsgpu_mesher *mesher);
+/* The deviation of a finalized device sink from its kept reference, chunk by chunk over the dense chunk list (which the stages
+ * keep stable: a chunk that lost its triangles stays in it).  *moved: the current chunk's vertices against the kept chunk's
+ * surface -- how far the output left the original.  *lost: the kept chunk's vertices against the current chunk's surface --
+ * what the original had that the output flattened.  Either may be NULL.  Over the chunks the counts, the histogram and sumQ
+ * add (D is the same, hence the scale); maxDistance2 is the maximum, and farthestChunk / farthestPoint name the lowest (dense
+ * chunk index, point index within the chunk) that attains it.  MLSGPU_ERR_INVALID before finalize, without a kept reference
+ * and for a refused maxDistance.  Changes nothing in the sink; works after any sequence of fill / simplify / repair / smooth. */
+int mlsgpu_hip_mesher_deviation(mlsgpu_mesher *mesher, float maxDistance, mlsgpu_deviation *moved, mlsgpu_deviation *lost);
+
 /* ---- host mesh sink: OOCMesher's weld as the reference runs it, on the host (src/mesher.cpp:220-469, north_star:
  *      "welding stays on host").  add() is MesherBase::InputFunctor: local components of the block by union-find over
  *      two edges per triangle (computeLocalComponents, :220-236), clumps merged across blocks through the external

@@ -4,6 +4,7 @@ Class and method names follow the reference's C++ surface (SplatTreeCL, MlsFunct
 DeviceWorkerGroupBase::Worker) so tests read like the reference's own.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -174,6 +175,24 @@ class FillStats(C.Structure):
 
     def as_dict(self):
         return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
+
+
+class Deviation(C.Structure):
+    """mlsgpu_deviation: the sizes, what took no part, the points within and beyond the search distance, the farthest point,
+    the histogram of the distances in sixteenths of the search distance, their fixed-point sum of squares and their maximum."""
+    _fields_ = [("numPoints", C.c_uint64), ("numVertices", C.c_uint64), ("numTriangles", C.c_uint64),
+                ("outOfRangeTriangles", C.c_uint64), ("degenerateTriangles", C.c_uint64), ("within", C.c_uint64),
+                ("beyond", C.c_uint64), ("farthestPoint", C.c_uint64), ("farthestChunk", C.c_uint64),
+                ("histogram", C.c_uint64 * 16), ("sumQ", C.c_int64), ("scaleExponent", C.c_int64),
+                ("maxDistance2", C.c_double), ("limit2", C.c_double)]
+
+    def as_dict(self):
+        """The fields (the histogram as a list of 16 ints) and, derived from them on the host, meanSquare = sumQ *
+        2^(scaleExponent - 30) / within (0.0 without a point within)."""
+        out = dict((name, [int(x) for x in getattr(self, name)] if name == "histogram"
+                    else (float if kind is C.c_double else int)(getattr(self, name))) for name, kind in self._fields_)
+        out["meanSquare"] = math.ldexp(self.sumQ, int(self.scaleExponent) - 30) / self.within if self.within else 0.0
+        return out
 
 
 class RepairStats(C.Structure):
@@ -405,6 +424,10 @@ def lib():
     sig("mlsgpu_hip_mesher_fill_holes", C.c_int, vp, u32, P(FillStats))
     sig("mlsgpu_hip_mesh_repair", C.c_int, vp, vp, u64, vp, u64, u32, vp, u64, vp, u64, vp, P(RepairStats))
     sig("mlsgpu_hip_mesher_repair", C.c_int, vp, u32, P(RepairStats))
+    sig("mlsgpu_hip_mesh_deviation", C.c_int, vp, vp, u64, vp, u64, vp, u64, C.c_float, vp, vp, P(Deviation))
+    sig("mlsgpu_hip_mesher_keep_reference", C.c_int, vp)
+    sig("mlsgpu_hip_mesher_drop_reference", C.c_int, vp)
+    sig("mlsgpu_hip_mesher_deviation", C.c_int, vp, C.c_float, P(Deviation), P(Deviation))
     sig("mlsgpu_hip_write_ply_normals", C.c_int, C.c_char_p, vp, vp, u64, vp, u64, vp, u32)
     sig("mlsgpu_hip_mesher_write_ply_normals", C.c_int, vp, C.c_uint32, C.c_char_p, vp, C.c_uint32, u64)
     sig("mlsgpu_hip_bucket", C.c_int, vp, vp, u64, P(GridStruct), P(BucketParams), BUCKET_FN, vp, P(u64))
@@ -972,6 +995,24 @@ class Mesher:
         check(lib().mlsgpu_hip_mesher_repair(self.h, int(flags), C.byref(st)))
         return st.as_dict()
 
+    def keep_reference(self):
+        """Copies every chunk of the finalized sink as it is now, for deviation() to measure against: call it directly behind
+        finalize(), before a stage that moves vertices.  Calling it again replaces the copy; reset() frees it."""
+        check(lib().mlsgpu_hip_mesher_keep_reference(self.h))
+
+    def drop_reference(self):
+        """Frees what keep_reference() copied."""
+        check(lib().mlsgpu_hip_mesher_drop_reference(self.h))
+
+    def deviation(self, max_distance):
+        """How far the sink's chunks are from the kept reference (mesh_deviation, chunk by chunk): (moved, lost), two dicts.
+        moved: the current vertices against the kept surface; lost: the kept vertices against the current surface.  Counts,
+        histogram and sumQ summed over the chunks, maxDistance2 the largest, farthestChunk / farthestPoint where it is.
+        Changes nothing in the sink."""
+        moved, lost = Deviation(), Deviation()
+        check(lib().mlsgpu_hip_mesher_deviation(self.h, float(max_distance), C.byref(moved), C.byref(lost)))
+        return moved.as_dict(), lost.as_dict()
+
     def write_ply(self, i, path, comments=(), buffer_bytes=0):
         """Output chunk i straight from HBM into FastPly::Writer's file through a bounded pinned buffer."""
         arr = (C.c_char_p * max(len(comments), 1))(*[c.encode("ascii") for c in comments])
@@ -1234,6 +1275,47 @@ def mesh_repair(ctx, vertices, triangles, flags=0, num_vertices=None, num_triang
         for buf in own:
             buf.free()
     return (out_v, out_t, st.as_dict(), out_s) if with_source else (out_v, out_t, st.as_dict())
+
+
+def mesh_deviation(ctx, points, vertices, triangles, max_distance, want_distances=True, want_nearest=True, num_points=None,
+                   num_vertices=None, num_triangles=None):
+    """The deviation report on the device (mlsgpu_hip_mesh_deviation): for every point the squared distance to the surface of
+    the mesh, exact up to max_distance, and its statistics; bit-reproducible whatever the schedule.  `points`, `vertices` /
+    `triangles` are numpy arrays (uploaded for the call) or DeviceBuffers of packed float32 xyz / uint32 triples.  Returns
+    (squared distances float64 [P] or None, nearest triangles uint32 [P] or None, the report as a dict): a point beyond
+    max_distance has +inf and 0xFFFFFFFF."""
+    own = []
+
+    def on_device(a, dtype, count):
+        if isinstance(a, DeviceBuffer):
+            return a, (a.nbytes // 12 if count is None else count)
+        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
+        buf = DeviceBuffer(ctx, array=a) if a.size else None
+        if buf is not None:
+            own.append(buf)
+        return buf, (len(a) if count is None else count)
+
+    st = Deviation()
+    try:
+        dp, n = on_device(points, np.float32, num_points)
+        dv, nv = on_device(vertices, np.float32, num_vertices)
+        dt, nt = on_device(triangles, np.uint32, num_triangles)
+        od = DeviceBuffer(ctx, nbytes=8 * n) if want_distances and n else None
+        on = DeviceBuffer(ctx, nbytes=4 * n) if want_nearest and n else None
+        own.extend(x for x in (od, on) if x is not None)
+        check(lib().mlsgpu_hip_mesh_deviation(ctx.h, dp.ptr if dp else None, n, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt,
+                                              float(max_distance), od.ptr if od else None, on.ptr if on else None, C.byref(st)))
+        distance2 = (od.download(np.float64, n) if od else np.zeros(0, np.float64)) if want_distances else None
+        nearest = (on.download(np.uint32, n) if on else np.zeros(0, np.uint32)) if want_nearest else None
+    finally:
+        for buf in own:
+            buf.free()
+    return distance2, nearest, st.as_dict()
+
+
+def mesher_deviation(mesher, max_distance):
+    """Mesher.deviation as a function, beside mesh_deviation."""
+    return mesher.deviation(max_distance)
 
 
 def mesher_repair(mesher, flags=0):

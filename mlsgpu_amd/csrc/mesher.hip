@@ -552,6 +552,19 @@ struct mlsgpu_mesher
     DeviceArray<float> outNormals;              /* 3 per vertex */
     std::vector<char> normalsReady;             /* per dense chunk */
     std::vector<mlsgpu_normals_stats> normalsOf;
+    /* the kept reference (mlsgpu_hip_mesher_keep_reference): a copy of the results as they were, with its own chunk tables */
+    bool referenceKept = false;
+    DeviceArray<float> refVertices;             /* 3 per vertex */
+    DeviceArray<uint32_t> refTriangles;         /* 3 per triangle */
+    std::vector<uint64_t> refVStart, refTStart; /* [chunks + 1] */
+    void dropReference()
+    {
+        referenceKept = false;
+        refVertices.release();
+        refTriangles.release();
+        refVStart.clear();
+        refTStart.clear();
+    }
     /* boundary export (mlsgpu_hip_mesher_boundary): valid until the next add */
     bool analyzed = false;
     /* the export's keys and their roots land in PINNED memory (tens of MB: a copy into pageable memory goes through the
@@ -654,6 +667,8 @@ struct mlsgpu_mesher
     int finish(uint32_t *numChunks)             /* finalized, with the chunks writeOutput left (none for an empty sink) */
     {
         finalized = true;
+        if (referenceKept && refVStart.size() != chunkVStart.size())
+            dropReference();    /* another chunk list: the kept chunks no longer pair with these */
         if (numChunks)
             *numChunks = (uint32_t) outChunks.size();
         return MLSGPU_OK;
@@ -870,6 +885,7 @@ MLSGPU_API int mlsgpu_hip_mesher_reset(mlsgpu_mesher *m)
     m->chunkIds.clear();
     m->outChunks.clear();
     m->dropResults();
+    m->dropReference();
     m->analyzed = false;
     m->cache.drop();
     return MLSGPU_OK;
@@ -1483,6 +1499,100 @@ MLSGPU_API int mlsgpu_hip_mesher_repair(mlsgpu_mesher *m, uint32_t flags, mlsgpu
     m->chunkVStart = vStart;
     m->chunkTStart = tStart;
     m->dropNormals();           /* the chunks have changed and moved */
+    return MLSGPU_OK;
+}
+
+/* ---- the deviation report of the sink against a kept copy of itself (deviation.hip) ---- */
+
+MLSGPU_API int mlsgpu_hip_mesher_keep_reference(mlsgpu_mesher *m)
+{
+    REQUIRE(m != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
+    mlsgpu_ctx *const ctx = m->ctx;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    m->dropReference();
+    const uint64_t nv = m->chunkVStart.back(), nt = m->chunkTStart.back();
+    PROPAGATE(m->refVertices.alloc(3 * nv));
+    PROPAGATE(m->refTriangles.alloc(3 * nt));
+    if (nv > 0)
+        HIP_CHECK(hipMemcpyAsync(m->refVertices, m->outVertices, nv * 12, hipMemcpyDeviceToDevice, ctx->stream));
+    if (nt > 0)
+        HIP_CHECK(hipMemcpyAsync(m->refTriangles, m->outTriangles, nt * 12, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    m->refVStart = m->chunkVStart;
+    m->refTStart = m->chunkTStart;
+    m->referenceKept = true;
+    return MLSGPU_OK;
+}
+
+MLSGPU_API int mlsgpu_hip_mesher_drop_reference(mlsgpu_mesher *m)
+{
+    REQUIRE(m != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    m->dropReference();
+    return MLSGPU_OK;
+}
+
+/* *total += the report of dense chunk c: the counts add, the maximum and the lowest (chunk, point) that attains it are kept.
+ * The chunks come in ascending order, so a later chunk takes the maximum over only by exceeding it. */
+static void addDeviation(mlsgpu_deviation *total, const mlsgpu_deviation &one, uint64_t c)
+{
+    total->numPoints += one.numPoints;
+    total->numVertices += one.numVertices;
+    total->numTriangles += one.numTriangles;
+    total->outOfRangeTriangles += one.outOfRangeTriangles;
+    total->degenerateTriangles += one.degenerateTriangles;
+    total->beyond += one.beyond;
+    for (int k = 0; k < 16; k++)
+        total->histogram[k] += one.histogram[k];
+    total->sumQ += one.sumQ;
+    if (one.numPoints > 0)
+        total->scaleExponent = one.scaleExponent;       /* D is the same for every chunk, hence e */
+    if (one.within > 0 && (total->within == 0 || one.maxDistance2 > total->maxDistance2))
+    {
+        total->maxDistance2 = one.maxDistance2;
+        total->farthestChunk = c;
+        total->farthestPoint = one.farthestPoint;
+    }
+    total->within += one.within;
+}
+
+MLSGPU_API int mlsgpu_hip_mesher_deviation(mlsgpu_mesher *m, float maxDistance, mlsgpu_deviation *moved, mlsgpu_deviation *lost)
+{
+    REQUIRE(m != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized && m->referenceKept && m->refVStart.size() == m->chunkVStart.size(), MLSGPU_ERR_INVALID);
+    REQUIRE(std::isfinite(maxDistance) && maxDistance > 0.0f, MLSGPU_ERR_INVALID);
+    mlsgpu_ctx *const ctx = m->ctx;
+    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
+    mlsgpu_deviation *const totals[2] = {moved, lost};
+    for (mlsgpu_deviation *total : totals)
+        if (total != nullptr)
+        {
+            std::memset(total, 0, sizeof(*total));
+            total->farthestPoint = UINT64_MAX;
+            total->limit2 = (double) maxDistance * (double) maxDistance;
+        }
+    for (size_t c = 0; c < nc; c++)
+    {
+        const mlsgpu_mesher::Span now = m->span(c);
+        const mlsgpu_mesher::Span kept = {m->refVStart[c], m->refTStart[c], m->refVStart[c + 1] - m->refVStart[c],
+                                          m->refTStart[c + 1] - m->refTStart[c]};
+        mlsgpu_deviation one;
+        if (moved != nullptr)
+        {
+            PROPAGATE(mlsgpu_hip_mesh_deviation(ctx, m->outVertices + 3 * now.v0, now.nv, m->refVertices + 3 * kept.v0, kept.nv,
+                                                m->refTriangles + 3 * kept.t0, kept.nt, maxDistance, nullptr, nullptr, &one));
+            addDeviation(moved, one, c);
+        }
+        if (lost != nullptr)
+        {
+            PROPAGATE(mlsgpu_hip_mesh_deviation(ctx, m->refVertices + 3 * kept.v0, kept.nv, m->outVertices + 3 * now.v0, now.nv,
+                                                m->outTriangles + 3 * now.t0, now.nt, maxDistance, nullptr, nullptr, &one));
+            addDeviation(lost, one, c);
+        }
+    }
     return MLSGPU_OK;
 }
 

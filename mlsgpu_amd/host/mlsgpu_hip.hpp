@@ -24,6 +24,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/mlsgpu_hip.h"
@@ -172,6 +173,20 @@ inline mlsgpu_fill_stats fillHoles(const Context &ctx, const Buffer<float> &vert
     check(mlsgpu_hip_mesh_fill_holes(ctx.get(), vertices.get(), numVertices, triangles.get(), numTriangles, maxEdges, pinned,
                                      outVertices, capVertices, outTriangles, capTriangles, s));
     return *s;
+}
+
+/// The deviation report (mlsgpu_hip_mesh_deviation): the squared distance of numPoints points to the surface of a mesh, exact up
+/// to maxDistance, and its statistics; everything in device memory and nothing modified.  distance2 / nearest are NULL or get
+/// one entry per point (+infinity and 0xFFFFFFFF for a point beyond maxDistance).
+inline mlsgpu_deviation deviation(const Context &ctx, const Buffer<float> &points, std::uint64_t numPoints,
+                                  const Buffer<float> &vertices, std::uint64_t numVertices, const Buffer<std::uint32_t> &triangles,
+                                  std::uint64_t numTriangles, float maxDistance, double *distance2 = NULL,
+                                  std::uint32_t *nearest = NULL)
+{
+    mlsgpu_deviation st;
+    check(mlsgpu_hip_mesh_deviation(ctx.get(), points.get(), numPoints, vertices.get(), numVertices, triangles.get(), numTriangles,
+                                    maxDistance, distance2, nearest, &st));
+    return st;
 }
 
 /// Repair of a mesh in device memory (mlsgpu_hip_mesh_repair): triangles with a repeated directed side are dropped and pinched
@@ -718,6 +733,18 @@ public:
     {
         mlsgpu_fill_stats st;
         check(mlsgpu_hip_mesher_fill_holes(h, maxEdges, &st));
+        return st;
+    }
+    /// Keeps a copy of every chunk of the finalized mesher as it is now (mlsgpu_hip_mesher_keep_reference), for deviation() to
+    /// measure against: directly behind finalize(), before a stage that moves vertices.
+    void keepReference() { check(mlsgpu_hip_mesher_keep_reference(h)); }
+    void dropReference() { check(mlsgpu_hip_mesher_drop_reference(h)); }
+    /// How far the chunks are from the kept reference (mlsgpu_hip_mesher_deviation): first the current vertices against the kept
+    /// surface ("moved"), second the kept vertices against the current surface ("lost").  Changes nothing.
+    std::pair<mlsgpu_deviation, mlsgpu_deviation> deviation(float maxDistance)
+    {
+        std::pair<mlsgpu_deviation, mlsgpu_deviation> st;
+        check(mlsgpu_hip_mesher_deviation(h, maxDistance, &st.first, &st.second));
         return st;
     }
     /// Every output chunk of the finalized mesher repaired (mlsgpu_hip_mesher_repair): triangles with a repeated side dropped,
