@@ -12,7 +12,7 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--deviation D] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--deviation D] [--self-intersections] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
  * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
@@ -36,6 +36,10 @@
  *   vertices against the kept surface, and `lost`, the kept vertices against the output's surface -- the points within and
  *   beyond D, the largest and the RMS distance, and the distances that 50 % and 90 % of the points within stay under, read
  *   off a histogram of 16 bins.  Without such a stage `moved` is all zeros.
+ * --self-intersections (device weld only): after the last of those stages and before the write, the triangle pairs of every
+ *   output chunk that certainly pass through each other are counted where the chunk lies (pairs across chunks are not looked
+ *   for; touching and coplanar overlap are not reported): one line, `self-intersections pairs N triangles N chunks N first C A
+ *   B` -- the lowest chunk that has a pair and its lowest pair -- or `first -`.  The output files are the same with and without.
  * --normals (device weld only): every output chunk is written with its area-weighted vertex normals (nx ny nz after z),
  *   computed where the chunk lies -- after --simplify and --smooth when they are given; one line per chunk.
  */
@@ -84,7 +88,7 @@ int main(int argc, char **argv)
     std::uint32_t repairFlags = 0;
     long smoothIterations = 0, fillEdges = 0;
     float deviationDistance = 0.0f;
-    bool deviationGiven = false;
+    bool deviationGiven = false, intersectionsGiven = false;
     std::string tmpDir;
     std::vector<std::string> plys, rest;
     for (int i = 1; i < argc; i++)
@@ -129,6 +133,8 @@ int main(int argc, char **argv)
             deviationDistance = (float) atof(argv[++i]);
             deviationGiven = true;
         }
+        else if (a == "--self-intersections")
+            intersectionsGiven = true;
         else if (a == "--repair")
         {
             repairGiven = true;
@@ -151,7 +157,7 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--deviation D] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--deviation D] [--self-intersections] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
         return 2;
     }
@@ -208,6 +214,11 @@ int main(int argc, char **argv)
     if (deviationGiven && hostWeld)
     {
         std::cerr << "--deviation needs --weld device: the host welder's output is not on the device\n";
+        return 2;
+    }
+    if (intersectionsGiven && hostWeld)
+    {
+        std::cerr << "--self-intersections needs --weld device: the host welder's output is not on the device\n";
         return 2;
     }
     if (repairGiven && hostWeld)
@@ -288,6 +299,7 @@ int main(int argc, char **argv)
         mlsgpu_repair_stats repaired = mlsgpu_repair_stats();
         std::size_t repairedChunks = 0;
         std::pair<mlsgpu_deviation, mlsgpu_deviation> deviated;
+        mlsgpu_self_intersections crossed = mlsgpu_self_intersections();
         {
             BucketFarm farm(devices, cfg, 4 /* --device-threads */, 1, hostWeld ? NULL : &deviceMesher);
             if (hostWeld)
@@ -347,6 +359,8 @@ int main(int argc, char **argv)
             }
             if (deviationGiven)
                 deviated = deviceMesher.deviation(deviationDistance);
+            if (intersectionsGiven)
+                crossed = deviceMesher.selfIntersections();
             written = deviceMesher.writeChunks(chunks, [&](std::uint64_t) { return outName; }, comments, writeNormals);
             deviceMesher.getStatistics(st);
         }
@@ -397,6 +411,16 @@ int main(int argc, char **argv)
         {
             printDeviation("moved", deviated.first);
             printDeviation("lost", deviated.second);
+        }
+        if (intersectionsGiven)
+        {
+            std::printf("self-intersections pairs %llu triangles %llu chunks %llu first", (unsigned long long) crossed.crossingPairs,
+                        (unsigned long long) crossed.crossingTriangles, (unsigned long long) crossed.crossingChunks);
+            if (crossed.crossingPairs > 0)
+                std::printf(" %llu %llu %llu\n", (unsigned long long) crossed.lowestChunk, (unsigned long long) crossed.lowestA,
+                            (unsigned long long) crossed.lowestB);
+            else
+                std::printf(" -\n");
         }
         if (writeNormals)
             for (std::uint32_t i = 0; i < written; i++)

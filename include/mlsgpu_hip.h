@@ -1170,6 +1170,84 @@ int mlsgpu_hip_mesher_drop_reference(mlsgpu_mesher *mesher);
  * and for a refused maxDistance.  Changes nothing in the sink; works after any sequence of fill / simplify / repair / smooth. */
 int mlsgpu_hip_mesher_deviation(mlsgpu_mesher *mesher, float maxDistance, mlsgpu_deviation *moved, mlsgpu_deviation *lost);
 
+/* ---- self-intersection report of a device-resident mesh: the pairs of triangles that CERTAINLY pass through each other.
+ *      mlsgpu_hip_mesh_topology says whether a simplified, smoothed or filled mesh is still a manifold and
+ *      mlsgpu_hip_mesh_deviation how far it moved; a surface that a stage pulled through itself is a perfect manifold with a
+ *      small deviation, and this report is what sees it.  The reference has no counterpart.  Deterministic: all arithmetic is
+ *      in double on the floats converted exactly, every + - * below is ONE correctly rounded IEEE operation (no contraction),
+ *      dot(u, v) = (u.x*v.x + u.y*v.y) + u.z*v.z, cross(u, v) = (u.y*v.z - u.z*v.y, u.z*v.x - u.x*v.z, u.x*v.y - u.y*v.x),
+ *      and every field of the report is a count, a minimum or a maximum -- the output does not depend on the schedule, and the
+ *      order of the triangles changes only which indices are named.
+ *      1. A triangle with an index >= V is counted in outOfRangeTriangles (the index is compared, never used as an address);
+ *         otherwise a triangle that names a vertex twice is counted in degenerateTriangles.  Neither takes part.
+ *      2. Per axis, lo / hi are the smallest / largest of a triangle's three corner coordinates.  Two triangles A < B (by
+ *         index) that take part are a CANDIDATE pair iff, on every axis, loA <= hiB and loB <= hiA, as float comparisons.
+ *         This belongs to the contract, not to the implementation: any conservative spatial cull is then exact.
+ *         candidatePairs counts them, neighbours included.
+ *      3. The certain sign orient(a, b, c, x): r0 = a - x, r1 = b - x, r2 = c - x; det = dot(r0, cross(r1, r2)); perm is the
+ *         same expression with the six products of the cross and the three of the dot taken over absolute values -- with
+ *         p = (|r1.y*r2.z| + |r1.z*r2.y|, |r1.z*r2.x| + |r1.x*r2.z|, |r1.x*r2.y| + |r1.y*r2.x|), perm = (|r0.x|*p.x +
+ *         |r0.y|*p.y) + |r0.z|*p.z, a sum of non-negative terms in the same order.  The sign is 0 if |det| <= perm * 2^-48,
+ *         otherwise the sign of det.  The constant is derived, not tuned: the forward error of this evaluation on exact
+ *         differences is below 8 * 2^-53 * perm (Shewchuk's static filter for orient3d), the three rounded differences add
+ *         less than 2^-50 * perm; so, away from underflow, a sign that is not 0 is the true sign.  An x equal in coordinates
+ *         to a, b or c gives a zero row or a zero cross product, hence det == perm * 0 == 0 exactly: shared corners need no
+ *         index test, and welded duplicates behave like shared ones.
+ *      4. Side (p, q) PIERCES triangle (a, b, c) iff orient(a,b,c,p) * orient(a,b,c,q) < 0 and s0 = orient(p,q,a,b), s1 =
+ *         orient(p,q,b,c), s2 = orient(p,q,c,a) are all nonzero and equal.  (Every sign is a function of its twelve
+ *         coordinates alone: whether an implementation works out one it does not need cannot change a result.)
+ *      5. A candidate pair CROSSES iff one of A's sides (a, b), (b, c), (c, a) pierces B or one of B's pierces A, in the
+ *         stored corner order.
+ *      6. The report.  crossingPairs; crossingTriangles: the triangles with at least one partner; lowestA, lowestB: the
+ *         lexicographically lowest crossing pair, UINT64_MAX each if there is none; maxPartners: the most partners of one
+ *         triangle, and maxPartnersTriangle the lowest index that attains it, UINT64_MAX if there is no crossing.
+ *      THE LIMIT: the report says "these pairs certainly pass through each other" and is a lower bound.  Touching, coplanar
+ *      overlap and whatever rests on an uncertain sign are deliberately not reported; two neighbours folded flat onto each
+ *      other are not found (a smoothing fold shows through the next ring of triangles). ---- */
+typedef struct mlsgpu_self_intersections
+{
+    uint64_t numVertices, numTriangles;
+    uint64_t outOfRangeTriangles;   /* an index >= numVertices */
+    uint64_t degenerateTriangles;   /* in range, a vertex twice */
+    uint64_t candidatePairs;        /* step 2 */
+    uint64_t crossingPairs;         /* step 5 */
+    uint64_t crossingTriangles;
+    uint64_t lowestA, lowestB;
+    uint64_t maxPartners, maxPartnersTriangle;
+    uint64_t lowestChunk;           /* 0; mlsgpu_hip_mesher_self_intersections: the dense chunk of lowestA / lowestB */
+    uint64_t crossingChunks;        /* 0; mlsgpu_hip_mesher_self_intersections: the chunks with a crossing pair */
+} mlsgpu_self_intersections;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_self_intersections) == 104, "mlsgpu_self_intersections is part of the ABI");
+#else
+typedef char mlsgpu_self_intersections_size_is_104[sizeof(mlsgpu_self_intersections) == 104 ? 1 : -1];
+#endif
+/* The mesh of numVertices packed float xyz and numTriangles uint32 index triples on ctx's device, not modified.  dPartners is
+ * NULL or holds one uint32 per triangle: the number of its partners, 0 for a triangle that takes no part.  dPairs is NULL or
+ * has room for pairCapacity rows of two uint32 (A, B), A < B: the crossing pairs in ascending lexicographic order.  The
+ * capacity rule is mlsgpu_hip_mesh_fill_holes': with a dPairs and pairCapacity < crossingPairs the call returns
+ * MLSGPU_ERR_LENGTH, *out (and dPartners) complete and the list untouched, which is how a caller asks for the size; a NULL
+ * dPairs asks for no list and is no error.  MLSGPU_ERR_INVALID, before anything touches the device, for a NULL ctx or out;
+ * MLSGPU_ERR_LENGTH, before anything is allocated, unless numVertices < 2^32 and 3 * numTriangles < 2^32.
+ * MLSGPU_ERR_INVALID for a coordinate that is not finite (counted on the device).  MLSGPU_ERR_LENGTH if the grid's record
+ * count cannot be brought under 2^32, or for 2^32 crossing pairs or more where the list is taken.  No vertices or no triangles
+ * is not an error.  The cull is a sparse uniform grid over the mesh's box: a triangle has a record in every cell its box
+ * touches, and a pair is looked at in the one cell that holds the larger of the two boxes' lower corners per axis; the cell
+ * size starts at the mean extent of a triangle's box and is doubled until the records number at most max(2^20, 8 per
+ * triangle).  Scratch is allocated for the call and freed on return: 16 bytes per triangle (its cell count, where its records
+ * begin, the cell of its lower corner) and 4 more where dPartners is NULL, 24 bytes per grid record (the two sides of a
+ * sort's 64-bit keys and 32-bit values), 24 bytes per crossing pair where the list is written, the sorts' histograms and the
+ * scan's tile sums; MLSGPU_ERR_NOMEM if the device does not have it.  Blocks until the report is there. */
+int mlsgpu_hip_mesh_self_intersections(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices,
+                                       const uint32_t *dTriangles, uint64_t numTriangles, uint32_t *dPartners,
+                                       uint32_t *dPairs, uint64_t pairCapacity, mlsgpu_self_intersections *out);
+/* The same for a finalized device sink, chunk by chunk over the dense chunk list.  The counts add; maxPartners is the maximum
+ * and maxPartnersTriangle the triangle, within the lowest chunk that attains it, that the chunk's report names;
+ * lowestChunk / lowestA / lowestB name the lowest (dense chunk index, A, B) and crossingChunks counts the chunks that have a
+ * crossing pair.  THE LIMIT: crossings between triangles of different chunks are not looked for.  MLSGPU_ERR_INVALID before
+ * finalize.  Changes nothing in the sink; works after any sequence of fill / simplify / repair / smooth. */
+int mlsgpu_hip_mesher_self_intersections(mlsgpu_mesher *mesher, mlsgpu_self_intersections *out);
+
 /* ---- host mesh sink: OOCMesher's weld as the reference runs it, on the host (src/mesher.cpp:220-469, north_star:
  *      "welding stays on host").  add() is MesherBase::InputFunctor: local components of the block by union-find over
  *      two edges per triangle (computeLocalComponents, :220-236), clumps merged across blocks through the external

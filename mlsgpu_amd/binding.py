@@ -195,6 +195,18 @@ class Deviation(C.Structure):
         return out
 
 
+class SelfIntersections(C.Structure):
+    """mlsgpu_self_intersections: the sizes, what took no part, the candidate pairs of the box test, the pairs that certainly
+    cross and the triangles they touch, the lowest pair, the triangle with the most partners, and, for a sink, the chunks."""
+    _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
+                ("degenerateTriangles", C.c_uint64), ("candidatePairs", C.c_uint64), ("crossingPairs", C.c_uint64),
+                ("crossingTriangles", C.c_uint64), ("lowestA", C.c_uint64), ("lowestB", C.c_uint64), ("maxPartners", C.c_uint64),
+                ("maxPartnersTriangle", C.c_uint64), ("lowestChunk", C.c_uint64), ("crossingChunks", C.c_uint64)]
+
+    def as_dict(self):
+        return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
+
+
 class RepairStats(C.Structure):
     """mlsgpu_repair_stats: what took no part, the repeated sides and the triangles dropped for them, the vertices that went,
     split and came, the sizes of the result."""
@@ -428,6 +440,8 @@ def lib():
     sig("mlsgpu_hip_mesher_keep_reference", C.c_int, vp)
     sig("mlsgpu_hip_mesher_drop_reference", C.c_int, vp)
     sig("mlsgpu_hip_mesher_deviation", C.c_int, vp, C.c_float, P(Deviation), P(Deviation))
+    sig("mlsgpu_hip_mesh_self_intersections", C.c_int, vp, vp, u64, vp, u64, vp, vp, u64, P(SelfIntersections))
+    sig("mlsgpu_hip_mesher_self_intersections", C.c_int, vp, P(SelfIntersections))
     sig("mlsgpu_hip_write_ply_normals", C.c_int, C.c_char_p, vp, vp, u64, vp, u64, vp, u32)
     sig("mlsgpu_hip_mesher_write_ply_normals", C.c_int, vp, C.c_uint32, C.c_char_p, vp, C.c_uint32, u64)
     sig("mlsgpu_hip_bucket", C.c_int, vp, vp, u64, P(GridStruct), P(BucketParams), BUCKET_FN, vp, P(u64))
@@ -1013,6 +1027,14 @@ class Mesher:
         check(lib().mlsgpu_hip_mesher_deviation(self.h, float(max_distance), C.byref(moved), C.byref(lost)))
         return moved.as_dict(), lost.as_dict()
 
+    def self_intersections(self):
+        """The pairs of triangles that certainly pass through each other (mesh_self_intersections, chunk by chunk), as a
+        dict: the counts summed over the chunks, lowestChunk / lowestA / lowestB the lowest pair, crossingChunks the chunks
+        that have one.  Crossings between triangles of different chunks are not looked for.  Changes nothing in the sink."""
+        st = SelfIntersections()
+        check(lib().mlsgpu_hip_mesher_self_intersections(self.h, C.byref(st)))
+        return st.as_dict()
+
     def write_ply(self, i, path, comments=(), buffer_bytes=0):
         """Output chunk i straight from HBM into FastPly::Writer's file through a bounded pinned buffer."""
         arr = (C.c_char_p * max(len(comments), 1))(*[c.encode("ascii") for c in comments])
@@ -1316,6 +1338,51 @@ def mesh_deviation(ctx, points, vertices, triangles, max_distance, want_distance
 def mesher_deviation(mesher, max_distance):
     """Mesher.deviation as a function, beside mesh_deviation."""
     return mesher.deviation(max_distance)
+
+
+def mesh_self_intersections(ctx, vertices, triangles, want_partners=True, want_pairs=True, num_vertices=None, num_triangles=None):
+    """The self-intersection report on the device (mlsgpu_hip_mesh_self_intersections): the pairs of triangles that certainly
+    pass through each other -- a lower bound: touching, coplanar overlap and uncertain signs are not reported; the same
+    answer whatever the schedule.  `vertices` / `triangles` are numpy arrays (uploaded for the call) or DeviceBuffers of packed
+    float32 xyz / uint32 triples.  With want_pairs and a crossing, one call asks for the number of pairs and a second one
+    writes them.  Returns (partners uint32 [T] or None, pairs uint32 [N, 2] sorted or None, the report as a dict)."""
+    own = []
+
+    def on_device(a, dtype, count):
+        if isinstance(a, DeviceBuffer):
+            return a, (a.nbytes // 12 if count is None else count)
+        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
+        buf = DeviceBuffer(ctx, array=a) if a.size else None
+        if buf is not None:
+            own.append(buf)
+        return buf, (len(a) if count is None else count)
+
+    st = SelfIntersections()
+    try:
+        dv, nv = on_device(vertices, np.float32, num_vertices)
+        dt, nt = on_device(triangles, np.uint32, num_triangles)
+        op = DeviceBuffer(ctx, nbytes=4 * nt) if want_partners and nt else None
+        if op is not None:
+            own.append(op)
+        args = (ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, op.ptr if op else None)
+        check(lib().mlsgpu_hip_mesh_self_intersections(*args, None, 0, C.byref(st)))
+        pairs = np.zeros((0, 2), np.uint32) if want_pairs else None
+        if want_pairs and st.crossingPairs:
+            n = int(st.crossingPairs)
+            ol = DeviceBuffer(ctx, nbytes=8 * n)
+            own.append(ol)
+            check(lib().mlsgpu_hip_mesh_self_intersections(*args, ol.ptr, n, C.byref(st)))
+            pairs = ol.download(np.uint32, 2 * n).reshape(-1, 2)
+        partners = (op.download(np.uint32, nt) if op else np.zeros(0, np.uint32)) if want_partners else None
+    finally:
+        for buf in own:
+            buf.free()
+    return partners, pairs, st.as_dict()
+
+
+def mesher_self_intersections(mesher):
+    """Mesher.self_intersections as a function, beside mesh_self_intersections."""
+    return mesher.self_intersections()
 
 
 def mesher_repair(mesher, flags=0):

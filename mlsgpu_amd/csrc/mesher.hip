@@ -1596,6 +1596,47 @@ MLSGPU_API int mlsgpu_hip_mesher_deviation(mlsgpu_mesher *m, float maxDistance, 
     return MLSGPU_OK;
 }
 
+/* The self-intersection report (intersect.hip) of every dense chunk, added up: the chunks come in ascending order, so the
+ * first one with a crossing names the lowest pair and a later one takes the maximum over only by exceeding it. */
+MLSGPU_API int mlsgpu_hip_mesher_self_intersections(mlsgpu_mesher *m, mlsgpu_self_intersections *out)
+{
+    REQUIRE(m != nullptr && out != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
+    mlsgpu_ctx *const ctx = m->ctx;
+    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
+    std::memset(out, 0, sizeof(*out));
+    out->lowestA = out->lowestB = out->maxPartnersTriangle = UINT64_MAX;
+    for (size_t c = 0; c < nc; c++)
+    {
+        const auto [v0, t0, nv, nt] = m->span(c);
+        mlsgpu_self_intersections one;
+        PROPAGATE(mlsgpu_hip_mesh_self_intersections(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, nullptr, nullptr, 0,
+                                                     &one));
+        out->numVertices += one.numVertices;
+        out->numTriangles += one.numTriangles;
+        out->outOfRangeTriangles += one.outOfRangeTriangles;
+        out->degenerateTriangles += one.degenerateTriangles;
+        out->candidatePairs += one.candidatePairs;
+        out->crossingPairs += one.crossingPairs;
+        out->crossingTriangles += one.crossingTriangles;
+        if (one.crossingPairs == 0)
+            continue;
+        if (out->crossingChunks++ == 0)
+        {
+            out->lowestChunk = c;
+            out->lowestA = one.lowestA;
+            out->lowestB = one.lowestB;
+        }
+        if (one.maxPartners > out->maxPartners)
+        {
+            out->maxPartners = one.maxPartners;
+            out->maxPartnersTriangle = one.maxPartnersTriangle;
+        }
+    }
+    return MLSGPU_OK;
+}
+
 /* The normals (normals.hip) of dense chunk c of a finalized sink, computed where the chunk lies at the first request.  Under
  * the mutex. */
 int mlsgpu_mesher::chunkNormals(uint32_t c, const float **dNormals, mlsgpu_normals_stats *out)

@@ -189,6 +189,23 @@ inline mlsgpu_deviation deviation(const Context &ctx, const Buffer<float> &point
     return st;
 }
 
+/// The self-intersection report (mlsgpu_hip_mesh_self_intersections): the pairs of triangles of a mesh in device memory that
+/// certainly pass through each other -- a lower bound: touching, coplanar overlap and uncertain signs are not reported.
+/// partners is NULL or gets one count per triangle; pairs is NULL or has room for pairCapacity rows (A, B) and gets the crossing
+/// pairs in ascending order.  With a pairs and too little room the list stays untouched, *st is complete (when given) and
+/// std::length_error is thrown: that is how to ask for the size.
+inline mlsgpu_self_intersections selfIntersections(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
+                                                   const Buffer<std::uint32_t> &triangles, std::uint64_t numTriangles,
+                                                   std::uint32_t *partners = NULL, std::uint32_t *pairs = NULL,
+                                                   std::uint64_t pairCapacity = 0, mlsgpu_self_intersections *st = NULL)
+{
+    mlsgpu_self_intersections own;
+    mlsgpu_self_intersections *const s = st != NULL ? st : &own;
+    check(mlsgpu_hip_mesh_self_intersections(ctx.get(), vertices.get(), numVertices, triangles.get(), numTriangles, partners, pairs,
+                                             pairCapacity, s));
+    return *s;
+}
+
 /// Repair of a mesh in device memory (mlsgpu_hip_mesh_repair): triangles with a repeated directed side are dropped and pinched
 /// vertices split (flags: 0 or MLSGPU_REPAIR_SPLIT_PINCHES), so that the topology report calls the result manifold.
 /// outVertices / outTriangles have room for capVertices / capTriangles and do not overlap the inputs; outSource is NULL or gets
@@ -745,6 +762,14 @@ public:
     {
         std::pair<mlsgpu_deviation, mlsgpu_deviation> st;
         check(mlsgpu_hip_mesher_deviation(h, maxDistance, &st.first, &st.second));
+        return st;
+    }
+    /// The triangle pairs of each chunk that certainly pass through each other (mlsgpu_hip_mesher_self_intersections), added up
+    /// over the chunks; pairs across chunks are not looked for.  Changes nothing.
+    mlsgpu_self_intersections selfIntersections()
+    {
+        mlsgpu_self_intersections st;
+        check(mlsgpu_hip_mesher_self_intersections(h, &st));
         return st;
     }
     /// Every output chunk of the finalized mesher repaired (mlsgpu_hip_mesher_repair): triangles with a repeated side dropped,
