@@ -12,7 +12,7 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--deviation D] [--self-intersections] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
  * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
@@ -40,9 +40,14 @@
  *   output chunk that certainly pass through each other are counted where the chunk lies (pairs across chunks are not looked
  *   for; touching and coplanar overlap are not reported): one line, `self-intersections pairs N triangles N chunks N first C A
  *   B` -- the lowest chunk that has a pair and its lowest pair -- or `first -`.  The output files are the same with and without.
+ * --compact BITS (device weld only; BITS 32 or 8..24): every output chunk comes back as a compact blob -- encoded where it lies,
+ *   one copy across the link, decoded on the host -- and the decoded arrays go to the same PLY writer.  One line, `compact bits B
+ *   raw N blob N ratio R exceptions N step X Y Z` (bytes summed over the chunks, the largest quantisation step per axis).  With
+ *   32 the files are byte-identical to those written without the flag; below, vertices move by at most half a step.
  * --normals (device weld only): every output chunk is written with its area-weighted vertex normals (nx ny nz after z),
  *   computed where the chunk lies -- after --simplify and --smooth when they are given; one line per chunk.
  */
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -89,6 +94,7 @@ int main(int argc, char **argv)
     long smoothIterations = 0, fillEdges = 0;
     float deviationDistance = 0.0f;
     bool deviationGiven = false, intersectionsGiven = false;
+    long compactBits = 0;
     std::string tmpDir;
     std::vector<std::string> plys, rest;
     for (int i = 1; i < argc; i++)
@@ -135,6 +141,15 @@ int main(int argc, char **argv)
         }
         else if (a == "--self-intersections")
             intersectionsGiven = true;
+        else if (a == "--compact" && i + 1 < argc)
+        {
+            compactBits = atol(argv[++i]);
+            if (compactBits != 32 && (compactBits < 8 || compactBits > 24))
+            {
+                std::cerr << "--compact takes 32 or 8..24\n";
+                return 2;
+            }
+        }
         else if (a == "--repair")
         {
             repairGiven = true;
@@ -157,7 +172,7 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--deviation D] [--self-intersections] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
         return 2;
     }
@@ -219,6 +234,12 @@ int main(int argc, char **argv)
     if (intersectionsGiven && hostWeld)
     {
         std::cerr << "--self-intersections needs --weld device: the host welder's output is not on the device\n";
+        return 2;
+    }
+    if (compactBits != 0 && (hostWeld || writeNormals))
+    {
+        std::cerr << (hostWeld ? "--compact needs --weld device: the host welder's output is not on the device\n"
+                               : "--compact carries no normals: not with --normals\n");
         return 2;
     }
     if (repairGiven && hostWeld)
@@ -300,6 +321,8 @@ int main(int argc, char **argv)
         std::size_t repairedChunks = 0;
         std::pair<mlsgpu_deviation, mlsgpu_deviation> deviated;
         mlsgpu_self_intersections crossed = mlsgpu_self_intersections();
+        mlsgpu_compact_stats compacted = mlsgpu_compact_stats();
+        std::uint64_t compactRaw = 0;
         {
             BucketFarm farm(devices, cfg, 4 /* --device-threads */, 1, hostWeld ? NULL : &deviceMesher);
             if (hostWeld)
@@ -361,7 +384,28 @@ int main(int argc, char **argv)
                 deviated = deviceMesher.deviation(deviationDistance);
             if (intersectionsGiven)
                 crossed = deviceMesher.selfIntersections();
-            written = deviceMesher.writeChunks(chunks, [&](std::uint64_t) { return outName; }, comments, writeNormals);
+            if (compactBits != 0)
+            {
+                // encode -> copy -> decode, then the writer of host arrays: the same file as straight from HBM
+                std::vector<std::uint32_t> blob, triangles;
+                std::vector<float> vertices;
+                const char *const comment = comments[0].c_str();
+                for (std::uint32_t i = 0; i < chunks; i++)
+                {
+                    const mlsgpu_compact_stats one = deviceMesher.chunkCompact(i, (std::uint32_t) compactBits, blob);
+                    compactDecode(blob.data(), one.blobBytes, vertices, triangles);
+                    check(mlsgpu_hip_write_ply(outName.c_str(), vertices.data(), one.numVertices, triangles.data(), one.numTriangles,
+                                               &comment, 1));
+                    compactRaw += 12 * (one.numVertices + one.numTriangles);
+                    compacted.blobBytes += one.blobBytes;
+                    compacted.exceptions += one.exceptions;
+                    for (int a = 0; a < 3; a++)
+                        compacted.step[a] = std::max(compacted.step[a], one.step[a]);
+                }
+                written = chunks;
+            }
+            else
+                written = deviceMesher.writeChunks(chunks, [&](std::uint64_t) { return outName; }, comments, writeNormals);
             deviceMesher.getStatistics(st);
         }
         std::printf("files in %zu splats %llu grid %d..%d %d..%d %d..%d bins %zu devices %zu weld %s files %zu vertices %llu "
@@ -422,6 +466,11 @@ int main(int argc, char **argv)
             else
                 std::printf(" -\n");
         }
+        if (compactBits != 0)
+            std::printf("compact bits %ld raw %llu blob %llu ratio %.4f exceptions %llu step %.9g %.9g %.9g\n", compactBits,
+                        (unsigned long long) compactRaw, (unsigned long long) compacted.blobBytes,
+                        compactRaw ? (double) compacted.blobBytes / (double) compactRaw : 0.0, (unsigned long long) compacted.exceptions,
+                        compacted.step[0], compacted.step[1], compacted.step[2]);
         if (writeNormals)
             for (std::uint32_t i = 0; i < written; i++)
             {

@@ -1248,6 +1248,93 @@ int mlsgpu_hip_mesh_self_intersections(mlsgpu_ctx *ctx, const float *dVertices, 
  * finalize.  Changes nothing in the sink; works after any sequence of fill / simplify / repair / smooth. */
 int mlsgpu_hip_mesher_self_intersections(mlsgpu_mesher *mesher, mlsgpu_self_intersections *out);
 
+/* ---- compact read-back of a device-resident mesh: the SAME mesh in fewer bytes for the link to the host.  A chunk leaves HBM
+ *      as 12 bytes per vertex and 12 per triangle; the sink numbers vertices block by block and slice by slice, so the indices of
+ *      64 consecutive triangles lie within a few thousand of each other, and a frame-of-reference code per 64 triangles with an
+ *      exception list holds them in about a third.  Triangles are lossless; vertices are bit-exact at vertexBits = 32 and
+ *      quantised to a stated bound below.  The reference has no counterpart.  THE FORMAT, version 1: a blob is a sequence of
+ *      little-endian 32-bit words; its bytes are a function of the input arrays and vertexBits only (every field is a minimum, a
+ *      count, a scan or an OR of disjoint bits), and all padding bits are zero.  A BIT STREAM of values of b bits: value i
+ *      occupies bits [i*b, (i+1)*b), bit j of the stream is bit (j mod 32) of word j / 32, the stream ends with the word that
+ *      holds its last bit.
+ *      1. Header, 16 words: 0 magic "MLSC" (0x43534C4D); 1 version 1; 2 vertexBits; 3 group size 64; 4-5 numVertices (low word
+ *         first); 6-7 numTriangles; 8-10 lo and 11-13 hi as float bits per axis; 14-15 the words of the whole blob.
+ *      2. Vertex section.  vertexBits b is 32 or lies in 8..24.  b = 32: the 3 V floats copied as bits (any bit pattern), lo = hi
+ *         = 0.  b < 32: lo / hi per axis are the minimum / maximum as INTEGERS after the order-preserving map of float bits to
+ *         uint32 (u = bits ^ 0xFFFFFFFF for a set sign bit, bits | 0x80000000 otherwise: a total order with -0 < +0), both +0 for
+ *         no vertices.  d = double(hi) - double(lo); q = 0 if d = 0, otherwise q = floor((double(x) - double(lo)) *
+ *         (double(2^b - 1) / d) + 0.5) clamped to [0, 2^b - 1], every operation ONE correctly rounded double operation (no
+ *         contraction).  The section is the bit stream of the 3 V values q of b bits, vertex v axis a being value 3 v + a.
+ *         Decoding: x' = float(double(lo) + double(q) * (d / double(2^b - 1))), and |x' - x| <= 0.5 * d / (2^b - 1) +
+ *         ulp32(max(|lo|, |hi|)) per axis.
+ *      3. Triangle section.  G = ceil(T / 64) groups of n <= 64 consecutive triangles.  G + 1 offsets, in words relative to the
+ *         first group record, the first 0 and the last the length of all records; then the records.  A group has 3 n SLOTS, slot
+ *         3 t + k being corner k of its triangle t; base is its smallest index and a slot's value v = index - base.  For a width
+ *         w in 1..31, v is INLINE if v < 2^w - 1; otherwise the slot holds the escape 2^w - 1 and v joins the group's exception
+ *         list, in slot order.  w = 32 has no exceptions.  cost(w) = 4 * ceil(3 n w / 32) + 4 * exceptions(w), and the group
+ *         takes the smallest w of minimum cost.  A record: base; the word w | exceptions << 8; the bit stream of the 3 n slot
+ *         values of w bits; the exceptions.  Indices are not compared with numVertices: any uint32 triples come back bit for bit
+ *         and in their order.
+ *      Normals are not part of the format. ---- */
+#define MLSGPU_COMPACT_MAGIC 0x43534C4Du
+#define MLSGPU_COMPACT_VERSION 1u
+#define MLSGPU_COMPACT_GROUP 64u
+#define MLSGPU_COMPACT_HEADER_WORDS 16u
+typedef struct mlsgpu_compact_stats
+{
+    uint64_t numVertices, numTriangles;
+    uint64_t vertexBits;
+    uint64_t blobBytes;             /* 64 + vertexBytes + triangleBytes */
+    uint64_t vertexBytes;           /* the vertex section */
+    uint64_t triangleBytes;         /* offsets and records */
+    uint64_t groups;
+    uint64_t exceptions;            /* over all groups */
+    uint64_t widthHistogram[33];    /* [w]: the groups of width w; [0] stays 0 */
+    double step[3];                 /* d / (2^b - 1) per axis: a decoded coordinate is lo + q * step; 0 for b = 32 or d = 0 */
+} mlsgpu_compact_stats;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_compact_stats) == 352, "mlsgpu_compact_stats is part of the ABI");
+#else
+typedef char mlsgpu_compact_stats_size_is_352[sizeof(mlsgpu_compact_stats) == 352 ? 1 : -1];
+#endif
+/* Encodes the mesh of numVertices packed float xyz and numTriangles uint32 index triples on ctx's device, not modified, into
+ * the capacityBytes at dOut (device memory, 4-byte aligned, not overlapping the inputs).  The capacity rule is
+ * mlsgpu_hip_mesh_fill_holes': with a dOut that is NULL or holds fewer than blobBytes, the planning pass alone runs, *stats is
+ * complete, the output is untouched and the call returns MLSGPU_ERR_LENGTH, which is how a caller asks for the size; bytes of
+ * dOut beyond blobBytes are never written.  MLSGPU_ERR_INVALID, before anything touches the device, for a NULL ctx or stats, a
+ * vertexBits that is not 32 or in 8..24, a dOut that is not 4-byte aligned; MLSGPU_ERR_LENGTH, before anything is allocated,
+ * unless numVertices < 2^32, 3 * numTriangles < 2^32 and 194 words for every group stay below 2^32 (the longest record a group
+ * can have: a record stream of 2^32 words or more cannot be addressed by its offsets).  MLSGPU_ERR_INVALID for vertexBits < 32
+ * and a coordinate that is not finite (counted on the device); at 32 any bits pass.  No vertices or no triangles is not an
+ * error.  Three kernels plan: the extents (integer min / max), one wave per group (base by a wave minimum, the exceptions of
+ * every width from the bit lengths of the 192 values, the arg-min cost) and a scan of the record lengths; three write: header,
+ * vertices and groups, each bit stream assembled in a tile of on-chip memory and stored as whole words.  Scratch is allocated
+ * for the call and freed on return: 12 bytes per group (base, width and exceptions, offset), the scan's tile sums (4 bytes per
+ * 2048 groups) and 312 bytes of counters; MLSGPU_ERR_NOMEM if the device does not have it.  Blocks until the blob is there. */
+int mlsgpu_hip_mesh_compact(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices, const uint32_t *dTriangles,
+                            uint64_t numTriangles, uint32_t vertexBits, void *dOut, uint64_t capacityBytes,
+                            mlsgpu_compact_stats *stats);
+/* Output chunk i of a finalized device sink (after any fill / simplify / repair / smooth), encoded into device scratch of
+ * blobBytes and copied into the caller's HOST memory, pinned or not.  The same capacity rule: a NULL hostBlob or too few
+ * capacityBytes return MLSGPU_ERR_LENGTH with *stats complete and nothing written or allocated for the blob.
+ * MLSGPU_ERR_INVALID before finalize or for an i that is no output chunk.  Leaves the sink's arrays and cached normals
+ * untouched. */
+int mlsgpu_hip_mesher_chunk_compact(mlsgpu_mesher *mesher, uint32_t i, uint32_t vertexBits, void *hostBlob, uint64_t capacityBytes,
+                                    mlsgpu_compact_stats *stats);
+/* The host side: no GPU and no HIP call.  The blob is UNTRUSTED: both calls validate every header field, every offset and every
+ * record of the `bytes` at `blob` (4-byte aligned) before anything is written, and return MLSGPU_ERR_FORMAT unless: bytes is
+ * exactly the header's word count times 4; magic, version and group size are the format's; vertexBits is 32 or in 8..24;
+ * numVertices < 2^32 and 3 * numTriangles < 2^32; lo = hi = 0 as bits at 32, both finite with lo <= hi in the integer order
+ * below; the sections fill the blob exactly; the offsets start at 0, rise by exactly each record's length and end at the
+ * records' length; every w is in 1..32; exceptions <= slots, and the escapes among the slots number the exceptions (none at
+ * w = 32); base + v does not wrap.  Nothing outside the given buffers is read or written.  MLSGPU_ERR_INVALID for a NULL or
+ * misaligned blob or a NULL stats / output that is needed.  _info fills *stats from the blob (step as the decoder uses it).
+ * _decode writes numVertices packed xyz to `vertices` and numTriangles triples to `triangles` (the caller sizes them from
+ * _info); groups and vertex ranges are spread over `threads` std::threads, 0 meaning 8, at most 64, for the validation as
+ * for the writing. */
+int mlsgpu_hip_compact_info(const void *blob, uint64_t bytes, mlsgpu_compact_stats *stats);
+int mlsgpu_hip_compact_decode(const void *blob, uint64_t bytes, float *vertices, uint32_t *triangles, uint32_t threads);
+
 /* ---- host mesh sink: OOCMesher's weld as the reference runs it, on the host (src/mesher.cpp:220-469, north_star:
  *      "welding stays on host").  add() is MesherBase::InputFunctor: local components of the block by union-find over
  *      two edges per triangle (computeLocalComponents, :220-236), clumps merged across blocks through the external

@@ -207,6 +207,20 @@ class SelfIntersections(C.Structure):
         return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
 
 
+class CompactStats(C.Structure):
+    """mlsgpu_compact_stats: the sizes, the blob's bytes and those of its two sections, the groups and their exceptions, the
+    groups per width, the quantisation step per axis."""
+    _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("vertexBits", C.c_uint64), ("blobBytes", C.c_uint64),
+                ("vertexBytes", C.c_uint64), ("triangleBytes", C.c_uint64), ("groups", C.c_uint64), ("exceptions", C.c_uint64),
+                ("widthHistogram", C.c_uint64 * 33), ("step", C.c_double * 3)]
+
+    def as_dict(self):
+        out = dict((name, int(getattr(self, name))) for name, _ in self._fields_[:8])
+        out["widthHistogram"] = [int(x) for x in self.widthHistogram]
+        out["step"] = [float(x) for x in self.step]
+        return out
+
+
 class RepairStats(C.Structure):
     """mlsgpu_repair_stats: what took no part, the repeated sides and the triangles dropped for them, the vertices that went,
     split and came, the sizes of the result."""
@@ -442,6 +456,10 @@ def lib():
     sig("mlsgpu_hip_mesher_deviation", C.c_int, vp, C.c_float, P(Deviation), P(Deviation))
     sig("mlsgpu_hip_mesh_self_intersections", C.c_int, vp, vp, u64, vp, u64, vp, vp, u64, P(SelfIntersections))
     sig("mlsgpu_hip_mesher_self_intersections", C.c_int, vp, P(SelfIntersections))
+    sig("mlsgpu_hip_mesh_compact", C.c_int, vp, vp, u64, vp, u64, u32, vp, u64, P(CompactStats))
+    sig("mlsgpu_hip_mesher_chunk_compact", C.c_int, vp, u32, u32, vp, u64, P(CompactStats))
+    sig("mlsgpu_hip_compact_info", C.c_int, vp, u64, P(CompactStats))
+    sig("mlsgpu_hip_compact_decode", C.c_int, vp, u64, vp, vp, u32)
     sig("mlsgpu_hip_write_ply_normals", C.c_int, C.c_char_p, vp, vp, u64, vp, u64, vp, u32)
     sig("mlsgpu_hip_mesher_write_ply_normals", C.c_int, vp, C.c_uint32, C.c_char_p, vp, C.c_uint32, u64)
     sig("mlsgpu_hip_bucket", C.c_int, vp, vp, u64, P(GridStruct), P(BucketParams), BUCKET_FN, vp, P(u64))
@@ -1035,6 +1053,23 @@ class Mesher:
         check(lib().mlsgpu_hip_mesher_self_intersections(self.h, C.byref(st)))
         return st.as_dict()
 
+    def chunk_compact(self, i, vertex_bits=32, out=None):
+        """Output chunk i as a compact blob (mesh_compact) in host memory: encoded where the chunk lies and copied across in
+        one piece.  `out` is None (one call asks for the size, a numpy array is made) or a PinnedBuffer with room for the
+        blob.  Returns (the blob as a uint32 array -- a view of `out` where given --, the statistics as a dict).  Changes
+        nothing in the sink."""
+        st = CompactStats()
+        if out is None:
+            rc = lib().mlsgpu_hip_mesher_chunk_compact(self.h, i, vertex_bits, None, 0, C.byref(st))
+            if rc != 2:             # the size query ends in MLSGPU_ERR_LENGTH
+                check(rc)
+            blob = np.empty(int(st.blobBytes) // 4, np.uint32)
+            check(lib().mlsgpu_hip_mesher_chunk_compact(self.h, i, vertex_bits, _p(blob), blob.nbytes, C.byref(st)))
+            return blob, st.as_dict()
+        check(lib().mlsgpu_hip_mesher_chunk_compact(self.h, i, vertex_bits, out.ptr, out.nbytes, C.byref(st)))
+        words = int(st.blobBytes) // 4
+        return np.ctypeslib.as_array(C.cast(out.ptr, C.POINTER(C.c_uint32)), (words,)), st.as_dict()
+
     def write_ply(self, i, path, comments=(), buffer_bytes=0):
         """Output chunk i straight from HBM into FastPly::Writer's file through a bounded pinned buffer."""
         arr = (C.c_char_p * max(len(comments), 1))(*[c.encode("ascii") for c in comments])
@@ -1383,6 +1418,60 @@ def mesh_self_intersections(ctx, vertices, triangles, want_partners=True, want_p
 def mesher_self_intersections(mesher):
     """Mesher.self_intersections as a function, beside mesh_self_intersections."""
     return mesher.self_intersections()
+
+
+def mesh_compact(ctx, vertices, triangles, vertex_bits=32, num_vertices=None, num_triangles=None):
+    """The compact blob of a mesh, made on the device (mlsgpu_hip_mesh_compact): triangles lossless, vertices bit-exact at
+    vertex_bits = 32 and quantised to 8..24 bits otherwise.  `vertices` / `triangles` are numpy arrays (uploaded for the call) or
+    DeviceBuffers of packed float32 xyz / uint32 triples.  One call asks for the size, a second one writes.  Returns (the blob as
+    a uint32 array, the statistics as a dict)."""
+    own = []
+
+    def on_device(a, dtype, count):
+        if isinstance(a, DeviceBuffer):
+            return a, (a.nbytes // 12 if count is None else count)
+        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
+        buf = DeviceBuffer(ctx, array=a) if a.size else None
+        if buf is not None:
+            own.append(buf)
+        return buf, (len(a) if count is None else count)
+
+    st = CompactStats()
+    try:
+        dv, nv = on_device(vertices, np.float32, num_vertices)
+        dt, nt = on_device(triangles, np.uint32, num_triangles)
+        args = (ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, vertex_bits)
+        rc = lib().mlsgpu_hip_mesh_compact(*args, None, 0, C.byref(st))
+        if rc != 2:                 # the size query ends in MLSGPU_ERR_LENGTH
+            check(rc)
+        out = DeviceBuffer(ctx, nbytes=int(st.blobBytes))
+        own.append(out)
+        check(lib().mlsgpu_hip_mesh_compact(*args, out.ptr, out.nbytes, C.byref(st)))
+        blob = out.download(np.uint32, int(st.blobBytes) // 4)
+    finally:
+        for buf in own:
+            buf.free()
+    return blob, st.as_dict()
+
+
+def compact_info(blob):
+    """The statistics of a compact blob (bytes or a uint32 array), validated on the host (mlsgpu_hip_compact_info)."""
+    blob = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob)
+    st = CompactStats()
+    check(lib().mlsgpu_hip_compact_info(_p(blob), blob.nbytes, C.byref(st)))
+    return st.as_dict()
+
+
+def compact_decode(blob, threads=0):
+    """(vertices float32 [V, 3], triangles uint32 [T, 3]) of a compact blob (bytes or a uint32 array), decoded on the host by
+    `threads` threads, 0 meaning 8 (mlsgpu_hip_compact_decode).  The blob is validated first: FormatError."""
+    blob = np.ascontiguousarray(np.frombuffer(blob, np.uint8) if isinstance(blob, (bytes, bytearray)) else blob)
+    st = CompactStats()
+    check(lib().mlsgpu_hip_compact_info(_p(blob), blob.nbytes, C.byref(st)))
+    v = np.empty((int(st.numVertices), 3), np.float32)
+    t = np.empty((int(st.numTriangles), 3), np.uint32)
+    check(lib().mlsgpu_hip_compact_decode(_p(blob), blob.nbytes, _p(v), _p(t), threads))
+    return v, t
 
 
 def mesher_repair(mesher, flags=0):

@@ -332,6 +332,12 @@ static inline uint32_t roundUp(uint32_t a, uint32_t b) { return (a + b - 1) / b 
  * bit, a row of another chunk, 0 for the others; chunk c holds the rows [starts[c], starts[c + 1]) (host memory).  Blocks. */
 int seamMask(mlsgpu_ctx *ctx, const float *dVertices, uint64_t n, const uint64_t *starts, uint32_t numChunks, uint8_t *dPinned);
 
+/* compact.hip, for the sink's compact read-back (mesher.hip): mlsgpu_hip_mesh_compact with the blob going to dOut (device
+ * memory) or, through device scratch of the blob's size, to hostOut (host memory, pinned or not); the one that is given holds
+ * `capacity` bytes.  Blocks. */
+int compactMesh(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices, const uint32_t *dTriangles, uint64_t numTriangles,
+                uint32_t vertexBits, void *dOut, void *hostOut, uint64_t capacity, mlsgpu_compact_stats *stats);
+
 /* ---------------------------------------------------------------- device helpers */
 
 #ifdef __HIPCC__

@@ -1637,6 +1637,18 @@ MLSGPU_API int mlsgpu_hip_mesher_self_intersections(mlsgpu_mesher *m, mlsgpu_sel
     return MLSGPU_OK;
 }
 
+/* Output chunk i encoded where it lies (compact.hip) and copied to the caller's host memory; only reads the sink. */
+MLSGPU_API int mlsgpu_hip_mesher_chunk_compact(mlsgpu_mesher *m, uint32_t i, uint32_t vertexBits, void *hostBlob, uint64_t capacityBytes,
+                                               mlsgpu_compact_stats *stats)
+{
+    REQUIRE(m != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized && i < m->outChunks.size(), MLSGPU_ERR_INVALID);
+    const mlsgpu_mesher::Span s = m->span(m->outChunks[i]);
+    return compactMesh(m->ctx, m->outVertices + 3 * s.v0, s.nv, m->outTriangles + 3 * s.t0, s.nt, vertexBits, nullptr, hostBlob,
+                       capacityBytes, stats);
+}
+
 /* The normals (normals.hip) of dense chunk c of a finalized sink, computed where the chunk lies at the first request.  Under
  * the mutex. */
 int mlsgpu_mesher::chunkNormals(uint32_t c, const float **dNormals, mlsgpu_normals_stats *out)

@@ -206,6 +206,38 @@ inline mlsgpu_self_intersections selfIntersections(const Context &ctx, const Buf
     return *s;
 }
 
+/// The compact blob of a mesh in device memory (mlsgpu_hip_mesh_compact), written to the capacityBytes of device memory at out:
+/// triangles lossless, vertices bit-exact at vertexBits = 32 and quantised at 8..24.  With a NULL out or too little room nothing
+/// is written, *st is complete (when given) and std::length_error is thrown: that is how to ask for the size.
+inline mlsgpu_compact_stats compact(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
+                                    const Buffer<std::uint32_t> &triangles, std::uint64_t numTriangles, std::uint32_t vertexBits,
+                                    void *out, std::uint64_t capacityBytes, mlsgpu_compact_stats *st = NULL)
+{
+    mlsgpu_compact_stats own;
+    mlsgpu_compact_stats *const s = st != NULL ? st : &own;
+    check(mlsgpu_hip_mesh_compact(ctx.get(), vertices.get(), numVertices, triangles.get(), numTriangles, vertexBits, out, capacityBytes, s));
+    return *s;
+}
+
+/// What a compact blob in host memory holds (mlsgpu_hip_compact_info): validated first, Error(MLSGPU_ERR_FORMAT) if malformed.
+inline mlsgpu_compact_stats compactInfo(const void *blob, std::uint64_t bytes)
+{
+    mlsgpu_compact_stats st;
+    check(mlsgpu_hip_compact_info(blob, bytes, &st));
+    return st;
+}
+
+/// A compact blob in host memory decoded on `threads` host threads, 0 meaning 8 (mlsgpu_hip_compact_decode): no GPU involved.
+inline mlsgpu_compact_stats compactDecode(const void *blob, std::uint64_t bytes, std::vector<float> &vertices,
+                                          std::vector<std::uint32_t> &triangles, std::uint32_t threads = 0)
+{
+    const mlsgpu_compact_stats st = compactInfo(blob, bytes);
+    vertices.resize(3 * st.numVertices);
+    triangles.resize(3 * st.numTriangles);
+    check(mlsgpu_hip_compact_decode(blob, bytes, vertices.data(), triangles.data(), threads));
+    return st;
+}
+
 /// Repair of a mesh in device memory (mlsgpu_hip_mesh_repair): triangles with a repeated directed side are dropped and pinched
 /// vertices split (flags: 0 or MLSGPU_REPAIR_SPLIT_PINCHES), so that the topology report calls the result manifold.
 /// outVertices / outTriangles have room for capVertices / capTriangles and do not overlap the inputs; outSource is NULL or gets
@@ -770,6 +802,18 @@ public:
     {
         mlsgpu_self_intersections st;
         check(mlsgpu_hip_mesher_self_intersections(h, &st));
+        return st;
+    }
+    /// Output chunk i as a compact blob in host memory (mlsgpu_hip_mesher_chunk_compact): encoded where the chunk lies, one copy
+    /// across.  One call asks for the size, the second fills `blob`.  Changes nothing.
+    mlsgpu_compact_stats chunkCompact(std::uint32_t i, std::uint32_t vertexBits, std::vector<std::uint32_t> &blob)
+    {
+        mlsgpu_compact_stats st;
+        const int rc = mlsgpu_hip_mesher_chunk_compact(h, i, vertexBits, NULL, 0, &st);
+        if (rc != MLSGPU_ERR_LENGTH)        // the size query ends in the length error
+            check(rc);
+        blob.resize(st.blobBytes / 4);
+        check(mlsgpu_hip_mesher_chunk_compact(h, i, vertexBits, blob.data(), st.blobBytes, &st));
         return st;
     }
     /// Every output chunk of the finalized mesher repaired (mlsgpu_hip_mesher_repair): triangles with a repeated side dropped,
