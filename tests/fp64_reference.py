@@ -19,6 +19,11 @@ bit 2 = z), on a float32 field [z, y, x]: a corner is outside iff iso >= 0 (so -
 eight corners are finite.  The tetrahedra's edges are the lattice segments p -> p + d for the seven directions d in
 {0,1}^3 \\ {0}; an edge carries a vertex iff a valid cell holds it and its ends differ in outside-ness; the vertex is at
 p + t d with t = iso(p) / (iso(p) - iso(p + d)).
+
+The mesh comparison (match_vertices, triangles_in_tetrahedra) is valid up to 8192 corners a side: a point's tolerance is
+march_tol, MARCH_TOL scaled by the binade of its largest coordinate (unchanged below 128), and the matcher buckets the edge
+points of each binade by their own tolerance and keys the buckets by per-axis ranks, which fit an int64 where three bucket
+coordinates of 8192 / 2.2e-5 each would not.  What was measured at which coordinates stands above MARCH_TOL.
 """
 import numpy as np
 
@@ -36,6 +41,16 @@ MLS_MAX_ABS = 6e-5
 MLS_P99_ABS = 2.5e-6
 # marching: |float32 vertex - fp64 vertex| over every unflagged edge of the GENERATE_CASES, the torus and the special-value
 # fields (coordinates below 83): max 5.4e-6 = half an ulp of a coordinate in [64, 128) plus the error of t.  Pinned at 2x.
+# Half an ulp doubles with every binade (6.1e-5 in [1024, 2048), 2.4e-4 in [4096, 8192)), so above 128 the tolerance of a
+# point is MARCH_TOL * 2^(e - 6) with e = floor(log2(its largest |coordinate|)): march_tol below.  It IS MARCH_TOL for every
+# coordinate below 128 and keeps its ratio to half an ulp (2.88) above.  Measured on the thin grids of
+# tests/test_marching_extents_oracle.py (noise with NaN holes and a smooth tube; no vertex missing or extra, every triangle in
+# its tetrahedron, the float32 formula pinned), the oracle's worst error and its share of the bound:
+#   2049 x 5 x 4, 5 x 2049 x 4, 5 x 4 x 2049: 6.11e-5 = 0.348 - 0.350 (93 723 vertices on the first)
+#   4100 x 5 x 4: 2.41e-4 (noise), 2.43e-4 (tube) = 0.349        8189 x 4 x 4: 2.44e-4 = 0.349 (287 206 vertices)
+# Binade by binade on the 8189-long grid: 3.8e-6 below 128, 3.1e-5 in [128, 1024), 6.1e-5, 1.22e-4 and 2.44e-4 in the three
+# above, each 0.347 - 0.349 of its bound: the error is half an ulp of the coordinate plus the error of t everywhere, which is
+# what the scaling assumes.  The kernels' output on the 2049-long grids gives the same figures (bit-equal to the oracle).
 MARCH_TOL = 1.1e-5
 
 # ambiguity bands (relative): where float32 rounding may legitimately take the other branch of a comparison
@@ -248,14 +263,15 @@ def weld(batches):
     for b in batches:
         nv, ni = len(b["vertices"]), b["num_internal"]
         remap = np.zeros(nv, np.int64)
-        for i in range(nv):
-            if i >= ni:
-                k = int(b["keys"][i])
-                if k in key_map:
-                    assert np.array_equal(verts[key_map[k]].view(np.uint32), b["vertices"][i].view(np.uint32))
-                    remap[i] = key_map[k]
-                    continue
-                key_map[k] = len(verts)
+        remap[:ni] = len(verts) + np.arange(ni)             # internal vertices come first and are never shared
+        verts.extend(b["vertices"][:ni])
+        for i in range(ni, nv):
+            k = int(b["keys"][i])
+            if k in key_map:
+                assert np.array_equal(verts[key_map[k]].view(np.uint32), b["vertices"][i].view(np.uint32))
+                remap[i] = key_map[k]
+                continue
+            key_map[k] = len(verts)
             remap[i] = len(verts)
             verts.append(b["vertices"][i])
         if len(b["triangles"]):
@@ -282,80 +298,117 @@ def same_vertex_multiset(verts, expected_f32):
     return bool(np.array_equal(a, b))
 
 
+def march_tol(pos, tol=MARCH_TOL):
+    """Tolerance of every position [n, 3]: tol * max(1, 2^(e - 6)) with e = floor(log2(largest |coordinate|)), i.e. `tol`
+    itself below 128 and the same multiple of half a float32 ulp in every binade above (non-finite rows: tol)."""
+    p = np.abs(np.asarray(pos, np.float64).reshape(-1, 3))
+    big = np.where(np.all(np.isfinite(p), axis=1), p.max(axis=1, initial=0.0), 0.0)
+    _, e = np.frexp(big)                                  # big = m 2^e with m in [0.5, 1): floor(log2 big) = e - 1
+    return tol * np.ldexp(1.0, np.maximum(e - 7, 0))
+
+
+def _bucket_candidates(v, vi_all, P, pe, h):
+    """(vertex, edge) index pairs whose buckets of width h touch (the 27 neighbours): vertices v[vi_all], edge points P[pe].
+    A bucket's key is built from the per-axis RANKS of the edge points' bucket coordinates (at most len(pe) distinct values
+    an axis), not from the coordinates themselves: three coordinates of 8192 / h each do not fit one int64, their ranks do."""
+    bp = np.floor(P[pe] / h).astype(np.int64)
+    axes = [np.unique(bp[:, a]) for a in range(3)]
+    n = [len(u) for u in axes]
+    assert n[0] * n[1] * n[2] < 2 ** 63
+
+    def rank(a, b):
+        """Rank of the bucket coordinates b on axis a, and whether each occurs among the edge points at all."""
+        r = np.minimum(np.searchsorted(axes[a], b), n[a] - 1)
+        return r, axes[a][r] == b
+    pr = [rank(a, bp[:, a])[0] for a in range(3)]
+    pc = (pr[2] * n[1] + pr[1]) * n[0] + pr[0]
+    order = np.argsort(pc, kind="stable")
+    pcs = pc[order]
+    bv = np.floor(v[vi_all] / h).astype(np.int64)
+    vr = [[rank(a, bv[:, a] + o) for o in (-1, 0, 1)] for a in range(3)]
+    cand_v, cand_e = [], []
+    for off in np.array(np.meshgrid([-1, 0, 1], [-1, 0, 1], [-1, 0, 1], indexing="ij")).reshape(3, -1).T:
+        (rx, kx), (ry, ky), (rz, kz) = (vr[a][off[a] + 1] for a in range(3))
+        at = np.nonzero(kx & ky & kz)[0]
+        if len(at) == 0:
+            continue
+        c = (rz[at] * n[1] + ry[at]) * n[0] + rx[at]
+        a = np.searchsorted(pcs, c, "left")
+        cnt = np.searchsorted(pcs, c, "right") - a
+        if cnt.sum() == 0:
+            continue
+        rep = np.repeat(at, cnt)
+        idx = np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt) + np.repeat(a, cnt)
+        cand_v.append(vi_all[rep])
+        cand_e.append(pe[order[idx]])
+    return cand_v, cand_e
+
+
 def match_vertices(verts, ref, tol=MARCH_TOL):
-    """Match mesh vertices to the expected unflagged edge points (nearest first, each used once, within tol).
-    Returns dict(missing, extra, max_err, vertex_edge): missing = unflagged edges no vertex matched; extra = vertices left
-    over beyond one per flagged edge (negative: too few); vertex_edge[i] = edge index of vertex i or -1."""
+    """Match mesh vertices to the expected unflagged edge points (nearest first, each used once, within the edge point's
+    march_tol).  Returns dict(missing, extra, max_err, max_err_over_tol, vertex_edge): missing = unflagged edges no vertex
+    matched; extra = vertices left over beyond one per flagged edge (negative: too few); max_err_over_tol = the largest
+    distance of a matched pair as a share of that edge point's tolerance; vertex_edge[i] = edge index of vertex i or -1."""
     v = np.asarray(verts, np.float64)
     sel = np.nonzero(~ref["flagged"])[0]
     P = ref["pos"][sel]
     vertex_edge = np.full(len(v), -1, np.int64)
     if len(P) == 0 or len(v) == 0:
-        return dict(missing=len(P), extra=len(v) - int(ref["flagged"].sum()), max_err=0.0, vertex_edge=vertex_edge)
-    h = 2.0 * tol
-    fin = np.all(np.isfinite(v), axis=1)
-    bp = np.floor(P / h).astype(np.int64)
-    lo = bp.min(axis=0) - 2
-    span = bp.max(axis=0) - lo + 3
-
-    def code(b):
-        b = b - lo
-        return (b[:, 2] * span[1] + b[:, 1]) * span[0] + b[:, 0]
-    pc = code(bp)
-    order = np.argsort(pc, kind="stable")
-    pcs = pc[order]
-    vi_all = np.nonzero(fin)[0]
-    bv = np.floor(v[vi_all] / h).astype(np.int64)
-    inside = np.all((bv >= lo + 1) & (bv < lo + span - 1), axis=1)
-    vi_all, bv = vi_all[inside], bv[inside]
+        return dict(missing=len(P), extra=len(v) - int(ref["flagged"].sum()), max_err=0.0, max_err_over_tol=0.0,
+                    vertex_edge=vertex_edge)
+    ptol = march_tol(P, tol)
+    vi_all = np.nonzero(np.all(np.isfinite(v), axis=1))[0]
+    vtol = march_tol(v[vi_all], tol)
     cand_v, cand_e = [], []
-    for off in np.array(np.meshgrid([-1, 0, 1], [-1, 0, 1], [-1, 0, 1], indexing="ij")).reshape(3, -1).T:
-        c = code(bv + off)
-        a = np.searchsorted(pcs, c, "left")
-        b = np.searchsorted(pcs, c, "right")
-        cnt = b - a
-        if cnt.sum() == 0:
-            continue
-        rep = np.repeat(np.arange(len(c)), cnt)
-        idx = np.arange(cnt.sum()) - np.repeat(np.cumsum(cnt) - cnt, cnt) + np.repeat(a, cnt)
-        cand_v.append(vi_all[rep])
-        cand_e.append(order[idx])
+    for t in np.unique(ptol):                       # the edge points of one binade: buckets as wide as twice their tolerance
+        # (a vertex within t of such a point lies in its binade or, across a power of two, in the one next to it)
+        near = vi_all[(vtol >= 0.5 * t) & (vtol <= 2.0 * t)]
+        cv, ce = _bucket_candidates(v, near, P, np.nonzero(ptol == t)[0], 2.0 * t)
+        cand_v += cv
+        cand_e += ce
+    used_e = np.zeros(len(P), bool)
+    max_err = max_ratio = 0.0
     if cand_v:
         cv, ce = np.concatenate(cand_v), np.concatenate(cand_e)
         dist = np.sqrt(((v[cv] - P[ce]) ** 2).sum(axis=1))
-        keep = dist <= tol
+        keep = dist <= ptol[ce]
         cv, ce, dist = cv[keep], ce[keep], dist[keep]
+        # a pair whose vertex and edge point occur in no other pair is taken whatever the order; the greedy pass is for the rest
+        lone = (np.bincount(cv, minlength=len(v))[cv] == 1) & (np.bincount(ce, minlength=len(P))[ce] == 1)
+        vertex_edge[cv[lone]] = sel[ce[lone]]
+        used_e[ce[lone]] = True
+        if lone.any():
+            max_err = float(dist[lone].max())
+            max_ratio = float((dist[lone] / ptol[ce[lone]]).max())
+        cv, ce, dist = cv[~lone], ce[~lone], dist[~lone]
         o = np.argsort(dist, kind="stable")
-        used_e = np.zeros(len(P), bool)
-        max_err = 0.0
         for i in o:
             if vertex_edge[cv[i]] < 0 and not used_e[ce[i]]:
                 vertex_edge[cv[i]] = sel[ce[i]]
                 used_e[ce[i]] = True
                 max_err = max(max_err, float(dist[i]))
-    else:
-        used_e = np.zeros(len(P), bool)
-        max_err = 0.0
+                max_ratio = max(max_ratio, float(dist[i] / ptol[ce[i]]))
     missing = int(np.count_nonzero(~used_e))
     extra = int(np.count_nonzero(vertex_edge < 0)) - int(ref["flagged"].sum())
-    return dict(missing=missing, extra=extra, max_err=max_err, vertex_edge=vertex_edge)
+    return dict(missing=missing, extra=extra, max_err=max_err, max_err_over_tol=max_ratio, vertex_edge=vertex_edge)
 
 
 def triangles_in_tetrahedra(verts, tris, tol=MARCH_TOL):
-    """Number of triangles whose three vertices do NOT all lie in one Kuhn tetrahedron of one cell (0 = all fine).
-    Triangles with a non-finite vertex are skipped."""
+    """Number of triangles whose three vertices do NOT all lie in one Kuhn tetrahedron of one cell (0 = all fine), every
+    vertex within its own march_tol.  Triangles with a non-finite vertex are skipped."""
     v = np.asarray(verts, np.float64)[np.asarray(tris, np.int64)]       # [m, 3 vertices, 3 axes]
     v = v[np.all(np.isfinite(v), axis=(1, 2))]
     if len(v) == 0:
         return 0
+    vt = march_tol(v.reshape(-1, 3), tol).reshape(-1, 3)                 # [m, 3 vertices]
     cen = v.mean(axis=1)
     cell = np.floor(cen)
     loc = v - cell[:, None, :]                                           # local coordinates of the three vertices
     lc = cen - cell
     srt = np.argsort(-lc, axis=1, kind="stable")                         # the tetrahedron: u_srt0 >= u_srt1 >= u_srt2
     u = np.take_along_axis(loc, np.repeat(srt[:, None, :], 3, axis=1), axis=2)
-    ok = np.all((loc >= -tol) & (loc <= 1 + tol), axis=(1, 2))
-    ok &= np.all(u[:, :, 0] - u[:, :, 1] >= -tol, axis=1) & np.all(u[:, :, 1] - u[:, :, 2] >= -tol, axis=1)
+    ok = np.all((loc >= -vt[:, :, None]) & (loc <= 1 + vt[:, :, None]), axis=(1, 2))
+    ok &= np.all(u[:, :, 0] - u[:, :, 1] >= -vt, axis=1) & np.all(u[:, :, 1] - u[:, :, 2] >= -vt, axis=1)
     return int(np.count_nonzero(~ok))
 
 
@@ -382,6 +435,7 @@ def compare_mesh(batches, ref, tol=MARCH_TOL):
     v, t = weld(batches)
     m = match_vertices(v, ref, tol)
     return dict(vertices=len(v), triangles=len(t), missing=m["missing"], extra=m["extra"], max_err=m["max_err"],
+                max_err_over_tol=m["max_err_over_tol"],
                 triangles_match=len(t) == ref["triangles"], off_tetrahedron=triangles_in_tetrahedra(v, t, tol),
                 volume=signed_volume(v, t) if len(t) else 0.0, euler=euler_characteristic(len(v), t) if len(t) else 0,
                 f32_pinned=same_vertex_multiset(v, ref["pos_f32"]), welded=(v, t))

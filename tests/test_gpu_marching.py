@@ -6,6 +6,7 @@ import pytest
 
 import oracle_binding as ob
 from gpu_common import assert_batches_equal, ctx  # noqa: F401
+from marching_extent_cases import noise_fn
 from refdata import is_manifold, weld_batches
 from test_oracle_marching import (COMPACT_EXPECT, GENERATE_CASES, compact_fixture, host_generator, make_key)
 
@@ -239,19 +240,6 @@ def test_scale_bias(ctx):
     np.testing.assert_array_equal(got.view(np.uint32), exp.view(np.uint32))
     empty = m.binding.Mesh(None, None, None, 0, 0, 0)
     m.binding.check(m.lib().mlsgpu_hip_scale_bias(ctx.h, C.byref(empty), 3.0, 10.0, -20.0, 30.0))
-
-
-def noise_fn(seed, hole_rate):
-    """A hash-noise field with NaN holes: every cube code, every lattice word boundary, cells dropped by isValid."""
-    def fn(x, y, z):
-        h = (x.astype(np.uint64) * np.uint64(73856093)) ^ (y.astype(np.uint64) * np.uint64(19349663)) \
-            ^ (np.uint64(z) * np.uint64(83492791)) ^ np.uint64(seed * 2654435761)
-        h = (h * np.uint64(0x9E3779B97F4A7C15)) >> np.uint64(40)
-        v = (h.astype(np.float64) / float(1 << 24) - 0.5).astype(np.float32)
-        v = np.where(v == 0, np.float32(0.25), v)
-        holes = ((h >> np.uint64(7)) % np.uint64(1000)) < np.uint64(int(hole_rate * 1000))
-        return np.where(holes, np.float32(np.nan), v)
-    return fn
 
 
 @pytest.mark.parametrize("size,swathe,weld", [((97, 35, 41), 48, "lattice"), ((131, 67, 9), 16, "lattice"), ((33, 129, 20), 24, "lattice"),
