@@ -91,10 +91,19 @@ __device__ __forceinline__ uint32_t spread3(uint32_t v)
     v = (v | (v << 2)) & 0x09249249u;
     return v;
 }
+/* spread3(v + 1) from spread3(v): with the gaps between the coordinate's bits filled the carry runs through them
+ * (1023 + 1 gives 0, as the mask of spread3 does) */
+__device__ __forceinline__ uint32_t spreadNext(uint32_t s)
+{
+    return ((s | ~0x09249249u) + 1u) & 0x09249249u;
+}
+/* Bit b of x, y, z goes to bit 3b, 3b + 1, 3b + 2: the low three bits of a code are the PARITIES of its coordinates.
+ * entryScatterKernel's ranking rests on that (mls.hip's spread3 interleaves the same way). */
 __device__ __forceinline__ uint32_t makeCode(int x, int y, int z)
 {
     return spread3((uint32_t) x) | (spread3((uint32_t) y) << 1) | (spread3((uint32_t) z) << 2);
 }
+static_assert((0x09249249u & 7u) == 1u, "spread3 keeps bit 0 of a coordinate in bit 0");
 
 /* general form for the test kernel (any non-negative ints), octree.cl:121-136 verbatim semantics */
 __device__ uint32_t makeCodeLoop(int x, int y, int z)
@@ -260,23 +269,25 @@ struct EntryWriteOut
  * writeEntries fused with the FIRST pass of the entry sort (round 3).  The entries of a tile of ENT_TILE splats are never
  * written in (splat, slot) order: the counting kernel histograms the low digit of their keys per tile while it evaluates the
  * box tests, one digit scan turns the histograms into positions (the same kernel the sort uses), and the scattering kernel
- * regenerates the tile's entries from the remembered slot masks, lines them up in LDS in (splat, slot) order -- the order a
- * stable sort has to start from -- and sends them straight to where the first LSD pass would have put them.  That is one
+ * regenerates the tile's entries from the remembered notes, ranks them as a stable sort that starts from (splat, slot)
+ * order would (see entryScatterKernel) and sends them straight to where the first LSD pass would have put them.  That is one
  * write and one read of all entries (16 bytes each) and two launches less than writeEntries + histogram + scatter; the
  * remaining passes of the sort are unchanged.  Results are identical: same keys, same stable order.
  */
 enum
 {
     ENT_THREADS = 512,              /* threads per workgroup */
-    ENT_PER = 2,                    /* consecutive splats per thread.  entryScatter per launch of four buckets (cfg3): 1 splat
-                                     * per thread 193.5 us, 2: 170.0, 3: 208.6, 4: 211.9 -- twice the entries between two
-                                     * barriers and twice as long a run of every digit in memory, while three workgroups still
-                                     * fit a CU's LDS (two at 3 and 4) */
+    ENT_PER = 2,                    /* splats per thread (1 or 2).  entryHist + entryScatter per launch of four buckets
+                                     * (cfg3): 1 splat per thread 93.6 + 75.6 us, 2: 96.3 + 69.4 -- twice as long a run of
+                                     * every digit in memory, and three workgroups still fit a CU's LDS
+                                     * (profiles/NOTES_entry_rank.md) */
     ENT_TILE = ENT_THREADS * ENT_PER,   /* splats per workgroup */
     ENT_CAP = 8 * ENT_TILE,         /* at most eight entries per splat */
     ENT_BIN_BITS = 8,               /* the fused pass handles digits of up to 8 bits */
-    ENT_KEY_BITS = 22               /* ... of keys that leave ten bits of a word for the splat's place in the tile */
+    ENT_KEY_BITS = 22,              /* ... of keys that leave ten bits of a word for the splat's place in the tile */
+    ENT_MIN_DIGIT_BITS = 3          /* ... and of at least 3, or of a one-level tree: see entryScatterKernel */
 };
+static_assert(ENT_PER == 1 || ENT_PER == 2, "the splat's place in the tile has 32 - ENT_KEY_BITS bits");
 
 /* What entryHist leaves entryScatter per splat, 8 bytes: low word = slot mask (bits 0-7), level (8-12), lowest node x
  * (13-22); high word = lowest node y (0-9) and z (10-19); ten bits per coordinate inside the bounds -- so the scatter reads
@@ -395,9 +406,54 @@ struct EntryScatterArgs
     uint32_t idBits;            /* != 0: an entry leaves as ONE word, (key >> digitBits) << idBits | (id - firstSplat), in keysOut */
 };
 
-__global__ __launch_bounds__(ENT_THREADS) __attribute__((amdgpu_waves_per_eu(6, 8))) void entryScatterKernel(Lanes<EntryScatterArgs> lanes, uint32_t digitBits)
+/* The keys of one splat's 2 x 2 x 2 candidate nodes, from its note, times 8 (the bytes of a matrix word, see
+ * entryScatterKernel).  Morton digits are independent, so the spread coordinates have no bit in common and makeCode of
+ * the node (ilx + dx, ily + dy, ilz + dz) is a SUM of one part per axis: a key is one addition of two of six values that
+ * are made once per splat -- the kernel issues vector instructions for all eight slots of its splats, full or not, and is
+ * bound by their number. */
+struct NoteKeys
 {
-    enum { BINS = 1 << ENT_BIN_BITS, WAVES = ENT_THREADS / 64, MAX_ROUNDS = ENT_CAP / ENT_THREADS };
+    uint32_t x[2], yz[4];
+    NoteKeys() = default;
+    __device__ __forceinline__ NoteKeys(uint64_t note, const LevelOffsets &levelOffsets)
+    {
+        const uint32_t lo32 = (uint32_t) note, hi32 = (uint32_t) (note >> 32);
+        const uint32_t ilx = (lo32 >> 13) & 0x3FFu, ily = hi32 & 0x3FFu, ilz = (hi32 >> 10) & 0x3FFu;
+        const uint32_t levelOffset = levelOffsets.v[(lo32 >> 8) & 0x1Fu];      /* (a note of 0: level 0, never used) */
+        const uint32_t sx[2] = {spread3(ilx), spreadNext(spread3(ilx))};
+        const uint32_t sy[2] = {spread3(ily), spreadNext(spread3(ily))};
+        const uint32_t sz[2] = {spread3(ilz), spreadNext(spread3(ilz))};
+        for (uint32_t i = 0; i < 2; i++)
+            x[i] = sx[i] << 3;
+        for (uint32_t i = 0; i < 4; i++)
+            yz[i] = (sy[i & 1] << 4) + (sz[i >> 1] << 5) + (levelOffset << 3);
+    }
+    /* == 8 * (makeCode(ilx + (o & 1), ily + ((o >> 1) & 1), ilz + (o >> 2)) + levelOffset) */
+    __device__ __forceinline__ uint32_t key8(int o) const { return x[o & 1] + yz[o >> 1]; }
+};
+
+/*
+ * How the tile's entries are ranked.  The pass is one stable split of the tile's entries, taken in (splat, slot) order, by
+ * the low digit of their keys.  A generic split has to order the entries first and rank them round by round; this one
+ * does not, because NO TWO ENTRIES OF A SPLAT SHARE A DIGIT:
+ *  - a splat's entries are among the eight nodes (ilx + dx, ily + dy, ilz + dz), dx, dy, dz in {0, 1}, of ONE level, all
+ *    inside the bounds (goodEntry), where every coordinate is below 2^10;
+ *  - makeCode puts the lowest bit of x, y and z into bits 0, 1 and 2 of the code (spread3: bit b of a coordinate goes to
+ *    bit 3b, and y and z are shifted by 1 and 2) -- the parities of the coordinates.  ilx and ilx + 1 differ in parity
+ *    whatever carries the addition causes above bit 0, so the eight codes differ pairwise in their low three bits;
+ *  - all eight get the one levelOffset added, which permutes the residues modulo 8: the keys stay distinct modulo 8,
+ *    hence modulo every 2^b with b >= 3 (ENT_MIN_DIGIT_BITS).
+ * A narrower digit reaches this kernel only from a tree of ONE level (treeBuildBatch), where bound = 1 leaves a splat its
+ * slot 0 at most: one entry, nothing to share.
+ * So the stable rank of an entry among the tile's entries with its digit is the number of EARLIER SPLATS of the tile that
+ * hold that digit: with one bit per (digit, splat) in LDS -- match[group][digit], bit l = splat 64 * group + l of the
+ * tile -- that is a count of words before the splat's group plus a population count below its bit.  Every slot's
+ * operations are independent of every other slot's; nothing goes round by round.
+ */
+__global__ __launch_bounds__(ENT_THREADS) __attribute__((amdgpu_waves_per_eu(ENT_PER == 2 ? 6 : 8, 8))) void entryScatterKernel(Lanes<EntryScatterArgs> lanes, uint32_t digitBits)
+{
+    enum { BINS = 1 << ENT_BIN_BITS, WAVES = ENT_THREADS / 64, GROUPS = ENT_TILE / 64, MAX_ROUNDS = ENT_CAP / ENT_THREADS };
+    static_assert(BINS <= ENT_THREADS, "one thread per bin in the scan over the digits");
     const EntryScatterArgs &A = lanes.a[blockIdx.y];  /* by reference, as in entryHistKernel */
     if (blockIdx.x >= A.numTiles)
         return;
@@ -408,162 +464,122 @@ __global__ __launch_bounds__(ENT_THREADS) __attribute__((amdgpu_waves_per_eu(6, 
     const uint32_t numTiles = A.numTiles;
     const uint64_t n = A.n;
     uint32_t *const keysOut = A.keysOut, *const valsOut = A.valsOut;
-    __shared__ uint32_t waveBins[WAVES][BINS];
-    __shared__ uint32_t tileBase[BINS];
-    __shared__ uint32_t waveTotals[WAVES], waveTotalsAll[WAVES], waveCnt[WAVES];
-    /* An entry in LDS is ONE word: its key (ENT_KEY_BITS at most on this route) below the thread that holds its splat (the
-     * id is the tile's first id + that).  Key and id travel together through the reorder, so the ids need no pass of their
-     * own: six workgroup barriers instead of eight, and 41 KB of LDS for a tile of 1024 splats (three workgroups per CU). */
-    __shared__ uint32_t sEnt[ENT_CAP];          /* the tile's entries in (splat, slot) order; afterwards in the pass's order */
-    __shared__ uint32_t sMatch[WAVES][BINS];    /* per wave and digit: the lanes of HALF a wave that hold it (sortScatterKernel's
-                                                 * way of ranking, 32 lanes at a time: 64-bit words would cost the third workgroup
-                                                 * of a CU its LDS) */
+    /* The matrix is dead once every entry knows its place, and the entries are lined up only then: both live in the same
+     * 32 KB, the matrix of the WHOLE tile (no second half through a re-zeroed one).  An entry in LDS is ONE word: its key
+     * (ENT_KEY_BITS at most on this route) below its splat's place in the tile (the id is the tile's first id + that).
+     * With sPlace 49 KB for a tile of 1024 splats: three workgroups per CU. */
+    typedef unsigned long long Word;
+    __shared__ union
+    {
+        Word match[GROUPS][BINS];               /* conflict-free over the digits; a group's words belong to ONE wave */
+        uint32_t ent[ENT_CAP];                  /* the tile's entries in the pass's order */
+    } s;
+    static_assert(sizeof(s.match) <= sizeof(s.ent), "the matrix fits the entries' space");
+    __shared__ uint32_t sPlace[GROUPS][BINS];   /* per group and digit: where the group's first entry with the digit goes in
+                                                 * the tile; half a matrix word's offset is this table's */
+    __shared__ uint32_t tileBase[BINS];         /* what takes a place in the tile to its place in memory */
+    __shared__ uint32_t waveTotals[WAVES], waveTotalsAll[WAVES];
     const uint32_t numBins = 1u << digitBits, dmask = numBins - 1;
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (uint32_t d = threadIdx.x; d < numBins; d += ENT_THREADS)
-    {
-#pragma unroll
-        for (int w = 0; w < WAVES; w++)
-        {
-            waveBins[w][d] = 0;
-            sMatch[w][d] = 0u;
-        }
-    }
-    /* 1. the tile's entries, lined up in (splat, slot) order.  What the thread reads that does not depend on another read is
-     * requested here, together: its slot mask, its splat, and the digit totals and tile offsets of the bins it owns in the
-     * scan further down (one round of memory latency instead of three). */
+    for (uint32_t i = threadIdx.x; i < GROUPS * BINS; i += ENT_THREADS)
+        (&s.match[0][0])[i] = 0ull;
+    /* 1. one bit per entry.  Thread t holds splats t, t + ENT_THREADS (, ...) of the tile: a wave's 64 notes are one 512-byte
+     * stretch, and a wave's splats are one group of the matrix per round -- lane l is bit l.  What the thread reads that
+     * does not depend on another read is requested here, together: its notes, and the digit total and tile offset of the
+     * bin it owns in the scan further down. */
     const uint32_t tile = tileOfWorkgroup(blockIdx.x, numTiles);
-    const uint64_t i0 = (uint64_t) tile * ENT_TILE + (uint64_t) threadIdx.x * ENT_PER;
     uint64_t note[ENT_PER];
-    uint32_t cnt = 0;
 #pragma unroll
-    for (int s_ = 0; s_ < ENT_PER; s_++)
-        note[s_] = i0 + s_ < n ? notes[i0 + s_] : 0ull;
-    const uint32_t per = numBins > ENT_THREADS ? numBins / ENT_THREADS : 1;
-    const uint32_t d0 = threadIdx.x * per;
-    const uint32_t totalOfBin = d0 < numBins ? digitTotals[d0] : 0u;
-    const uint32_t histOfBin = d0 < numBins ? hist[(uint64_t) d0 * numTiles + tile] : 0u;
-#pragma unroll
-    for (int s_ = 0; s_ < ENT_PER; s_++)
-        cnt += (uint32_t) __popc((uint32_t) note[s_] & 0xFFu);
-    const uint32_t incl = waveInclusiveScan(cnt);
-    if (lane == 63)
-        waveCnt[wave] = incl;
-    __syncthreads();
-    uint32_t pos = incl - cnt, tileCount = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < WAVES; w++)
+    for (int h = 0; h < ENT_PER; h++)
     {
-        if (w < wave)
-            pos += waveCnt[w];
-        tileCount += waveCnt[w];
+        const uint64_t i = (uint64_t) tile * ENT_TILE + (uint32_t) h * ENT_THREADS + threadIdx.x;
+        note[h] = i < n ? notes[i] : 0ull;
     }
+    const uint32_t bin = threadIdx.x;
+    const uint32_t totalOfBin = bin < numBins ? digitTotals[bin] : 0u;
+    const uint32_t histOfBin = bin < numBins ? hist[(uint64_t) bin * numTiles + tile] : 0u;
+    NoteKeys keys[ENT_PER];
 #pragma unroll
-    for (int s_ = 0; s_ < ENT_PER; s_++)
+    for (int h = 0; h < ENT_PER; h++)
+        keys[h] = NoteKeys(note[h], P.levelOffsets);
+    /* the matrix word of slot o of splat h, as a byte offset: the row of the splat's group | 8 * the key's digit */
+    const uint32_t dmask8 = dmask << 3;
+    auto wordOf = [&](int h, int o) { return (keys[h].key8(o) & dmask8) | (((uint32_t) h * WAVES + wave) * (uint32_t) sizeof(s.match[0])); };
+    auto matchAt = [&](uint32_t w) { return reinterpret_cast<Word *>(reinterpret_cast<char *>(&s.match[0][0]) + w); };
+    auto placeAt = [&](uint32_t w) { return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(&sPlace[0][0]) + (w >> 1)); };
+    __syncthreads();
+    const Word bit = 1ull << lane;
+#pragma unroll
+    for (int h = 0; h < ENT_PER; h++)
+#pragma unroll
+        for (int o = 0; o < 8; o++)
+            if (note[h] & (1u << o))
+                atomicOr(matchAt(wordOf(h, o)), bit);       /* nothing comes back */
+    __syncthreads();
+    /* 2. per digit, the counts of its words and their exclusive prefix along the groups; the sum is the tile's histogram
+     * entry.  Then the scan over the bins: where the digit's run begins in the tile, and in memory. */
+    uint32_t mine = 0, before[GROUPS];
+    if (bin < numBins)
     {
-        const uint32_t mask = (uint32_t) note[s_] & 0xFFu;
-        if (mask != 0)
-        {
-            const uint32_t lo32 = (uint32_t) note[s_], hi32 = (uint32_t) (note[s_] >> 32);
-            const int shift = (int) ((lo32 >> 8) & 0x1Fu);
-            const int ilx = (int) ((lo32 >> 13) & 0x3FFu), ily = (int) (hi32 & 0x3FFu), ilz = (int) ((hi32 >> 10) & 0x3FFu);
-            const uint32_t levelOffset = P.levelOffsets.v[shift];
-            const uint32_t holder = (threadIdx.x * ENT_PER + (uint32_t) s_) << ENT_KEY_BITS;
 #pragma unroll
-            for (int o = 0; o < 8; o++)
-                if (mask & (1u << o))
-                    sEnt[pos++] = (makeCode(ilx + (o & 1), ily + ((o >> 1) & 1), ilz + (o >> 2)) + levelOffset) | holder;
+        for (int g = 0; g < GROUPS; g++)
+        {
+            before[g] = mine;
+            mine += (uint32_t) __popcll(s.match[g][bin]);
         }
     }
-    __syncthreads();
-    if (tileCount == 0)
-        return;
-    /* 2. one stable LSD pass over the tile, as sortScatterKernel: wave w owns `rounds` x 64 consecutive elements */
-    const uint32_t rounds = (tileCount + ENT_THREADS - 1) / ENT_THREADS;
-    const uint32_t first = wave * rounds * 64 + lane;
-    uint32_t ent[MAX_ROUNDS];
-#pragma unroll
-    for (int j = 0; j < MAX_ROUNDS; j++)
     {
-        const uint32_t e = first + j * 64;
-        const bool valid = (uint32_t) j < rounds && e < tileCount;
-        ent[j] = valid ? sEnt[e] : 0u;
-        if (valid)
-            atomicAdd(&waveBins[wave][ent[j] & dmask], 1u);
-    }
-    __syncthreads();
-    {
-        uint32_t mine = 0, mineAll = 0;
-        if (d0 < numBins)
-            for (uint32_t k = 0; k < per; k++)
-            {
-                mineAll += k == 0 ? totalOfBin : digitTotals[d0 + k];
-#pragma unroll
-                for (int w = 0; w < WAVES; w++)
-                    mine += waveBins[w][d0 + k];
-            }
-        const uint32_t inclMine = waveInclusiveScan(mine), inclAll = waveInclusiveScan(mineAll);
+        const uint32_t inclMine = waveInclusiveScan(mine), inclAll = waveInclusiveScan(totalOfBin);
         if (lane == 63)
         {
             waveTotals[wave] = inclMine;
             waveTotalsAll[wave] = inclAll;
         }
         __syncthreads();
-        uint32_t run = inclMine - mine, base = inclAll - mineAll;
+        uint32_t run = inclMine - mine, base = inclAll - totalOfBin;
         for (uint32_t w = 0; w < wave; w++)
         {
             run += waveTotals[w];
             base += waveTotalsAll[w];
         }
-        if (d0 < numBins)
-            for (uint32_t k = 0; k < per; k++)
-            {
-                const uint32_t d = d0 + k;
-                tileBase[d] = base + (k == 0 ? histOfBin : hist[(uint64_t) d * numTiles + tile]) - run;
-                base += k == 0 ? totalOfBin : digitTotals[d];
-#pragma unroll
-                for (int w = 0; w < WAVES; w++)
-                {
-                    const uint32_t c = waveBins[w][d];
-                    waveBins[w][d] = run;
-                    run += c;
-                }
-            }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < MAX_ROUNDS; j++)
-    {
-        if ((uint32_t) j >= rounds)     /* uniform: a tile holds 3.8 entries per splat on average, 8 at most */
-            continue;
-        const uint32_t e = first + j * 64;
-        const bool valid = e < tileCount;
-        const uint32_t digit = ent[j] & dmask;
-        /* the lanes with the same digit, through LDS: see sortScatterKernel */
-#pragma unroll
-        for (uint32_t half = 0; half < 2; half++)       /* the lower lanes first: the order of the elements */
+        if (bin < numBins)
         {
-            const bool mine = valid && (lane >> 5) == half;
-            const uint32_t bit = 1u << (lane & 31u);
-            if (mine)
-                atomicOr(&sMatch[wave][digit], bit);
-            __builtin_amdgcn_wave_barrier();
-            const uint32_t peers = mine ? sMatch[wave][digit] : 0u;
-            __builtin_amdgcn_wave_barrier();
-            if (mine)
-            {
-                const uint32_t rank = (uint32_t) __popc(peers & (bit - 1u));
-                const uint32_t dst = waveBins[wave][digit] + rank;
-                sEnt[dst] = ent[j];      /* (every wave took its elements into registers before the last two barriers) */
-                if (rank == 0)
-                {
-                    waveBins[wave][digit] = dst + (uint32_t) __popc(peers);
-                    sMatch[wave][digit] = 0u;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int g = 0; g < GROUPS; g++)
+                sPlace[g][bin] = run + before[g];
+            tileBase[bin] = base + histOfBin - run;
         }
-        __builtin_amdgcn_wave_barrier();
+    }
+    uint32_t tileCount = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < WAVES; w++)
+        tileCount += waveTotals[w];
+    if (tileCount == 0)
+        return;
+    __syncthreads();
+    /* every entry's place in the pass's order: its group's first + the splats below its own in the word (the last reads
+     * of the matrix) */
+    uint32_t dst[ENT_PER][8];
+#pragma unroll
+    for (int h = 0; h < ENT_PER; h++)
+#pragma unroll
+        for (int o = 0; o < 8; o++)
+            if (note[h] & (1u << o))
+            {
+                const uint32_t w = wordOf(h, o);
+                const Word m = *matchAt(w);
+                dst[h][o] = __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, *placeAt(w)));
+            }
+    __syncthreads();
+    /* ... and the entries go there, over the matrix */
+#pragma unroll
+    for (int h = 0; h < ENT_PER; h++)
+    {
+        const uint32_t holder = ((uint32_t) h * ENT_THREADS + threadIdx.x) << ENT_KEY_BITS;
+#pragma unroll
+        for (int o = 0; o < 8; o++)
+            if (note[h] & (1u << o))
+                s.ent[dst[h][o]] = (keys[h].key8(o) >> 3) | holder;
     }
     __syncthreads();
     /* 3. out, in the order of the pass: the run of a digit is contiguous in the tile and in memory */
@@ -575,7 +591,7 @@ __global__ __launch_bounds__(ENT_THREADS) __attribute__((amdgpu_waves_per_eu(6, 
         const uint32_t p = threadIdx.x + k * ENT_THREADS;
         if (p < tileCount)
         {
-            const uint32_t e = sEnt[p];
+            const uint32_t e = s.ent[p];
             const uint32_t key = e & ((1u << ENT_KEY_BITS) - 1u);
             const uint32_t out = tileBase[key & dmask] + p;
             const uint32_t id = tileFirstId + (e >> ENT_KEY_BITS);
@@ -832,8 +848,11 @@ static int treeBuildBatch(mlsgpu_tree *const *trees, const mlsgpu_tree_build *re
     const uint32_t passes = sortPasses(keyBits, SortCaps<uint32_t>::MAX_DIGIT_BITS);
     const uint32_t perPass = (keyBits + passes - 1) / passes;
     static const bool fusedOff = getenv("MLSGPU_HIP_OCTREE_FUSED") != nullptr && atoi(getenv("MLSGPU_HIP_OCTREE_FUSED")) == 0;
-    /* wider digits (deep trees) take the separate passes */
-    const bool fused = perPass <= ENT_BIN_BITS && keyBits <= ENT_KEY_BITS && !fusedOff;
+    /* wider digits (deep trees) take the separate passes.  entryScatterKernel's ranking needs a digit of three bits or a
+     * tree of one level (a one-bit key): every split sortPasses makes is one or the other, and one that were not would take
+     * the separate passes too */
+    const bool rankable = perPass >= ENT_MIN_DIGIT_BITS || maxShift == minShift;
+    const bool fused = perPass <= ENT_BIN_BITS && keyBits <= ENT_KEY_BITS && rankable && !fusedOff;
 
     /* the command list straight from the sort's last pass (NodeIn / NodeOut above): for the fused front end with ONE pass left */
     const bool direct = fused && keyBits <= 2 * perPass;

@@ -37,9 +37,18 @@ TRACKED = {
     "sortScatter": "sortScatterKernel",
     "sortHist": "sortHistKernel",
     "cellCode": "cellCodeKernel",
-    "writeEntries": "entryScatterKernel",
+    "writeEntries": ("entryHistKernel", "entryScatterKernel"),  # one launch of each per build: both kernels' bytes
     "writeSplatIds": "SplatIdsOut",             # rounds 1-3 and the deep-tree route; gone from the default route in round 4
 }
+
+
+def tracked(names):
+    """(label, the kernels of `names` behind it): a label stands for one kernel or for the kernels of a tuple."""
+    for label, needles in TRACKED.items():
+        needles = (needles,) if isinstance(needles, str) else needles
+        hits = [k for k in names if any(needle in k for needle in needles)]
+        if hits:
+            yield label, hits, len(needles)
 
 
 def find(directory, suffix):
@@ -117,13 +126,10 @@ def traffic(fetch_dir, write_dir, out):
             f.write('"%s",%d,%.1f,%.1f,%.0f,%.0f\n' % (k, n, fetch.get(k, 0), write.get(k, 0),
                                                        2 * 1024 * fetch.get(k, 0) / n, 1024 * write.get(k, 0) / n))
     per_launch, per_pass = {}, {}
-    for label, needle in TRACKED.items():
-        fk = [k for k in names if needle in k]
-        if not fk:
-            continue
+    for label, fk, kernels in tracked(names):
         n = sum(max(calls.get(k, 0), wcalls.get(k, 0)) for k in fk)
         moved = 2 * 1024 * sum(fetch.get(k, 0) for k in fk) + 1024 * sum(write.get(k, 0) for k in fk)
-        per_launch[label] = int(moved / max(n, 1))
+        per_launch[label] = int(moved * kernels / max(n, 1))      # a launch of every kernel of the label
         per_pass[label] = int(moved / PMC_PASSES_OF.get(label, PMC_PASSES))
     tpath = os.path.join(ROOT, "profiles", "traffic.json")
     doc = json.load(open(tpath)) if os.path.exists(tpath) else {}
@@ -177,13 +183,10 @@ def traffic_resolved(rd_dir, wr_dir, out):
                     % (k, n, r, r32, r64, r128, "yes" if abs(r - r32 - r64 - r128) <= 1e-6 * max(r, 1) else "no", fetch / n,
                        formula / n, fetch / formula if formula else 0.0, w, w64, write / n))
     per_launch, per_pass, factors = {}, {}, {}
-    for label, needle in TRACKED.items():
-        fk = [k for k in names if needle in k]
-        if not fk:
-            continue
+    for label, fk, kernels in tracked(names):
         n = sum(max(calls.get(k, 0), wcalls.get(k, 0)) for k in fk)
         rows = [row(k) for k in fk]
-        per_launch[label] = int((sum(x[6] for x in rows) + sum(x[8] for x in rows)) / max(n, 1))
+        per_launch[label] = int((sum(x[6] for x in rows) + sum(x[8] for x in rows)) * kernels / max(n, 1))
         per_pass[label] = int((sum(x[6] for x in rows) + sum(x[8] for x in rows)) / PMC_PASSES_OF.get(label, PMC_PASSES))
         factors[label] = round(sum(x[6] for x in rows) / max(sum(x[7] for x in rows), 1), 3)
     tpath = os.path.join(ROOT, "profiles", "traffic.json")
