@@ -12,7 +12,7 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--flip-edges R] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
  * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
@@ -27,12 +27,16 @@
  * --repair, --repair pinches (device weld only): before the write, every output chunk is repaired where it lies: triangles
  *   with a repeated directed side are dropped and pinched vertices split (with `pinches`: every umbrella of a vertex becomes a
  *   vertex of its own), so that --check says `manifold yes` -- after --simplify, which can make a chunk non-manifold, and
- *   before --smooth, --normals and --check; one line with the statistics.
+ *   before --flip-edges, --smooth, --normals and --check; one line with the statistics.
+ * --flip-edges R (device weld only, R > 0): before the write, every output chunk goes through at most R rounds of Delaunay edge
+ *   flips where it lies (minGain 1e-6, minCos 0.5): connectivity only, the vertices and the edges on a chunk's boundary stay
+ *   -- after --simplify and --repair, before --smooth; one line with the statistics and the smallest triangle quality before
+ *   and after.
  * --smooth N (device weld only, N > 0): before the write, every output chunk gets N Taubin iterations (lambda 0.5, mu -0.53)
- *   where it lies, the vertices on a chunk's boundary held fixed -- after --simplify when both are given; one line with the
+ *   where it lies, the vertices on a chunk's boundary held fixed -- after --simplify and --flip-edges when they are given; one line with the
  *   statistics.
  * --deviation D (device weld only, D > 0 in world units): the chunks are kept as the weld left them, and after the last of
- *   --fill-holes, --simplify, --repair and --smooth two lines say how far the output lies from them: `moved`, the output's
+ *   --fill-holes, --simplify, --repair, --flip-edges and --smooth two lines say how far the output lies from them: `moved`, the output's
  *   vertices against the kept surface, and `lost`, the kept vertices against the output's surface -- the points within and
  *   beyond D, the largest and the RMS distance, and the distances that 50 % and 90 % of the points within stay under, read
  *   off a histogram of 16 bins.  Without such a stage `moved` is all zeros.
@@ -91,7 +95,8 @@ int main(int argc, char **argv)
     float simplifyCells = 0.0f;
     bool simplifyGiven = false, quadricGiven = false, smoothGiven = false, fillGiven = false, repairGiven = false;
     std::uint32_t repairFlags = 0;
-    long smoothIterations = 0, fillEdges = 0;
+    long smoothIterations = 0, fillEdges = 0, flipRounds = 0;
+    bool flipGiven = false;
     float deviationDistance = 0.0f;
     bool deviationGiven = false, intersectionsGiven = false;
     long compactBits = 0;
@@ -128,6 +133,11 @@ int main(int argc, char **argv)
         {
             smoothIterations = atol(argv[++i]);
             smoothGiven = true;
+        }
+        else if (a == "--flip-edges" && i + 1 < argc)
+        {
+            flipRounds = atol(argv[++i]);
+            flipGiven = true;
         }
         else if (a == "--fill-holes" && i + 1 < argc)
         {
@@ -172,7 +182,7 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--flip-edges R] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
         return 2;
     }
@@ -209,6 +219,16 @@ int main(int argc, char **argv)
     if (smoothGiven && hostWeld)
     {
         std::cerr << "--smooth needs --weld device: the host welder's output is not on the device\n";
+        return 2;
+    }
+    if (flipGiven && !(flipRounds > 0 && flipRounds <= 1000000))
+    {
+        std::cerr << "--flip-edges takes a number of rounds > 0\n";
+        return 2;
+    }
+    if (flipGiven && hostWeld)
+    {
+        std::cerr << "--flip-edges needs --weld device: the host welder's output is not on the device\n";
         return 2;
     }
     if (fillGiven && !(fillEdges >= 3 && fillEdges <= (long) MLSGPU_FILL_MAX_EDGES))
@@ -319,6 +339,8 @@ int main(int argc, char **argv)
         std::size_t filledChunks = 0;
         mlsgpu_repair_stats repaired = mlsgpu_repair_stats();
         std::size_t repairedChunks = 0;
+        mlsgpu_flip_stats flipped = mlsgpu_flip_stats();
+        std::size_t flippedChunks = 0;
         std::pair<mlsgpu_deviation, mlsgpu_deviation> deviated;
         mlsgpu_self_intersections crossed = mlsgpu_self_intersections();
         mlsgpu_compact_stats compacted = mlsgpu_compact_stats();
@@ -374,6 +396,11 @@ int main(int argc, char **argv)
             {
                 repaired = deviceMesher.repair(repairFlags);
                 repairedChunks = chunks;
+            }
+            if (flipGiven)
+            {
+                flipped = deviceMesher.flipEdges((std::uint32_t) flipRounds, 1e-6, 0.5);
+                flippedChunks = chunks;
             }
             if (smoothGiven)
             {
@@ -446,6 +473,13 @@ int main(int argc, char **argv)
                         (unsigned long long) repaired.unusedVertices, (unsigned long long) repaired.splitVertices,
                         (unsigned long long) repaired.numVertices, (unsigned long long) repaired.outVertices,
                         (unsigned long long) repaired.numTriangles, (unsigned long long) repaired.outTriangles);
+        if (flipGiven)
+            std::printf("flip-edges chunks %zu interior-edges %llu rounds %llu flips %llu non-delaunay %llu -> %llu blocked %llu "
+                        "min-quality %.9g -> %.9g\n",
+                        flippedChunks, (unsigned long long) flipped.interiorEdges, (unsigned long long) flipped.rounds,
+                        (unsigned long long) flipped.flips, (unsigned long long) flipped.nonDelaunayBefore,
+                        (unsigned long long) flipped.nonDelaunayAfter, (unsigned long long) flipped.blockedAfter,
+                        flipped.minQualityBefore, flipped.minQualityAfter);
         if (smoothGiven)
             std::printf("smooth chunks %zu vertices %llu edges %llu boundary-vertices %llu isolated %llu passes %llu max-move %.9g\n",
                         smoothedChunks, (unsigned long long) smoothed.numVertices, (unsigned long long) smoothed.numEdges,

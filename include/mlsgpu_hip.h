@@ -911,6 +911,96 @@ int mlsgpu_hip_mesh_smooth(mlsgpu_ctx *ctx, const float *dVertices, uint64_t num
 int mlsgpu_hip_mesher_smooth(mlsgpu_mesher *mesher, uint32_t iterations, float lambda, float mu, uint32_t boundary,
                              mlsgpu_smooth_stats *stats);
 
+/* ---- Delaunay edge flips of a device-resident mesh, with a triangle quality report: marching tetrahedra leaves needles and
+ *      caps wherever the surface passes close to a lattice vertex, and a cluster simplify adds its own; flipping an interior
+ *      edge whose two opposite angles sum to more than pi (the intrinsic Delaunay criterion) takes them out by changing the
+ *      connectivity only.  Vertices keep their bits, boundary edges are never flipped (the seams between output chunks stay
+ *      closed), and the topology report of the result is the input's.  The reference has no counterpart.  Deterministic:
+ *      every floating-point operation below is ONE correctly rounded IEEE double operation on exactly converted floats (no
+ *      contraction), in the order written, and every statistic is a count, a minimum or a maximum -- the output depends
+ *      neither on the schedule nor on the order of the triangles.  For vectors u, v of doubles
+ *        u - v = (ux - vx, uy - vy, uz - vz);  dot(u, v) = (ux * vx + uy * vy) + uz * vz;
+ *        cross(u, v) = (uy * vz - uz * vy, uz * vx - ux * vz, ux * vy - uy * vx);  face(p, q, r) = cross(q - p, r - p).
+ *      1. A triangle with an index >= V is counted in outOfRangeTriangles (the index is compared, never used as an address);
+ *         otherwise a triangle with two equal indices is counted in degenerateTriangles.  Neither takes part, in any round:
+ *         their rows keep their bits.  (A flip never makes a participating triangle degenerate: step 3 and guard (i).)
+ *      2. The undirected edges {a, b} of the participating triangles are counted once each in numEdges.
+ *      3. An edge {a, b}, a < b, is INTERIOR REGULAR (interiorEdges) if exactly one triangle side is a -> b and exactly one is
+ *         b -> a, with T1 = (a, b, c) the triangle that holds a -> b and T2 = (b, a, d) the one that holds b -> a (each up to
+ *         rotation), and c != d.
+ *      4. Priority.  cot(p; q, r) = dot(q - p, r - p) / sqrt(dot(x, x)) with x = cross(q - p, r - p).
+ *         P = -(cot(c; a, b) + cot(d; b, a)).  The edge is NON-DELAUNAY if P > minGain; a NaN P never is, +infinity is (a
+ *         zero-area cap has it).  P is a ratio: scaling all coordinates by a power of two changes no output bit (as long
+ *         as nothing leaves the doubles' normal range).
+ *      5. Guards.  With n1 = face(a, b, c), n2 = face(b, a, d), N = n1 + n2, m1 = face(a, d, c), m2 = face(b, c, d), a
+ *         non-Delaunay edge is BLOCKED if
+ *           (i)   c -> d or d -> c is a side of a participating triangle, or
+ *           (ii)  dot(n1, n2) >= (minCos * sqrt(dot(n1, n1))) * sqrt(dot(n2, n2)) is false, or
+ *           (iii) dot(m1, N) > 0 && dot(m2, N) > 0 is false (the quad is not convex, or the flip would fold it),
+ *         and a CANDIDATE otherwise.
+ *      6. The choice of a round.  A candidate WINS if at each of its four vertices a, b, c, d it is the best of all candidates
+ *         that have that vertex among their four: the larger P wins, among equal P the smaller key a << bitLength(V) | b.
+ *         (bitLength(V) = the number of bits of V: 0 for 0, 3 for 4.)  Winners have disjoint vertex sets: no two share a
+ *         triangle or create the same edge, none invalidates another's guard (i), and their order does not matter.  The best
+ *         candidate of the mesh always wins: a round without a winner is a round without a candidate.
+ *      7. Rewrite.  For every winner the row of T1 becomes (a, d, c) and the row of T2 becomes (b, c, d).  Nothing else is
+ *         written.
+ *      8. Rounds.  The mesh is classified (steps 3-5); then, while fewer than maxRounds rounds have run: a round chooses and
+ *         rewrites (rounds counts it); if it had no winner, converged = 1 and the rounds end; otherwise its winners are added
+ *         to flips and the mesh is classified again.  maxRounds is a required cap: near-cocircular quads can alternate under
+ *         rounding.  maxRounds = 0 is a pure report (rounds = 0, converged = 0) and the output is a copy of the input.
+ *         A mesh in which no triangle takes part -- none at all, or V == 0 -- has no candidate: rounds = converged = 1 unless
+ *         maxRounds = 0.
+ *         nonDelaunayBefore is the first classification's number of non-Delaunay edges; nonDelaunayAfter and blockedAfter
+ *         are the last one's non-Delaunay and blocked edges -- those of the output mesh.  After convergence they are equal.
+ *      9. Quality.  For a participating triangle (p, q, r), with x = face(p, q, r), u = q - p, v = r - q, w = p - r:
+ *           q = (C * sqrt(dot(x, x))) / ((dot(u, u) + dot(v, v)) + dot(w, w)),  C = 3.4641016151377544 (the double at 2 sqrt 3);
+ *         q = 0 where the denominator is 0 or q is NaN.  q is 1 for an equilateral triangle and 0 for one without area.
+ *         quality*[min(15, floor(16 q))] counts the triangles, minQuality* is the smallest q (0 if no triangle takes part);
+ *         *Before of the input, *After of the output. ---- */
+typedef struct mlsgpu_flip_stats
+{
+    uint64_t numVertices, numTriangles;
+    uint64_t outOfRangeTriangles;   /* an index >= numVertices */
+    uint64_t degenerateTriangles;   /* in range, two indices equal */
+    uint64_t numEdges;              /* undirected, of the participating triangles */
+    uint64_t interiorEdges;         /* step 3 */
+    uint64_t rounds, flips, converged;                      /* step 8 */
+    uint64_t nonDelaunayBefore, nonDelaunayAfter, blockedAfter;
+    double minQualityBefore, minQualityAfter;               /* step 9 */
+    uint64_t qualityBefore[16], qualityAfter[16];
+} mlsgpu_flip_stats;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_flip_stats) == 368, "mlsgpu_flip_stats is part of the ABI");
+#else
+typedef char mlsgpu_flip_stats_size_is_368[sizeof(mlsgpu_flip_stats) == 368 ? 1 : -1];
+#endif
+/* numVertices packed float xyz and numTriangles uint32 index triples on ctx's device -> dOutTriangles, uint32 triples with
+ * room for 3 * numTriangles words, which may be exactly dTriangles (in place); any other overlap is not allowed.  Triangle t
+ * of the output is triangle t of the input, flipped or not.  MLSGPU_ERR_INVALID, before anything touches the device, unless
+ * minGain is finite and >= 0, -1 <= minCos <= 1 and stats is not NULL; MLSGPU_ERR_INVALID for a coordinate that is not finite
+ * (counted on the device; nothing is promised about the output then).  MLSGPU_ERR_LENGTH, before anything is allocated,
+ * unless numVertices < 2^32 and 3 * numTriangles < 2^32: the sides of every triangle are sorted, and the sort's values are
+ * 32-bit.  No vertices or no triangles is not an error.  Scratch is allocated for the call and freed on return: 96 bytes per
+ * triangle (three directed side records: the two sides of the sort's 64-bit keys and 32-bit values 72 -- the side the sort
+ * leaves free holds each record's priority and partner -- and the two opposite vertices 24), 24 bytes per vertex (the best
+ * priority, the best key, and where the sides that leave the vertex lie), and the sort's histogram; MLSGPU_ERR_NOMEM if the
+ * device does not have it.  Blocks until the statistics are there: one stream synchronisation per classification, to read
+ * its counts -- rounds + 1 of them, or rounds where the last round had no winner -- and one at the end. */
+int mlsgpu_hip_mesh_flip_edges(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices, const uint32_t *dTriangles,
+                               uint64_t numTriangles, uint32_t maxRounds, double minGain, double minCos,
+                               uint32_t *dOutTriangles, mlsgpu_flip_stats *stats);
+/* The same for every output chunk of a finalized device sink, on the mesher's context, after any fill / simplify / repair /
+ * smooth: each chunk's triangles are flipped where they lie, in place; vertices and chunk layout are untouched, and the
+ * chunks' normals are dropped, so normals requested afterwards are those of the flipped chunk.  Chunks are flipped
+ * INDEPENDENTLY; an edge two chunks share is a boundary edge of each and is never flipped, so the seams stay closed.
+ * *stats: the counts and histograms summed over the chunks, rounds the largest, converged the AND over the chunks that have
+ * triangles (without one: as for a mesh without triangles), the two minima the minima over them.  MLSGPU_ERR_INVALID before
+ * finalize and for the parameters mlsgpu_hip_mesh_flip_edges refuses (no results are lost then); may be called again.  After
+ * any other error the sink's results are dropped: finalize again. */
+int mlsgpu_hip_mesher_flip_edges(mlsgpu_mesher *mesher, uint32_t maxRounds, double minGain, double minCos,
+                                 mlsgpu_flip_stats *stats);
+
 /* ---- hole filling of a device-resident mesh: every small boundary loop is capped by a fan of triangles to the mean of its
  *      vertices, before the mesh crosses the link.  An MLS surface stops where the splats get sparse, and
  *      mlsgpu_hip_mesh_topology counts the holes that leaves (numBoundaries); this closes them.  The reference has no

@@ -165,6 +165,21 @@ class SmoothStats(C.Structure):
         return dict((name, (float if kind is C.c_double else int)(getattr(self, name))) for name, kind in self._fields_)
 
 
+class FlipStats(C.Structure):
+    """mlsgpu_flip_stats: what took no part, edges and interior regular edges, rounds, flips and whether the last round found no
+    winner, the non-Delaunay edges before and after and those a guard refuses, the triangle quality before and after."""
+    _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
+                ("degenerateTriangles", C.c_uint64), ("numEdges", C.c_uint64), ("interiorEdges", C.c_uint64),
+                ("rounds", C.c_uint64), ("flips", C.c_uint64), ("converged", C.c_uint64), ("nonDelaunayBefore", C.c_uint64),
+                ("nonDelaunayAfter", C.c_uint64), ("blockedAfter", C.c_uint64), ("minQualityBefore", C.c_double),
+                ("minQualityAfter", C.c_double), ("qualityBefore", C.c_uint64 * 16), ("qualityAfter", C.c_uint64 * 16)]
+
+    def as_dict(self):
+        """The fields; the two histograms as lists of 16 ints."""
+        return dict((name, [int(x) for x in getattr(self, name)] if name.startswith("quality")
+                     else (float if kind is C.c_double else int)(getattr(self, name))) for name, kind in self._fields_)
+
+
 class FillStats(C.Structure):
     """mlsgpu_fill_stats: what took no part, the boundary sides and their loops, what was filled, the sizes of the result."""
     _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
@@ -446,6 +461,8 @@ def lib():
     sig("mlsgpu_hip_mesher_chunk_normals", C.c_int, vp, u32, P(vp), P(NormalsStats))
     sig("mlsgpu_hip_mesh_smooth", C.c_int, vp, vp, u64, vp, u64, u32, C.c_float, C.c_float, u32, vp, P(SmoothStats))
     sig("mlsgpu_hip_mesher_smooth", C.c_int, vp, u32, C.c_float, C.c_float, u32, P(SmoothStats))
+    sig("mlsgpu_hip_mesh_flip_edges", C.c_int, vp, vp, u64, vp, u64, u32, C.c_double, C.c_double, vp, P(FlipStats))
+    sig("mlsgpu_hip_mesher_flip_edges", C.c_int, vp, u32, C.c_double, C.c_double, P(FlipStats))
     sig("mlsgpu_hip_mesh_fill_holes", C.c_int, vp, vp, u64, vp, u64, u32, vp, vp, u64, vp, u64, P(FillStats))
     sig("mlsgpu_hip_mesher_fill_holes", C.c_int, vp, u32, P(FillStats))
     sig("mlsgpu_hip_mesh_repair", C.c_int, vp, vp, u64, vp, u64, u32, vp, u64, vp, u64, vp, P(RepairStats))
@@ -1002,6 +1019,14 @@ class Mesher:
                                                        C.byref(st)))
         return st.as_dict()
 
+    def flip_edges(self, max_rounds, min_gain=1e-6, min_cos=0.5):
+        """Every output chunk of the finalized sink through at most max_rounds rounds of Delaunay edge flips, in place
+        (mesh_flip_edges): triangles only, the vertices and the chunk layout stay.  Returns the statistics: counts and
+        histograms summed over the chunks, rounds the largest, converged the AND, the minima the minima."""
+        st = FlipStats()
+        check(lib().mlsgpu_hip_mesher_flip_edges(self.h, int(max_rounds), float(min_gain), float(min_cos), C.byref(st)))
+        return st.as_dict()
+
     def smooth(self, iterations, lam=0.5, mu=-0.53, boundary=SMOOTH_BOUNDARY_FIXED):
         """Every output chunk of the finalized sink smoothed in place (mesh_smooth): positions only, the triangles and the
         chunk layout stay.  Returns the statistics: counts summed over the chunks, exponent and maxima the largest."""
@@ -1238,6 +1263,39 @@ def mesh_smooth(ctx, vertices, triangles, iterations, lam, mu, boundary=SMOOTH_B
         check(lib().mlsgpu_hip_mesh_smooth(ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, int(iterations), float(lam),
                                            float(mu), int(boundary), ov.ptr if ov else None, C.byref(st)))
         out = ov.download(np.float32, 3 * nv).reshape(-1, 3) if ov is not None else np.zeros((0, 3), np.float32)
+    finally:
+        for buf in own:
+            buf.free()
+    return out, st.as_dict()
+
+
+def mesh_flip_edges(ctx, vertices, triangles, max_rounds, min_gain=1e-6, min_cos=0.5, num_vertices=None, num_triangles=None,
+                    in_place=False):
+    """Delaunay edge flips on the device (mlsgpu_hip_mesh_flip_edges), with the triangle quality before and after;
+    bit-reproducible whatever the schedule or the order of the triangles.  `vertices` / `triangles` are numpy arrays (uploaded
+    for the call) or DeviceBuffers of packed float32 xyz / uint32 triples; in_place writes the result over the triangles on the
+    device.  Returns (triangles uint32 [T, 3] downloaded, statistics as a dict)."""
+    own = []
+
+    def on_device(a, dtype, count):
+        if isinstance(a, DeviceBuffer):
+            return a, (a.nbytes // 12 if count is None else count)
+        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
+        buf = DeviceBuffer(ctx, array=a) if a.size else None
+        if buf is not None:
+            own.append(buf)
+        return buf, (len(a) if count is None else count)
+
+    st = FlipStats()
+    try:
+        dv, nv = on_device(vertices, np.float32, num_vertices)
+        dt, nt = on_device(triangles, np.uint32, num_triangles)
+        ot = dt if in_place else DeviceBuffer(ctx, nbytes=12 * nt) if nt and dt is not None else None
+        if ot is not None and not in_place:
+            own.append(ot)
+        check(lib().mlsgpu_hip_mesh_flip_edges(ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, int(max_rounds),
+                                               float(min_gain), float(min_cos), ot.ptr if ot else None, C.byref(st)))
+        out = ot.download(np.uint32, 3 * nt).reshape(-1, 3) if ot is not None else np.zeros((0, 3), np.uint32)
     finally:
         for buf in own:
             buf.free()

@@ -1359,6 +1359,57 @@ MLSGPU_API int mlsgpu_hip_mesher_smooth(mlsgpu_mesher *m, uint32_t iterations, f
     return MLSGPU_OK;
 }
 
+/* Every output chunk through mlsgpu_hip_mesh_flip_edges (flip.hip), in place: only the triangles change. */
+MLSGPU_API int mlsgpu_hip_mesher_flip_edges(mlsgpu_mesher *m, uint32_t maxRounds, double minGain, double minCos, mlsgpu_flip_stats *stats)
+{
+    REQUIRE(m != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
+    /* mlsgpu_hip_mesh_flip_edges's own checks, here so that a refused parameter costs no results */
+    REQUIRE(std::isfinite(minGain) && minGain >= 0.0 && minCos >= -1.0 && minCos <= 1.0, MLSGPU_ERR_INVALID);
+    mlsgpu_ctx *const ctx = m->ctx;
+    m->dropNormals();           /* the triangles change */
+    std::memset(stats, 0, sizeof(*stats));
+    stats->converged = maxRounds > 0 ? 1 : 0;       /* the AND over the chunks starts where a mesh without triangles ends */
+    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
+    bool first = true;
+    for (size_t c = 0; c < nc; c++)
+    {
+        const auto [v0, t0, nv, nt] = m->span(c);
+        if (nt == 0)
+            continue;           /* a chunk without triangles has no output (finalize) */
+        mlsgpu_flip_stats one;
+        const int rc = mlsgpu_hip_mesh_flip_edges(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, maxRounds, minGain, minCos,
+                                                  m->outTriangles + 3 * t0, &one);
+        if (rc != MLSGPU_OK)
+        {
+            m->dropResults();   /* earlier chunks are flipped already */
+            return rc;
+        }
+        stats->numVertices += one.numVertices;
+        stats->numTriangles += one.numTriangles;
+        stats->outOfRangeTriangles += one.outOfRangeTriangles;
+        stats->degenerateTriangles += one.degenerateTriangles;
+        stats->numEdges += one.numEdges;
+        stats->interiorEdges += one.interiorEdges;
+        stats->rounds = std::max(stats->rounds, one.rounds);
+        stats->flips += one.flips;
+        stats->converged &= one.converged;
+        stats->nonDelaunayBefore += one.nonDelaunayBefore;
+        stats->nonDelaunayAfter += one.nonDelaunayAfter;
+        stats->blockedAfter += one.blockedAfter;
+        stats->minQualityBefore = first ? one.minQualityBefore : std::min(stats->minQualityBefore, one.minQualityBefore);
+        stats->minQualityAfter = first ? one.minQualityAfter : std::min(stats->minQualityAfter, one.minQualityAfter);
+        for (int k = 0; k < 16; k++)
+        {
+            stats->qualityBefore[k] += one.qualityBefore[k];
+            stats->qualityAfter[k] += one.qualityAfter[k];
+        }
+        first = false;
+    }
+    return MLSGPU_OK;
+}
+
 /* Every output chunk that has triangles through mlsgpu_hip_mesh_fill_holes (fill.hip).  The chunks grow, so they cannot stay
  * where they lie: a first round asks every chunk for its sizes, a second fills it into new arrays, behind the chunk before.
  * Nothing of the sink changes before the last chunk is done: an error leaves the results as they were. */

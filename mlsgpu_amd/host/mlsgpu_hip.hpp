@@ -267,6 +267,18 @@ inline mlsgpu_smooth_stats smooth(const Context &ctx, const Buffer<float> &verti
     return st;
 }
 
+/// Delaunay edge flips of a mesh in device memory, with its quality report (mlsgpu_hip_mesh_flip_edges): outTriangles has
+/// room for 3 indices per triangle and is either `triangles` itself (in place) or does not overlap the inputs.
+inline mlsgpu_flip_stats flipEdges(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
+                                   const Buffer<std::uint32_t> &triangles, std::uint64_t numTriangles, std::uint32_t maxRounds,
+                                   double minGain, double minCos, Buffer<std::uint32_t> &outTriangles)
+{
+    mlsgpu_flip_stats st;
+    check(mlsgpu_hip_mesh_flip_edges(ctx.get(), vertices.get(), numVertices, triangles.get(), numTriangles, maxRounds, minGain, minCos,
+                                     outTriangles.get(), &st));
+    return st;
+}
+
 /// Area-weighted vertex normals of a mesh in device memory (mlsgpu_hip_mesh_normals): outNormals has room for 3 floats per
 /// vertex and does not overlap the inputs.
 inline mlsgpu_normals_stats normals(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
@@ -823,6 +835,15 @@ public:
     {
         mlsgpu_repair_stats st;
         check(mlsgpu_hip_mesher_repair(h, flags, &st));
+        return st;
+    }
+    /// Every output chunk of the finalized mesher through at most maxRounds rounds of Delaunay edge flips, in place
+    /// (mlsgpu_hip_mesher_flip_edges): triangles only, behind repair() and before smooth().  Counts and histograms summed over
+    /// the chunks, rounds the largest, converged the AND, the minima the minima.
+    mlsgpu_flip_stats flipEdges(std::uint32_t maxRounds, double minGain = 1e-6, double minCos = 0.5)
+    {
+        mlsgpu_flip_stats st;
+        check(mlsgpu_hip_mesher_flip_edges(h, maxRounds, minGain, minCos, &st));
         return st;
     }
     /// Every output chunk of the finalized mesher smoothed in place (mlsgpu_hip_mesher_smooth); between finalize() -- or

@@ -1,0 +1,77 @@
+"""CPU-side checks of the edge flips' C-ABI: struct layout, symbols, and the argument checks that need no device."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import flip_cases as fc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SYMBOLS = ("mlsgpu_hip_mesh_flip_edges", "mlsgpu_hip_mesher_flip_edges")
+
+
+def header():
+    return open(os.path.join(ROOT, "include", "mlsgpu_hip.h")).read()
+
+
+def test_struct_size_is_the_headers():
+    from mlsgpu_amd import binding as b
+    assert re.findall(r"static_assert\(sizeof\(mlsgpu_flip_stats\) == (\d+)", header()) == ["368"]
+    assert re.search(r"typedef char mlsgpu_flip_stats_size_is_368\[sizeof\(mlsgpu_flip_stats\) == 368 \? 1 : -1\]", header())
+    assert C.sizeof(b.FlipStats) == 368
+    assert [f[0] for f in b.FlipStats._fields_] == list(fc.STAT_NAMES)
+    st = b.FlipStats(flips=7, converged=1, minQualityAfter=0.25)
+    st.qualityBefore[15] = 5
+    st.qualityAfter[0] = 3
+    d = st.as_dict()
+    assert list(d) == list(fc.STAT_NAMES)
+    assert d == dict(fc.empty_stats(), flips=7, converged=1, minQualityAfter=0.25, qualityBefore=[0] * 15 + [5], qualityAfter=[3] + [0] * 15)
+    assert all(type(d[name]) is (float if name.startswith("minQuality") else list if name.startswith("quality") else int) for name in d)
+
+
+def test_layout_is_the_c_compilers(tmp_path):
+    """The header as plain C: the size and every offset of the struct the binding mirrors."""
+    from mlsgpu_amd import binding as b
+    names = [f[0] for f in b.FlipStats._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "mlsgpu_hip.h"\nint main(void) {\n'
+                   'printf("%%zu %s\\n", sizeof(mlsgpu_flip_stats), %s);\nreturn 0; }\n'
+                   % (" ".join(["%zu"] * len(names)), ", ".join("offsetof(mlsgpu_flip_stats, %s)" % n for n in names)))
+    exe = tmp_path / "layout"
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    out = subprocess.check_output([str(exe)]).decode().split()
+    assert [int(x) for x in out] == [368] + [getattr(b.FlipStats, n).offset for n in names]
+
+
+def test_symbols_are_declared_exported_and_bound():
+    import mlsgpu_amd
+    from mlsgpu_amd import binding as b
+    raw = C.CDLL(mlsgpu_amd.library_path())
+    L = mlsgpu_amd.lib()
+    hpp = open(os.path.join(ROOT, "mlsgpu_amd", "host", "mlsgpu_hip.hpp")).read()
+    for name in SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % name, header()), name
+        assert hasattr(raw, name), name
+        assert getattr(L, name).argtypes, name
+        assert name in hpp, name
+    assert L.mlsgpu_hip_mesh_flip_edges.argtypes[6:8] == [C.c_double, C.c_double]
+    assert L.mlsgpu_hip_mesher_flip_edges.argtypes[2:4] == [C.c_double, C.c_double]
+    assert callable(b.mesh_flip_edges) and mlsgpu_amd.mesh_flip_edges is b.mesh_flip_edges
+    assert callable(b.Mesher.flip_edges)
+    assert mlsgpu_amd.FlipStats is b.FlipStats
+    assert "flipEdges" in hpp
+    makefile = open(os.path.join(ROOT, "mlsgpu_amd", "csrc", "Makefile")).read()
+    assert re.search(r"^OBJS = .*\bflip\.o\b", makefile, re.M)
+
+
+def test_argument_checks_need_no_gpu():
+    """A NULL context / mesher / statistics comes back before any device work."""
+    from mlsgpu_amd import binding as b
+    L = b.lib()
+    st = b.FlipStats()
+    for call in (lambda: L.mlsgpu_hip_mesh_flip_edges(None, None, 0, None, 0, 4, 1e-6, 0.5, None, C.byref(st)),
+                 lambda: L.mlsgpu_hip_mesh_flip_edges(None, None, 0, None, 0, 4, 1e-6, 0.5, None, None),
+                 lambda: L.mlsgpu_hip_mesher_flip_edges(None, 4, 1e-6, 0.5, C.byref(st)),
+                 lambda: L.mlsgpu_hip_mesher_flip_edges(None, 4, 1e-6, 0.5, None)):
+        assert call() == 1
+        assert b"requirement failed" in L.mlsgpu_hip_last_error()
