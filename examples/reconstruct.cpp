@@ -12,7 +12,7 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--flip-edges R] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--collapse-edges F] [--flip-edges R] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
  * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
@@ -28,6 +28,11 @@
  *   with a repeated directed side are dropped and pinched vertices split (with `pinches`: every umbrella of a vertex becomes a
  *   vertex of its own), so that --check says `manifold yes` -- after --simplify, which can make a chunk non-manifold, and
  *   before --flip-edges, --smooth, --normals and --check; one line with the statistics.
+ * --collapse-edges F (device weld only, F > 0 in grid spacings): before the write, the interior edges of every output chunk
+ *   that are at most F spacings long are collapsed where the chunk lies (minCos 0.5, at most 64 rounds): a vertex and two
+ *   triangles go per edge -- the needles that marching leaves where the surface passes close to a lattice vertex --, the
+ *   vertices on a chunk's boundary stay, and so does the topology -- after --simplify and --repair, before --flip-edges,
+ *   --smooth and --normals; one line with the statistics and the smallest triangle quality before and after.
  * --flip-edges R (device weld only, R > 0): before the write, every output chunk goes through at most R rounds of Delaunay edge
  *   flips where it lies (minGain 1e-6, minCos 0.5): connectivity only, the vertices and the edges on a chunk's boundary stay
  *   -- after --simplify and --repair, before --smooth; one line with the statistics and the smallest triangle quality before
@@ -36,7 +41,7 @@
  *   where it lies, the vertices on a chunk's boundary held fixed -- after --simplify and --flip-edges when they are given; one line with the
  *   statistics.
  * --deviation D (device weld only, D > 0 in world units): the chunks are kept as the weld left them, and after the last of
- *   --fill-holes, --simplify, --repair, --flip-edges and --smooth two lines say how far the output lies from them: `moved`, the output's
+ *   --fill-holes, --simplify, --repair, --collapse-edges, --flip-edges and --smooth two lines say how far the output lies from them: `moved`, the output's
  *   vertices against the kept surface, and `lost`, the kept vertices against the output's surface -- the points within and
  *   beyond D, the largest and the RMS distance, and the distances that 50 % and 90 % of the points within stay under, read
  *   off a histogram of 16 bins.  Without such a stage `moved` is all zeros.
@@ -96,7 +101,8 @@ int main(int argc, char **argv)
     bool simplifyGiven = false, quadricGiven = false, smoothGiven = false, fillGiven = false, repairGiven = false;
     std::uint32_t repairFlags = 0;
     long smoothIterations = 0, fillEdges = 0, flipRounds = 0;
-    bool flipGiven = false;
+    bool flipGiven = false, collapseGiven = false;
+    double collapseSpacings = 0.0;
     float deviationDistance = 0.0f;
     bool deviationGiven = false, intersectionsGiven = false;
     long compactBits = 0;
@@ -138,6 +144,11 @@ int main(int argc, char **argv)
         {
             flipRounds = atol(argv[++i]);
             flipGiven = true;
+        }
+        else if (a == "--collapse-edges" && i + 1 < argc)
+        {
+            collapseSpacings = atof(argv[++i]);
+            collapseGiven = true;
         }
         else if (a == "--fill-holes" && i + 1 < argc)
         {
@@ -182,7 +193,7 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--flip-edges R] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--collapse-edges F] [--flip-edges R] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
         return 2;
     }
@@ -229,6 +240,16 @@ int main(int argc, char **argv)
     if (flipGiven && hostWeld)
     {
         std::cerr << "--flip-edges needs --weld device: the host welder's output is not on the device\n";
+        return 2;
+    }
+    if (collapseGiven && !(collapseSpacings > 0.0 && collapseSpacings <= std::numeric_limits<float>::max()))
+    {
+        std::cerr << "--collapse-edges takes a number of grid spacings > 0\n";
+        return 2;
+    }
+    if (collapseGiven && hostWeld)
+    {
+        std::cerr << "--collapse-edges needs --weld device: the host welder's output is not on the device\n";
         return 2;
     }
     if (fillGiven && !(fillEdges >= 3 && fillEdges <= (long) MLSGPU_FILL_MAX_EDGES))
@@ -339,6 +360,8 @@ int main(int argc, char **argv)
         std::size_t filledChunks = 0;
         mlsgpu_repair_stats repaired = mlsgpu_repair_stats();
         std::size_t repairedChunks = 0;
+        mlsgpu_collapse_stats collapsed = mlsgpu_collapse_stats();
+        std::size_t collapsedChunks = 0;
         mlsgpu_flip_stats flipped = mlsgpu_flip_stats();
         std::size_t flippedChunks = 0;
         std::pair<mlsgpu_deviation, mlsgpu_deviation> deviated;
@@ -396,6 +419,11 @@ int main(int argc, char **argv)
             {
                 repaired = deviceMesher.repair(repairFlags);
                 repairedChunks = chunks;
+            }
+            if (collapseGiven)
+            {
+                collapsed = deviceMesher.collapseEdges(64, collapseSpacings * spacing, 0.5);
+                collapsedChunks = chunks;
             }
             if (flipGiven)
             {
@@ -473,6 +501,15 @@ int main(int argc, char **argv)
                         (unsigned long long) repaired.unusedVertices, (unsigned long long) repaired.splitVertices,
                         (unsigned long long) repaired.numVertices, (unsigned long long) repaired.outVertices,
                         (unsigned long long) repaired.numTriangles, (unsigned long long) repaired.outTriangles);
+        if (collapseGiven)
+            std::printf("collapse-edges chunks %zu interior-edges %llu fixed %llu rounds %llu collapses %llu short %llu -> %llu "
+                        "blocked %llu vertices %llu -> %llu triangles %llu -> %llu min-quality %.9g -> %.9g\n",
+                        collapsedChunks, (unsigned long long) collapsed.interiorEdges, (unsigned long long) collapsed.fixedVertices,
+                        (unsigned long long) collapsed.rounds, (unsigned long long) collapsed.collapses,
+                        (unsigned long long) collapsed.shortBefore, (unsigned long long) collapsed.shortAfter,
+                        (unsigned long long) collapsed.blockedAfter, (unsigned long long) collapsed.numVertices,
+                        (unsigned long long) collapsed.outVertices, (unsigned long long) collapsed.numTriangles,
+                        (unsigned long long) collapsed.outTriangles, collapsed.minQualityBefore, collapsed.minQualityAfter);
         if (flipGiven)
             std::printf("flip-edges chunks %zu interior-edges %llu rounds %llu flips %llu non-delaunay %llu -> %llu blocked %llu "
                         "min-quality %.9g -> %.9g\n",

@@ -1001,6 +1001,112 @@ int mlsgpu_hip_mesh_flip_edges(mlsgpu_ctx *ctx, const float *dVertices, uint64_t
 int mlsgpu_hip_mesher_flip_edges(mlsgpu_mesher *mesher, uint32_t maxRounds, double minGain, double minCos,
                                  mlsgpu_flip_stats *stats);
 
+/* ---- short-edge collapse of a device-resident mesh, with the flips' triangle quality report: marching tetrahedra's worst
+ *      slivers have a short edge -- two vertices almost on top of each other where the surface passes close to a lattice
+ *      vertex --, which no flip improves.  Collapsing an interior edge of at most maxLength takes the needle out where it is:
+ *      one vertex and two triangles go, a vertex moves by at most maxLength / 2, and everything else keeps its bits.  The
+ *      reference has no counterpart.  Deterministic in the flips' sense: every floating-point operation below is ONE
+ *      correctly rounded IEEE double operation on exactly converted floats (no contraction), in the order written, every
+ *      statistic is a count, a minimum or a maximum, and the output depends neither on the schedule nor on the order of the
+ *      triangles or of a triangle's corners (only q of step 11 is taken in a row's own order, as for the flips).  u - v, dot,
+ *      cross and face are those of the flips.  T = maxLength * maxLength.
+ *      1. Participation is step 1 of the flips: a triangle with an index >= V is counted in outOfRangeTriangles, otherwise one
+ *         with two equal indices in degenerateTriangles (both of the input), and neither takes part; unlike there, they are
+ *         not part of the output, which is renumbered.
+ *      2. The SIDES are the directed sides of the participating triangles.  A vertex is FIXED if a side that leaves it or
+ *         arrives at it occurs more than once or has no reverse: every boundary vertex -- and with them every seam between
+ *         output chunks -- and the ends of irregular edges.  numEdges, interiorEdges (step 3) and fixedVertices are those of
+ *         the first classification.
+ *      3. An edge {a, b}, a < b, is INTERIOR REGULAR as in step 3 of the flips, with T1 = (a, b, c), T2 = (b, a, d), c != d.
+ *      4. L2 = dot(pb - pa, pb - pa).  The edge is SHORT if L2 <= T (never for a NaN; an edge of length zero is short even at
+ *         maxLength 0).  minLengthSq* is the smallest L2 of the interior regular edges, +infinity if there is none.
+ *      5. Survivor.  If exactly one end is fixed, it survives with the bits of its position and the other end is removed.  If
+ *         neither is, a survives and b is removed, and the new position is, per coordinate,
+ *         (float) (((double) pa + (double) pb) * 0.5).  (Both fixed: guard (i).)
+ *      6. Guards.  N(x) = the other vertices of the participating triangles that hold x.  A short edge is BLOCKED if
+ *           (i)   both ends are fixed, or
+ *           (ii)  more than MLSGPU_COLLAPSE_MAX_VALENCE participating triangles hold a, or more than that hold b (the bound
+ *                 on what one thread walks; marching's valences are far below it), or
+ *           (iii) N(a) and N(b) have a vertex other than c and d in common (the link condition), or
+ *           (iv)  c -> d or d -> c is a side (the link condition's edge part, conservatively: it blocks the tetrahedron), or
+ *           (v)   a participating triangle other than T1 and T2 that holds x = a or x = b fails the fold test: rotated to
+ *                 (x, q, r), with n = face(px, pq, pr) and n' = face(p', pq, pr), p' the double of the new position, it
+ *                 fails if dot(n, n) != 0 and
+ *                 dot(n, n') > 0 && dot(n, n') >= (minCos * sqrt(dot(n, n))) * sqrt(dot(n', n')) is false,
+ *         and a CANDIDATE otherwise.
+ *      7. The choice of a round.  With S = {a, b} + N(a) + N(b), a candidate WINS if at every vertex of its S it is the best of
+ *         all candidates that have that vertex in their S: the smaller L2 wins, among equal L2 the smaller key
+ *         a << bitLength(V) | b, in the input's vertex numbers.  Winners have disjoint S: no triangle is near two of them,
+ *         none changes another's guards, and their order does not matter.  The best candidate of the mesh always wins: a
+ *         round without a winner is a round without a candidate.
+ *      8. Rewrite.  For every winner the removed vertex becomes the survivor in every triangle that holds it -- T1 and T2
+ *         then name the survivor twice and take no part any more -- and the survivor gets its position.
+ *      9. Rounds, as step 8 of the flips: the mesh is classified (steps 1-6, on the rewritten rows and positions); then,
+ *         while fewer than maxRounds rounds have run: a round chooses and rewrites (rounds counts it); if it had no winner,
+ *         converged = 1 and the rounds end; otherwise its winners are added to collapses and the mesh is classified again.
+ *         maxRounds = 0 is a pure report.  A mesh in which no triangle takes part has rounds = converged = 1 unless
+ *         maxRounds = 0.  shortBefore is the first classification's number of short edges; shortAfter and blockedAfter are
+ *         the last one's short and blocked edges -- those of the output mesh.  After convergence they are equal.
+ *     10. Output.  The vertices that a participating triangle still uses, in ascending input order, each with the bits it
+ *         ended with (outVertices; unusedVertices counts the others, removed or never used); the participating triangles in
+ *         input order with their corners renumbered (outTriangles); dOutSource, if not NULL, gets every output vertex's
+ *         input index.
+ *     11. Quality: q of step 9 of the flips, *Before of the input, *After of the output.
+ *      What follows: an input that mlsgpu_hip_mesh_topology calls manifold gives an output with the same manifold flag,
+ *      components, boundaries, boundary edges and Euler characteristic; fixed vertices keep their order and their bits; a mesh
+ *      without a short edge, a defect or an unused vertex comes back bit for bit; collapsing a converged output again makes
+ *      no collapse; scaling the coordinates and maxLength by a power of two scales the output and changes no count (as long
+ *      as nothing leaves the floats' and doubles' normal range). ---- */
+#define MLSGPU_COLLAPSE_MAX_VALENCE 64u
+typedef struct mlsgpu_collapse_stats
+{
+    uint64_t numVertices, numTriangles;
+    uint64_t outOfRangeTriangles;   /* an index >= numVertices */
+    uint64_t degenerateTriangles;   /* in range, two indices equal */
+    uint64_t numEdges;              /* undirected, of the participating triangles */
+    uint64_t interiorEdges;         /* step 3 */
+    uint64_t fixedVertices;         /* step 2 */
+    uint64_t rounds, collapses, converged;                  /* step 9 */
+    uint64_t shortBefore, shortAfter, blockedAfter;
+    uint64_t unusedVertices, outVertices, outTriangles;     /* step 10 */
+    double minQualityBefore, minQualityAfter;               /* step 11 */
+    double minLengthSqBefore, minLengthSqAfter;             /* step 4 */
+    uint64_t qualityBefore[16], qualityAfter[16];
+} mlsgpu_collapse_stats;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_collapse_stats) == 416, "mlsgpu_collapse_stats is part of the ABI");
+#else
+typedef char mlsgpu_collapse_stats_size_is_416[sizeof(mlsgpu_collapse_stats) == 416 ? 1 : -1];
+#endif
+/* numVertices packed float xyz and numTriangles uint32 index triples on ctx's device -> dOutVertices / dOutTriangles (and
+ * dOutSource, uint32 per output vertex, or NULL), with room for capVertices / capTriangles rows; no overlap with the inputs,
+ * which are left alone.  The capacity rule and the size query are mlsgpu_hip_mesh_repair's: MLSGPU_ERR_LENGTH, with *stats
+ * complete, if a capacity is below outVertices / outTriangles -- NULL outputs with zero capacities ask for the sizes (and
+ * come back MLSGPU_OK if the result is empty).  MLSGPU_ERR_INVALID, before anything touches the device, unless maxLength is
+ * finite and >= 0, 0 <= minCos <= 1 and stats is not NULL; MLSGPU_ERR_INVALID for a coordinate that is not finite (counted on
+ * the device).  MLSGPU_ERR_LENGTH, before anything is allocated, unless numVertices < 2^32 and 3 * numTriangles < 2^32.  No
+ * vertices or no triangles is not an error.  Scratch is allocated for the call and freed on return: 96 bytes per triangle
+ * (three directed side records: the two sides of the sort's 64-bit keys and 32-bit values 72 -- the side the sort leaves free
+ * holds a candidate's L2 --, each side's third vertex 12, the row's working copy 12), 44 bytes per vertex (the best L2, the
+ * best key, where the sides that leave the vertex lie, the fixed flag, the position's working copy, the output number), the
+ * sort's histogram and the scans' tile sums; MLSGPU_ERR_NOMEM if the device does not have it.  Blocks until the statistics
+ * are there: one stream synchronisation per classification -- rounds + 1 of them, or rounds where the last round had no
+ * winner -- one for the sizes and one behind the output. */
+int mlsgpu_hip_mesh_collapse_edges(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices, const uint32_t *dTriangles,
+                                   uint64_t numTriangles, uint32_t maxRounds, double maxLength, double minCos,
+                                   float *dOutVertices, uint64_t capVertices, uint32_t *dOutTriangles, uint64_t capTriangles,
+                                   uint32_t *dOutSource, mlsgpu_collapse_stats *stats);
+/* The same for every output chunk of a finalized device sink, on the mesher's context, after any fill / simplify / repair /
+ * smooth / flip, by the route of mlsgpu_hip_mesher_repair: every chunk is sized first and then collapsed into new arrays,
+ * each chunk behind the one before, and the new generation takes the old one's place only when all chunks are done -- an
+ * error leaves the results as they were.  The chunks' normals are dropped.  Chunks are collapsed INDEPENDENTLY: a vertex two
+ * chunks share lies on the boundary of each, so it is fixed in both and the seams stay closed bit for bit.  *stats: the counts
+ * and histograms summed over the chunks, rounds the largest, converged the AND over the chunks that have triangles (without
+ * one: as for a mesh without triangles), the four minima the minima over them.  MLSGPU_ERR_INVALID before finalize and for
+ * the parameters mlsgpu_hip_mesh_collapse_edges refuses; may be called again. */
+int mlsgpu_hip_mesher_collapse_edges(mlsgpu_mesher *mesher, uint32_t maxRounds, double maxLength, double minCos,
+                                     mlsgpu_collapse_stats *stats);
+
 /* ---- hole filling of a device-resident mesh: every small boundary loop is capped by a fan of triangles to the mean of its
  *      vertices, before the mesh crosses the link.  An MLS surface stops where the splats get sparse, and
  *      mlsgpu_hip_mesh_topology counts the holes that leaves (numBoundaries); this closes them.  The reference has no

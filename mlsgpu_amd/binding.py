@@ -180,6 +180,24 @@ class FlipStats(C.Structure):
                      else (float if kind is C.c_double else int)(getattr(self, name))) for name, kind in self._fields_)
 
 
+class CollapseStats(C.Structure):
+    """mlsgpu_collapse_stats: what took no part, edges, interior regular edges and fixed vertices, rounds, collapses and whether
+    the last round found no winner, the short edges before and after and those a guard refuses, the sizes of the result, the
+    triangle quality and the smallest squared edge length before and after."""
+    _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
+                ("degenerateTriangles", C.c_uint64), ("numEdges", C.c_uint64), ("interiorEdges", C.c_uint64),
+                ("fixedVertices", C.c_uint64), ("rounds", C.c_uint64), ("collapses", C.c_uint64), ("converged", C.c_uint64),
+                ("shortBefore", C.c_uint64), ("shortAfter", C.c_uint64), ("blockedAfter", C.c_uint64),
+                ("unusedVertices", C.c_uint64), ("outVertices", C.c_uint64), ("outTriangles", C.c_uint64),
+                ("minQualityBefore", C.c_double), ("minQualityAfter", C.c_double), ("minLengthSqBefore", C.c_double),
+                ("minLengthSqAfter", C.c_double), ("qualityBefore", C.c_uint64 * 16), ("qualityAfter", C.c_uint64 * 16)]
+
+    def as_dict(self):
+        """The fields; the two histograms as lists of 16 ints."""
+        return dict((name, [int(x) for x in getattr(self, name)] if name.startswith("quality")
+                     else (float if kind is C.c_double else int)(getattr(self, name))) for name, kind in self._fields_)
+
+
 class FillStats(C.Structure):
     """mlsgpu_fill_stats: what took no part, the boundary sides and their loops, what was filled, the sizes of the result."""
     _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
@@ -463,6 +481,9 @@ def lib():
     sig("mlsgpu_hip_mesher_smooth", C.c_int, vp, u32, C.c_float, C.c_float, u32, P(SmoothStats))
     sig("mlsgpu_hip_mesh_flip_edges", C.c_int, vp, vp, u64, vp, u64, u32, C.c_double, C.c_double, vp, P(FlipStats))
     sig("mlsgpu_hip_mesher_flip_edges", C.c_int, vp, u32, C.c_double, C.c_double, P(FlipStats))
+    sig("mlsgpu_hip_mesh_collapse_edges", C.c_int, vp, vp, u64, vp, u64, u32, C.c_double, C.c_double, vp, u64, vp, u64, vp,
+        P(CollapseStats))
+    sig("mlsgpu_hip_mesher_collapse_edges", C.c_int, vp, u32, C.c_double, C.c_double, P(CollapseStats))
     sig("mlsgpu_hip_mesh_fill_holes", C.c_int, vp, vp, u64, vp, u64, u32, vp, vp, u64, vp, u64, P(FillStats))
     sig("mlsgpu_hip_mesher_fill_holes", C.c_int, vp, u32, P(FillStats))
     sig("mlsgpu_hip_mesh_repair", C.c_int, vp, vp, u64, vp, u64, u32, vp, u64, vp, u64, vp, P(RepairStats))
@@ -1027,6 +1048,15 @@ class Mesher:
         check(lib().mlsgpu_hip_mesher_flip_edges(self.h, int(max_rounds), float(min_gain), float(min_cos), C.byref(st)))
         return st.as_dict()
 
+    def collapse_edges(self, max_rounds, max_length, min_cos=0.5):
+        """Every output chunk of the finalized sink with its interior edges of at most max_length collapsed
+        (mesh_collapse_edges): a vertex and two triangles go per edge, seams and boundaries keep their bits.  The chunks move
+        into new arrays: addresses from an earlier chunk() are gone.  Returns the statistics: counts and histograms summed over
+        the chunks, rounds the largest, converged the AND, the minima the minima."""
+        st = CollapseStats()
+        check(lib().mlsgpu_hip_mesher_collapse_edges(self.h, int(max_rounds), float(max_length), float(min_cos), C.byref(st)))
+        return st.as_dict()
+
     def smooth(self, iterations, lam=0.5, mu=-0.53, boundary=SMOOTH_BOUNDARY_FIXED):
         """Every output chunk of the finalized sink smoothed in place (mesh_smooth): positions only, the triangles and the
         chunk layout stay.  Returns the statistics: counts summed over the chunks, exponent and maxima the largest."""
@@ -1300,6 +1330,49 @@ def mesh_flip_edges(ctx, vertices, triangles, max_rounds, min_gain=1e-6, min_cos
         for buf in own:
             buf.free()
     return out, st.as_dict()
+
+
+def mesh_collapse_edges(ctx, vertices, triangles, max_rounds, max_length, min_cos=0.5, num_vertices=None, num_triangles=None,
+                        with_source=False):
+    """Short-edge collapse on the device (mlsgpu_hip_mesh_collapse_edges), with the triangle quality before and after: every
+    interior edge of at most max_length that the guards admit goes, with one vertex and two triangles, and the topology stays;
+    bit-reproducible whatever the schedule or the order of the triangles.  `vertices` / `triangles` are numpy arrays (uploaded
+    for the call) or DeviceBuffers of packed float32 xyz / uint32 triples, which are left alone.  One call asks for the sizes,
+    a second one writes.  Returns (vertices float32 [V', 3], triangles uint32 [T', 3], statistics as a dict), the arrays
+    downloaded, and with with_source a fourth: the input index of every output vertex, uint32 [V']."""
+    own = []
+
+    def on_device(a, dtype, count):
+        if isinstance(a, DeviceBuffer):
+            return a, (a.nbytes // 12 if count is None else count)
+        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
+        buf = DeviceBuffer(ctx, array=a) if a.size else None
+        if buf is not None:
+            own.append(buf)
+        return buf, (len(a) if count is None else count)
+
+    st = CollapseStats()
+    try:
+        dv, nv = on_device(vertices, np.float32, num_vertices)
+        dt, nt = on_device(triangles, np.uint32, num_triangles)
+        args = (ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, int(max_rounds), float(max_length), float(min_cos))
+        rc = lib().mlsgpu_hip_mesh_collapse_edges(*args, None, 0, None, 0, None, C.byref(st))
+        if rc != 0 and not (rc == _LENGTH and st.outVertices + st.outTriangles > 0):
+            check(rc)
+        ov = DeviceBuffer(ctx, nbytes=12 * st.outVertices) if st.outVertices else None
+        ot = DeviceBuffer(ctx, nbytes=12 * st.outTriangles) if st.outTriangles else None
+        os_ = DeviceBuffer(ctx, nbytes=4 * st.outVertices) if st.outVertices and with_source else None
+        own.extend(x for x in (ov, ot, os_) if x is not None)
+        if rc != 0:
+            check(lib().mlsgpu_hip_mesh_collapse_edges(*args, ov.ptr if ov else None, st.outVertices, ot.ptr if ot else None,
+                                                       st.outTriangles, os_.ptr if os_ else None, C.byref(st)))
+        out_v = ov.download(np.float32, 3 * st.outVertices).reshape(-1, 3) if ov else np.zeros((0, 3), np.float32)
+        out_t = ot.download(np.uint32, 3 * st.outTriangles).reshape(-1, 3) if ot else np.zeros((0, 3), np.uint32)
+        out_s = os_.download(np.uint32, st.outVertices) if os_ else np.zeros(0, np.uint32)
+    finally:
+        for buf in own:
+            buf.free()
+    return (out_v, out_t, st.as_dict(), out_s) if with_source else (out_v, out_t, st.as_dict())
 
 
 def mesh_fill_holes(ctx, vertices, triangles, max_edges, pinned=None, num_vertices=None, num_triangles=None):

@@ -1553,6 +1553,91 @@ MLSGPU_API int mlsgpu_hip_mesher_repair(mlsgpu_mesher *m, uint32_t flags, mlsgpu
     return MLSGPU_OK;
 }
 
+/* Every output chunk that has triangles through mlsgpu_hip_mesh_collapse_edges (collapse.hip), by the route of the repair
+ * above: a first round asks every chunk for its sizes, a second collapses it into new arrays, behind the chunk before.  Nothing
+ * of the sink changes before the last chunk is done: an error leaves the results as they were. */
+MLSGPU_API int mlsgpu_hip_mesher_collapse_edges(mlsgpu_mesher *m, uint32_t maxRounds, double maxLength, double minCos,
+                                                mlsgpu_collapse_stats *stats)
+{
+    REQUIRE(m != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
+    /* mlsgpu_hip_mesh_collapse_edges's own checks, here so that a refused parameter does no work */
+    REQUIRE(std::isfinite(maxLength) && maxLength >= 0.0 && minCos >= 0.0 && minCos <= 1.0, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
+    mlsgpu_ctx *const ctx = m->ctx;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    std::memset(stats, 0, sizeof(*stats));
+    stats->converged = maxRounds > 0 ? 1 : 0;       /* the AND over the chunks starts where a mesh without triangles ends */
+    stats->minLengthSqBefore = stats->minLengthSqAfter = INFINITY;
+    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
+    std::vector<mlsgpu_collapse_stats> one(nc);
+    std::vector<uint64_t> vStart(nc + 1, 0), tStart(nc + 1, 0);
+    for (size_t c = 0; c < nc; c++)
+    {
+        const auto [v0, t0, nv, nt] = m->span(c);
+        std::memset(&one[c], 0, sizeof(one[c]));
+        if (nt > 0)     /* a chunk without triangles has no output (finalize), and keeps none */
+        {
+            /* no room at all: the call stops at its capacity check, with the sizes (or keeps nothing, and is done) */
+            const int rc = mlsgpu_hip_mesh_collapse_edges(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, maxRounds, maxLength,
+                                                          minCos, nullptr, 0, nullptr, 0, nullptr, &one[c]);
+            if (rc != MLSGPU_ERR_LENGTH && rc != MLSGPU_OK)
+                return rc;
+        }
+        vStart[c + 1] = vStart[c] + one[c].outVertices;
+        tStart[c + 1] = tStart[c] + one[c].outTriangles;
+    }
+    DeviceArray<float> newVertices;
+    DeviceArray<uint32_t> newTriangles;
+    PROPAGATE(newVertices.alloc(std::max<uint64_t>(3 * vStart[nc], 1)));
+    PROPAGATE(newTriangles.alloc(std::max<uint64_t>(3 * tStart[nc], 1)));
+    bool first = true;
+    for (size_t c = 0; c < nc; c++)
+    {
+        const auto [v0, t0, nv, nt] = m->span(c);
+        if (nt == 0)
+            continue;
+        if (one[c].outTriangles > 0)
+            PROPAGATE(mlsgpu_hip_mesh_collapse_edges(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, maxRounds, maxLength, minCos,
+                                                     newVertices + 3 * vStart[c], one[c].outVertices, newTriangles + 3 * tStart[c],
+                                                     one[c].outTriangles, nullptr, &one[c]));
+        const mlsgpu_collapse_stats &s = one[c];
+        stats->numVertices += s.numVertices;
+        stats->numTriangles += s.numTriangles;
+        stats->outOfRangeTriangles += s.outOfRangeTriangles;
+        stats->degenerateTriangles += s.degenerateTriangles;
+        stats->numEdges += s.numEdges;
+        stats->interiorEdges += s.interiorEdges;
+        stats->fixedVertices += s.fixedVertices;
+        stats->rounds = std::max(stats->rounds, s.rounds);
+        stats->collapses += s.collapses;
+        stats->converged &= s.converged;
+        stats->shortBefore += s.shortBefore;
+        stats->shortAfter += s.shortAfter;
+        stats->blockedAfter += s.blockedAfter;
+        stats->unusedVertices += s.unusedVertices;
+        stats->outVertices += s.outVertices;
+        stats->outTriangles += s.outTriangles;
+        stats->minQualityBefore = first ? s.minQualityBefore : std::min(stats->minQualityBefore, s.minQualityBefore);
+        stats->minQualityAfter = first ? s.minQualityAfter : std::min(stats->minQualityAfter, s.minQualityAfter);
+        stats->minLengthSqBefore = std::min(stats->minLengthSqBefore, s.minLengthSqBefore);
+        stats->minLengthSqAfter = std::min(stats->minLengthSqAfter, s.minLengthSqAfter);
+        for (int k = 0; k < 16; k++)
+        {
+            stats->qualityBefore[k] += s.qualityBefore[k];
+            stats->qualityAfter[k] += s.qualityAfter[k];
+        }
+        first = false;
+    }
+    /* the new generation takes the old one's place (which goes with this call) */
+    m->outVertices = std::move(newVertices);
+    m->outTriangles = std::move(newTriangles);
+    m->chunkVStart = vStart;
+    m->chunkTStart = tStart;
+    m->dropNormals();           /* the chunks have changed and moved */
+    return MLSGPU_OK;
+}
+
 /* ---- the deviation report of the sink against a kept copy of itself (deviation.hip) ---- */
 
 MLSGPU_API int mlsgpu_hip_mesher_keep_reference(mlsgpu_mesher *m)

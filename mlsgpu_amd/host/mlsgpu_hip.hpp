@@ -279,6 +279,24 @@ inline mlsgpu_flip_stats flipEdges(const Context &ctx, const Buffer<float> &vert
     return st;
 }
 
+/// Short-edge collapse of a mesh in device memory, with its quality report (mlsgpu_hip_mesh_collapse_edges): interior edges of
+/// at most maxLength go, one vertex and two triangles apiece, and the topology stays.  outVertices / outTriangles have room
+/// for capVertices / capTriangles and do not overlap the inputs; outSource is NULL or gets the input index of every output
+/// vertex.  With too little room (NULL and 0 ask for the sizes) nothing is written, *st is complete and std::length_error is
+/// thrown.
+inline mlsgpu_collapse_stats collapseEdges(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
+                                           const Buffer<std::uint32_t> &triangles, std::uint64_t numTriangles,
+                                           std::uint32_t maxRounds, double maxLength, double minCos, float *outVertices,
+                                           std::uint64_t capVertices, std::uint32_t *outTriangles, std::uint64_t capTriangles,
+                                           std::uint32_t *outSource = NULL, mlsgpu_collapse_stats *st = NULL)
+{
+    mlsgpu_collapse_stats own;
+    mlsgpu_collapse_stats *const s = st != NULL ? st : &own;
+    check(mlsgpu_hip_mesh_collapse_edges(ctx.get(), vertices.get(), numVertices, triangles.get(), numTriangles, maxRounds, maxLength,
+                                         minCos, outVertices, capVertices, outTriangles, capTriangles, outSource, s));
+    return *s;
+}
+
 /// Area-weighted vertex normals of a mesh in device memory (mlsgpu_hip_mesh_normals): outNormals has room for 3 floats per
 /// vertex and does not overlap the inputs.
 inline mlsgpu_normals_stats normals(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
@@ -835,6 +853,16 @@ public:
     {
         mlsgpu_repair_stats st;
         check(mlsgpu_hip_mesher_repair(h, flags, &st));
+        return st;
+    }
+    /// Every output chunk of the finalized mesher with its interior edges of at most maxLength collapsed
+    /// (mlsgpu_hip_mesher_collapse_edges): behind simplify() and repair(), before flipEdges() and smooth().  The chunks move into
+    /// new arrays; seams keep their bits.  Counts and histograms summed over the chunks, rounds the largest, converged the AND,
+    /// the minima the minima.
+    mlsgpu_collapse_stats collapseEdges(std::uint32_t maxRounds, double maxLength, double minCos = 0.5)
+    {
+        mlsgpu_collapse_stats st;
+        check(mlsgpu_hip_mesher_collapse_edges(h, maxRounds, maxLength, minCos, &st));
         return st;
     }
     /// Every output chunk of the finalized mesher through at most maxRounds rounds of Delaunay edge flips, in place
