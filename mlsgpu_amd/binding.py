@@ -126,46 +126,50 @@ class Topology(C.Structure):
                 ("manifold", C.c_uint32)]
 
 
-class SimplifyStats(C.Structure):
+class Stats(C.Structure):
+    """The base of the statistics structures below."""
+
+    def as_dict(self):
+        """The fields in their order: a double as a float, an array as a list of floats or ints by its element type, everything
+        else as an int."""
+        out = {}
+        for name, kind in self._fields_:
+            value = getattr(self, name)
+            if issubclass(kind, C.Array):
+                out[name] = [(float if kind._type_ is C.c_double else int)(x) for x in value]
+            else:
+                out[name] = (float if kind is C.c_double else int)(value)
+        return out
+
+
+class SimplifyStats(Stats):
     """mlsgpu_simplify_stats: inTriangles = outTriangles + collapsedTriangles + duplicateTriangles."""
     _fields_ = [("inVertices", C.c_uint64), ("inTriangles", C.c_uint64), ("outVertices", C.c_uint64),
                 ("outTriangles", C.c_uint64), ("collapsedTriangles", C.c_uint64), ("duplicateTriangles", C.c_uint64)]
 
-    def as_dict(self):
-        return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
 
-
-class SimplifyQuadricStats(C.Structure):
+class SimplifyQuadricStats(Stats):
     """mlsgpu_simplify_quadric_stats: SimplifyStats' six, how the output vertices of several members were placed, and the
     exponent of the quadrics' scale."""
     _fields_ = SimplifyStats._fields_ + [("solvedVertices", C.c_uint64), ("flatVertices", C.c_uint64),
                                          ("escapedVertices", C.c_uint64), ("scaleExponent", C.c_int64)]
 
-    def as_dict(self):
-        return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
 
-
-class NormalsStats(C.Structure):
+class NormalsStats(Stats):
     """mlsgpu_normals_stats: what took no part, the vertices left without a normal, and the scale's exponent."""
     _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
                 ("nonFiniteTriangles", C.c_uint64), ("zeroNormals", C.c_uint64), ("scaleExponent", C.c_int64)]
 
-    def as_dict(self):
-        return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
 
-
-class SmoothStats(C.Structure):
+class SmoothStats(Stats):
     """mlsgpu_smooth_stats: what took no part, edges and boundary, the passes run, the scale's exponent, how far it moved."""
     _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
                 ("degenerateTriangles", C.c_uint64), ("numEdges", C.c_uint64), ("boundaryEdges", C.c_uint64),
                 ("boundaryVertices", C.c_uint64), ("isolatedVertices", C.c_uint64), ("passes", C.c_uint64),
                 ("scaleExponent", C.c_int64), ("maxMove", C.c_double), ("maxCoordinate", C.c_double)]
 
-    def as_dict(self):
-        return dict((name, (float if kind is C.c_double else int)(getattr(self, name))) for name, kind in self._fields_)
 
-
-class FlipStats(C.Structure):
+class FlipStats(Stats):
     """mlsgpu_flip_stats: what took no part, edges and interior regular edges, rounds, flips and whether the last round found no
     winner, the non-Delaunay edges before and after and those a guard refuses, the triangle quality before and after."""
     _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
@@ -174,13 +178,8 @@ class FlipStats(C.Structure):
                 ("nonDelaunayAfter", C.c_uint64), ("blockedAfter", C.c_uint64), ("minQualityBefore", C.c_double),
                 ("minQualityAfter", C.c_double), ("qualityBefore", C.c_uint64 * 16), ("qualityAfter", C.c_uint64 * 16)]
 
-    def as_dict(self):
-        """The fields; the two histograms as lists of 16 ints."""
-        return dict((name, [int(x) for x in getattr(self, name)] if name.startswith("quality")
-                     else (float if kind is C.c_double else int)(getattr(self, name))) for name, kind in self._fields_)
 
-
-class CollapseStats(C.Structure):
+class CollapseStats(Stats):
     """mlsgpu_collapse_stats: what took no part, edges, interior regular edges and fixed vertices, rounds, collapses and whether
     the last round found no winner, the short edges before and after and those a guard refuses, the sizes of the result, the
     triangle quality and the smallest squared edge length before and after."""
@@ -192,13 +191,8 @@ class CollapseStats(C.Structure):
                 ("minQualityBefore", C.c_double), ("minQualityAfter", C.c_double), ("minLengthSqBefore", C.c_double),
                 ("minLengthSqAfter", C.c_double), ("qualityBefore", C.c_uint64 * 16), ("qualityAfter", C.c_uint64 * 16)]
 
-    def as_dict(self):
-        """The fields; the two histograms as lists of 16 ints."""
-        return dict((name, [int(x) for x in getattr(self, name)] if name.startswith("quality")
-                     else (float if kind is C.c_double else int)(getattr(self, name))) for name, kind in self._fields_)
 
-
-class FillStats(C.Structure):
+class FillStats(Stats):
     """mlsgpu_fill_stats: what took no part, the boundary sides and their loops, what was filled, the sizes of the result."""
     _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
                 ("degenerateTriangles", C.c_uint64), ("boundaryEdges", C.c_uint64), ("irregularEdges", C.c_uint64),
@@ -206,11 +200,8 @@ class FillStats(C.Structure):
                 ("filledEdges", C.c_uint64), ("longestLoop", C.c_uint64), ("outVertices", C.c_uint64),
                 ("outTriangles", C.c_uint64), ("scaleExponent", C.c_int64)]
 
-    def as_dict(self):
-        return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
 
-
-class Deviation(C.Structure):
+class Deviation(Stats):
     """mlsgpu_deviation: the sizes, what took no part, the points within and beyond the search distance, the farthest point,
     the histogram of the distances in sixteenths of the search distance, their fixed-point sum of squares and their maximum."""
     _fields_ = [("numPoints", C.c_uint64), ("numVertices", C.c_uint64), ("numTriangles", C.c_uint64),
@@ -222,13 +213,12 @@ class Deviation(C.Structure):
     def as_dict(self):
         """The fields (the histogram as a list of 16 ints) and, derived from them on the host, meanSquare = sumQ *
         2^(scaleExponent - 30) / within (0.0 without a point within)."""
-        out = dict((name, [int(x) for x in getattr(self, name)] if name == "histogram"
-                    else (float if kind is C.c_double else int)(getattr(self, name))) for name, kind in self._fields_)
+        out = super().as_dict()
         out["meanSquare"] = math.ldexp(self.sumQ, int(self.scaleExponent) - 30) / self.within if self.within else 0.0
         return out
 
 
-class SelfIntersections(C.Structure):
+class SelfIntersections(Stats):
     """mlsgpu_self_intersections: the sizes, what took no part, the candidate pairs of the box test, the pairs that certainly
     cross and the triangles they touch, the lowest pair, the triangle with the most partners, and, for a sink, the chunks."""
     _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
@@ -236,34 +226,22 @@ class SelfIntersections(C.Structure):
                 ("crossingTriangles", C.c_uint64), ("lowestA", C.c_uint64), ("lowestB", C.c_uint64), ("maxPartners", C.c_uint64),
                 ("maxPartnersTriangle", C.c_uint64), ("lowestChunk", C.c_uint64), ("crossingChunks", C.c_uint64)]
 
-    def as_dict(self):
-        return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
 
-
-class CompactStats(C.Structure):
+class CompactStats(Stats):
     """mlsgpu_compact_stats: the sizes, the blob's bytes and those of its two sections, the groups and their exceptions, the
     groups per width, the quantisation step per axis."""
     _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("vertexBits", C.c_uint64), ("blobBytes", C.c_uint64),
                 ("vertexBytes", C.c_uint64), ("triangleBytes", C.c_uint64), ("groups", C.c_uint64), ("exceptions", C.c_uint64),
                 ("widthHistogram", C.c_uint64 * 33), ("step", C.c_double * 3)]
 
-    def as_dict(self):
-        out = dict((name, int(getattr(self, name))) for name, _ in self._fields_[:8])
-        out["widthHistogram"] = [int(x) for x in self.widthHistogram]
-        out["step"] = [float(x) for x in self.step]
-        return out
 
-
-class RepairStats(C.Structure):
+class RepairStats(Stats):
     """mlsgpu_repair_stats: what took no part, the repeated sides and the triangles dropped for them, the vertices that went,
     split and came, the sizes of the result."""
     _fields_ = [("numVertices", C.c_uint64), ("numTriangles", C.c_uint64), ("outOfRangeTriangles", C.c_uint64),
                 ("degenerateTriangles", C.c_uint64), ("repeatedSides", C.c_uint64), ("droppedTriangles", C.c_uint64),
                 ("unusedVertices", C.c_uint64), ("splitVertices", C.c_uint64), ("addedVertices", C.c_uint64),
                 ("outVertices", C.c_uint64), ("outTriangles", C.c_uint64)]
-
-    def as_dict(self):
-        return dict((name, int(getattr(self, name))) for name, _ in self._fields_)
 
 
 # MLSGPU_REPAIR_SPLIT_PINCHES: every umbrella of a vertex becomes a vertex of its own
@@ -522,7 +500,7 @@ def lib():
 
 
 _ERRORS = {1: InvalidArgument, 2: LengthError, 3: HipError, 4: HipError, 5: MlsError, 6: DensityError, 7: FormatError}
-_LENGTH = 2     # MLSGPU_ERR_LENGTH: also how mesh_fill_holes answers a question for its sizes
+_LENGTH = 2     # MLSGPU_ERR_LENGTH: also how a call without room answers a question for its sizes (_size_then_write)
 
 
 def check(rc):
@@ -1170,23 +1148,74 @@ class Mesher:
             pass
 
 
+class _Staging:
+    """The device buffers that one mesh_* call makes for itself, freed when the `with` block ends: the uploads of the arguments
+    that came as numpy arrays, and the outputs."""
+
+    def __init__(self, ctx):
+        self.ctx, self.own = ctx, []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for buf in self.own:
+            buf.free()
+
+    def upload(self, array):
+        """A buffer with the array's bytes, or None for an empty one."""
+        return self._keep(DeviceBuffer(self.ctx, array=array)) if array.size else None
+
+    def triples(self, a, dtype, count):
+        """(buffer or None, rows) of packed triples: a DeviceBuffer as it is, a numpy array uploaded; `count` overrides the rows."""
+        if isinstance(a, DeviceBuffer):
+            return a, (a.nbytes // 12 if count is None else count)
+        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
+        return self.upload(a), (len(a) if count is None else count)
+
+    def out(self, nbytes):
+        """A buffer of nbytes, or None for none."""
+        return self._keep(DeviceBuffer(self.ctx, nbytes=int(nbytes))) if nbytes else None
+
+    def _keep(self, buf):
+        self.own.append(buf)
+        return buf
+
+
+def _ptr(buf):
+    return buf.ptr if buf else None
+
+
+def _rows(buf, dtype, count):
+    """`count` packed triples downloaded from a buffer that may be None: [count, 3]."""
+    return buf.download(dtype, 3 * count).reshape(-1, 3) if buf and count else np.zeros((0, 3), dtype)
+
+
+def _size_then_write(S, entry, args, st, has_source, with_source=False):
+    """The protocol of the stages whose result has another size (fill, repair, collapse): one call without room asks for the
+    sizes, a second one writes.  `args` are the entry's arguments before its outputs; has_source says that it has an outSource
+    slot, with_source that the caller wants it filled.  MLSGPU_ERR_LENGTH with a result to make room for is the answer to the
+    question, and MLSGPU_OK that the result is empty and there is nothing to write.  Returns (vertices, triangles, statistics
+    as a dict), the arrays downloaded, and with with_source a fourth: the input index of every output vertex."""
+    rc = entry(*args, None, 0, None, 0, *((None,) if has_source else ()), C.byref(st))
+    if rc != 0 and not (rc == _LENGTH and st.outVertices + st.outTriangles > 0):
+        check(rc)
+    ov, ot = S.out(12 * st.outVertices), S.out(12 * st.outTriangles)
+    os_ = S.out(4 * st.outVertices) if with_source else None
+    if rc != 0:
+        check(entry(*args, _ptr(ov), st.outVertices, _ptr(ot), st.outTriangles, *((_ptr(os_),) if has_source else ()), C.byref(st)))
+    out = (_rows(ov, np.float32, st.outVertices), _rows(ot, np.uint32, st.outTriangles), st.as_dict())
+    return out + (os_.download(np.uint32, st.outVertices) if os_ else np.zeros(0, np.uint32),) if with_source else out
+
+
 def mesh_topology(ctx, triangles, num_vertices, num_triangles=None):
     """Manifold::isManifold (test/manifold.h:98-232) on the device, in its count-all form: a Topology.  `triangles` is a
     numpy array of index triples (uploaded for the call) or a DeviceBuffer of uint32 triples; num_triangles defaults to
     all of it."""
     t = Topology()
-    if isinstance(triangles, DeviceBuffer):
-        n = triangles.nbytes // 12 if num_triangles is None else num_triangles
-        check(lib().mlsgpu_hip_mesh_topology(ctx.h, triangles.ptr, n, num_vertices, C.byref(t)))
-        return t
-    tri = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
-    n = len(tri) if num_triangles is None else num_triangles
-    buf = DeviceBuffer(ctx, array=tri) if tri.size else None
-    try:
-        check(lib().mlsgpu_hip_mesh_topology(ctx.h, buf.ptr if buf else None, n, num_vertices, C.byref(t)))
-    finally:
-        if buf is not None:
-            buf.free()
+    with _Staging(ctx) as S:
+        dt, n = S.triples(triangles, np.uint32, num_triangles)
+        check(lib().mlsgpu_hip_mesh_topology(ctx.h, _ptr(dt), n, num_vertices, C.byref(t)))
     return t
 
 
@@ -1208,62 +1237,27 @@ def mesh_simplify_quadric(ctx, vertices, triangles, origin, cell_size, num_verti
 
 
 def _mesh_simplify(entry, st, ctx, vertices, triangles, origin, cell_size, num_vertices, num_triangles):
-    own = []
-
-    def on_device(a, dtype, count):
-        if isinstance(a, DeviceBuffer):
-            return a, (a.nbytes // 12 if count is None else count)
-        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
-        buf = DeviceBuffer(ctx, array=a) if a.size else None
-        if buf is not None:
-            own.append(buf)
-        return buf, (len(a) if count is None else count)
-
-    try:
-        dv, nv = on_device(vertices, np.float32, num_vertices)
-        dt, nt = on_device(triangles, np.uint32, num_triangles)
-        ov = DeviceBuffer(ctx, nbytes=12 * nv) if nv and dv is not None else None
-        ot = DeviceBuffer(ctx, nbytes=12 * nt) if nt and dt is not None else None
-        own.extend(x for x in (ov, ot) if x is not None)
-        check(entry(ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, (C.c_float * 3)(*[float(x) for x in origin]),
-                    float(cell_size), ov.ptr if ov else None, ot.ptr if ot else None, C.byref(st)))
-        out_v = ov.download(np.float32, 3 * st.outVertices).reshape(-1, 3) if st.outVertices else np.zeros((0, 3), np.float32)
-        out_t = ot.download(np.uint32, 3 * st.outTriangles).reshape(-1, 3) if st.outTriangles else np.zeros((0, 3), np.uint32)
-    finally:
-        for buf in own:
-            buf.free()
-    return out_v, out_t, st.as_dict()
+    with _Staging(ctx) as S:
+        dv, nv = S.triples(vertices, np.float32, num_vertices)
+        dt, nt = S.triples(triangles, np.uint32, num_triangles)
+        ov = S.out(12 * nv) if dv is not None else None
+        ot = S.out(12 * nt) if dt is not None else None
+        check(entry(ctx.h, _ptr(dv), nv, _ptr(dt), nt, (C.c_float * 3)(*[float(x) for x in origin]), float(cell_size), _ptr(ov),
+                    _ptr(ot), C.byref(st)))
+        return _rows(ov, np.float32, st.outVertices), _rows(ot, np.uint32, st.outTriangles), st.as_dict()
 
 
 def mesh_normals(ctx, vertices, triangles, num_vertices=None, num_triangles=None):
     """Area-weighted vertex normals on the device (mlsgpu_hip_mesh_normals), bit-reproducible whatever the schedule.
     `vertices` / `triangles` are numpy arrays (uploaded for the call) or DeviceBuffers of packed float32 xyz / uint32
     triples.  Returns (normals float32 [V, 3] downloaded, statistics as a dict)."""
-    own = []
-
-    def on_device(a, dtype, count):
-        if isinstance(a, DeviceBuffer):
-            return a, (a.nbytes // 12 if count is None else count)
-        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
-        buf = DeviceBuffer(ctx, array=a) if a.size else None
-        if buf is not None:
-            own.append(buf)
-        return buf, (len(a) if count is None else count)
-
     st = NormalsStats()
-    try:
-        dv, nv = on_device(vertices, np.float32, num_vertices)
-        dt, nt = on_device(triangles, np.uint32, num_triangles)
-        on = DeviceBuffer(ctx, nbytes=12 * nv) if nv and dv is not None else None
-        if on is not None:
-            own.append(on)
-        check(lib().mlsgpu_hip_mesh_normals(ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt,
-                                            on.ptr if on else None, C.byref(st)))
-        out = on.download(np.float32, 3 * nv).reshape(-1, 3) if on is not None else np.zeros((0, 3), np.float32)
-    finally:
-        for buf in own:
-            buf.free()
-    return out, st.as_dict()
+    with _Staging(ctx) as S:
+        dv, nv = S.triples(vertices, np.float32, num_vertices)
+        dt, nt = S.triples(triangles, np.uint32, num_triangles)
+        on = S.out(12 * nv) if dv is not None else None
+        check(lib().mlsgpu_hip_mesh_normals(ctx.h, _ptr(dv), nv, _ptr(dt), nt, _ptr(on), C.byref(st)))
+        return _rows(on, np.float32, nv), st.as_dict()
 
 
 def mesh_smooth(ctx, vertices, triangles, iterations, lam, mu, boundary=SMOOTH_BOUNDARY_FIXED, num_vertices=None, num_triangles=None,
@@ -1272,31 +1266,14 @@ def mesh_smooth(ctx, vertices, triangles, iterations, lam, mu, boundary=SMOOTH_B
     of the triangles or the numbering of the vertices.  `vertices` / `triangles` are numpy arrays (uploaded for the call) or
     DeviceBuffers of packed float32 xyz / uint32 triples; in_place writes the result over the vertices on the device.
     Returns (vertices float32 [V, 3] downloaded, statistics as a dict)."""
-    own = []
-
-    def on_device(a, dtype, count):
-        if isinstance(a, DeviceBuffer):
-            return a, (a.nbytes // 12 if count is None else count)
-        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
-        buf = DeviceBuffer(ctx, array=a) if a.size else None
-        if buf is not None:
-            own.append(buf)
-        return buf, (len(a) if count is None else count)
-
     st = SmoothStats()
-    try:
-        dv, nv = on_device(vertices, np.float32, num_vertices)
-        dt, nt = on_device(triangles, np.uint32, num_triangles)
-        ov = dv if in_place else DeviceBuffer(ctx, nbytes=12 * nv) if nv and dv is not None else None
-        if ov is not None and not in_place:
-            own.append(ov)
-        check(lib().mlsgpu_hip_mesh_smooth(ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, int(iterations), float(lam),
-                                           float(mu), int(boundary), ov.ptr if ov else None, C.byref(st)))
-        out = ov.download(np.float32, 3 * nv).reshape(-1, 3) if ov is not None else np.zeros((0, 3), np.float32)
-    finally:
-        for buf in own:
-            buf.free()
-    return out, st.as_dict()
+    with _Staging(ctx) as S:
+        dv, nv = S.triples(vertices, np.float32, num_vertices)
+        dt, nt = S.triples(triangles, np.uint32, num_triangles)
+        ov = dv if in_place else S.out(12 * nv) if dv is not None else None
+        check(lib().mlsgpu_hip_mesh_smooth(ctx.h, _ptr(dv), nv, _ptr(dt), nt, int(iterations), float(lam), float(mu), int(boundary),
+                                           _ptr(ov), C.byref(st)))
+        return _rows(ov, np.float32, nv), st.as_dict()
 
 
 def mesh_flip_edges(ctx, vertices, triangles, max_rounds, min_gain=1e-6, min_cos=0.5, num_vertices=None, num_triangles=None,
@@ -1305,31 +1282,14 @@ def mesh_flip_edges(ctx, vertices, triangles, max_rounds, min_gain=1e-6, min_cos
     bit-reproducible whatever the schedule or the order of the triangles.  `vertices` / `triangles` are numpy arrays (uploaded
     for the call) or DeviceBuffers of packed float32 xyz / uint32 triples; in_place writes the result over the triangles on the
     device.  Returns (triangles uint32 [T, 3] downloaded, statistics as a dict)."""
-    own = []
-
-    def on_device(a, dtype, count):
-        if isinstance(a, DeviceBuffer):
-            return a, (a.nbytes // 12 if count is None else count)
-        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
-        buf = DeviceBuffer(ctx, array=a) if a.size else None
-        if buf is not None:
-            own.append(buf)
-        return buf, (len(a) if count is None else count)
-
     st = FlipStats()
-    try:
-        dv, nv = on_device(vertices, np.float32, num_vertices)
-        dt, nt = on_device(triangles, np.uint32, num_triangles)
-        ot = dt if in_place else DeviceBuffer(ctx, nbytes=12 * nt) if nt and dt is not None else None
-        if ot is not None and not in_place:
-            own.append(ot)
-        check(lib().mlsgpu_hip_mesh_flip_edges(ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, int(max_rounds),
-                                               float(min_gain), float(min_cos), ot.ptr if ot else None, C.byref(st)))
-        out = ot.download(np.uint32, 3 * nt).reshape(-1, 3) if ot is not None else np.zeros((0, 3), np.uint32)
-    finally:
-        for buf in own:
-            buf.free()
-    return out, st.as_dict()
+    with _Staging(ctx) as S:
+        dv, nv = S.triples(vertices, np.float32, num_vertices)
+        dt, nt = S.triples(triangles, np.uint32, num_triangles)
+        ot = dt if in_place else S.out(12 * nt) if dt is not None else None
+        check(lib().mlsgpu_hip_mesh_flip_edges(ctx.h, _ptr(dv), nv, _ptr(dt), nt, int(max_rounds), float(min_gain), float(min_cos),
+                                               _ptr(ot), C.byref(st)))
+        return _rows(ot, np.uint32, nt), st.as_dict()
 
 
 def mesh_collapse_edges(ctx, vertices, triangles, max_rounds, max_length, min_cos=0.5, num_vertices=None, num_triangles=None,
@@ -1340,39 +1300,11 @@ def mesh_collapse_edges(ctx, vertices, triangles, max_rounds, max_length, min_co
     for the call) or DeviceBuffers of packed float32 xyz / uint32 triples, which are left alone.  One call asks for the sizes,
     a second one writes.  Returns (vertices float32 [V', 3], triangles uint32 [T', 3], statistics as a dict), the arrays
     downloaded, and with with_source a fourth: the input index of every output vertex, uint32 [V']."""
-    own = []
-
-    def on_device(a, dtype, count):
-        if isinstance(a, DeviceBuffer):
-            return a, (a.nbytes // 12 if count is None else count)
-        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
-        buf = DeviceBuffer(ctx, array=a) if a.size else None
-        if buf is not None:
-            own.append(buf)
-        return buf, (len(a) if count is None else count)
-
-    st = CollapseStats()
-    try:
-        dv, nv = on_device(vertices, np.float32, num_vertices)
-        dt, nt = on_device(triangles, np.uint32, num_triangles)
-        args = (ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, int(max_rounds), float(max_length), float(min_cos))
-        rc = lib().mlsgpu_hip_mesh_collapse_edges(*args, None, 0, None, 0, None, C.byref(st))
-        if rc != 0 and not (rc == _LENGTH and st.outVertices + st.outTriangles > 0):
-            check(rc)
-        ov = DeviceBuffer(ctx, nbytes=12 * st.outVertices) if st.outVertices else None
-        ot = DeviceBuffer(ctx, nbytes=12 * st.outTriangles) if st.outTriangles else None
-        os_ = DeviceBuffer(ctx, nbytes=4 * st.outVertices) if st.outVertices and with_source else None
-        own.extend(x for x in (ov, ot, os_) if x is not None)
-        if rc != 0:
-            check(lib().mlsgpu_hip_mesh_collapse_edges(*args, ov.ptr if ov else None, st.outVertices, ot.ptr if ot else None,
-                                                       st.outTriangles, os_.ptr if os_ else None, C.byref(st)))
-        out_v = ov.download(np.float32, 3 * st.outVertices).reshape(-1, 3) if ov else np.zeros((0, 3), np.float32)
-        out_t = ot.download(np.uint32, 3 * st.outTriangles).reshape(-1, 3) if ot else np.zeros((0, 3), np.uint32)
-        out_s = os_.download(np.uint32, st.outVertices) if os_ else np.zeros(0, np.uint32)
-    finally:
-        for buf in own:
-            buf.free()
-    return (out_v, out_t, st.as_dict(), out_s) if with_source else (out_v, out_t, st.as_dict())
+    with _Staging(ctx) as S:
+        dv, nv = S.triples(vertices, np.float32, num_vertices)
+        dt, nt = S.triples(triangles, np.uint32, num_triangles)
+        args = (ctx.h, _ptr(dv), nv, _ptr(dt), nt, int(max_rounds), float(max_length), float(min_cos))
+        return _size_then_write(S, lib().mlsgpu_hip_mesh_collapse_edges, args, CollapseStats(), True, with_source)
 
 
 def mesh_fill_holes(ctx, vertices, triangles, max_edges, pinned=None, num_vertices=None, num_triangles=None):
@@ -1382,45 +1314,17 @@ def mesh_fill_holes(ctx, vertices, triangles, max_edges, pinned=None, num_vertic
     float32 xyz / uint32 triples, `pinned` is None, a numpy array of one flag per vertex or a DeviceBuffer of one byte per
     vertex.  One call asks for the sizes, a second one fills.  Returns (vertices float32 [V', 3], triangles uint32 [T', 3],
     statistics as a dict), the arrays downloaded: the input's rows first, then the new ones."""
-    own = []
-
-    def on_device(a, dtype, count):
-        if isinstance(a, DeviceBuffer):
-            return a, (a.nbytes // 12 if count is None else count)
-        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
-        buf = DeviceBuffer(ctx, array=a) if a.size else None
-        if buf is not None:
-            own.append(buf)
-        return buf, (len(a) if count is None else count)
-
-    st = FillStats()
-    try:
-        dv, nv = on_device(vertices, np.float32, num_vertices)
-        dt, nt = on_device(triangles, np.uint32, num_triangles)
+    with _Staging(ctx) as S:
+        dv, nv = S.triples(vertices, np.float32, num_vertices)
+        dt, nt = S.triples(triangles, np.uint32, num_triangles)
         dp = pinned
         if pinned is not None and not isinstance(pinned, DeviceBuffer):
             mask = np.ascontiguousarray(np.asarray(pinned) != 0, np.uint8).reshape(-1)
             if len(mask) != nv:
                 raise InvalidArgument("pinned has %d entries for %d vertices" % (len(mask), nv))
-            dp = DeviceBuffer(ctx, array=mask) if mask.size else None
-            if dp is not None:
-                own.append(dp)
-        args = (ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, int(max_edges), dp.ptr if dp else None)
-        rc = lib().mlsgpu_hip_mesh_fill_holes(*args, None, 0, None, 0, C.byref(st))
-        if rc != 0 and not (rc == _LENGTH and st.outVertices + st.outTriangles > 0):
-            check(rc)
-        ov = DeviceBuffer(ctx, nbytes=12 * st.outVertices) if st.outVertices else None
-        ot = DeviceBuffer(ctx, nbytes=12 * st.outTriangles) if st.outTriangles else None
-        own.extend(x for x in (ov, ot) if x is not None)
-        if rc != 0:
-            check(lib().mlsgpu_hip_mesh_fill_holes(*args, ov.ptr if ov else None, st.outVertices, ot.ptr if ot else None,
-                                                   st.outTriangles, C.byref(st)))
-        out_v = ov.download(np.float32, 3 * st.outVertices).reshape(-1, 3) if ov else np.zeros((0, 3), np.float32)
-        out_t = ot.download(np.uint32, 3 * st.outTriangles).reshape(-1, 3) if ot else np.zeros((0, 3), np.uint32)
-    finally:
-        for buf in own:
-            buf.free()
-    return out_v, out_t, st.as_dict()
+            dp = S.upload(mask)
+        args = (ctx.h, _ptr(dv), nv, _ptr(dt), nt, int(max_edges), _ptr(dp))
+        return _size_then_write(S, lib().mlsgpu_hip_mesh_fill_holes, args, FillStats(), False)
 
 
 def mesh_repair(ctx, vertices, triangles, flags=0, num_vertices=None, num_triangles=None, with_source=False):
@@ -1430,39 +1334,11 @@ def mesh_repair(ctx, vertices, triangles, flags=0, num_vertices=None, num_triang
     or DeviceBuffers of packed float32 xyz / uint32 triples.  One call asks for the sizes, a second one writes.  Returns
     (vertices float32 [V', 3], triangles uint32 [T', 3], statistics as a dict), the arrays downloaded, and with with_source a
     fourth: the input index of every output vertex, uint32 [V']."""
-    own = []
-
-    def on_device(a, dtype, count):
-        if isinstance(a, DeviceBuffer):
-            return a, (a.nbytes // 12 if count is None else count)
-        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
-        buf = DeviceBuffer(ctx, array=a) if a.size else None
-        if buf is not None:
-            own.append(buf)
-        return buf, (len(a) if count is None else count)
-
-    st = RepairStats()
-    try:
-        dv, nv = on_device(vertices, np.float32, num_vertices)
-        dt, nt = on_device(triangles, np.uint32, num_triangles)
-        args = (ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, int(flags))
-        rc = lib().mlsgpu_hip_mesh_repair(*args, None, 0, None, 0, None, C.byref(st))
-        if rc != 0 and not (rc == _LENGTH and st.outVertices + st.outTriangles > 0):
-            check(rc)
-        ov = DeviceBuffer(ctx, nbytes=12 * st.outVertices) if st.outVertices else None
-        ot = DeviceBuffer(ctx, nbytes=12 * st.outTriangles) if st.outTriangles else None
-        os_ = DeviceBuffer(ctx, nbytes=4 * st.outVertices) if st.outVertices and with_source else None
-        own.extend(x for x in (ov, ot, os_) if x is not None)
-        if rc != 0:
-            check(lib().mlsgpu_hip_mesh_repair(*args, ov.ptr if ov else None, st.outVertices, ot.ptr if ot else None,
-                                               st.outTriangles, os_.ptr if os_ else None, C.byref(st)))
-        out_v = ov.download(np.float32, 3 * st.outVertices).reshape(-1, 3) if ov else np.zeros((0, 3), np.float32)
-        out_t = ot.download(np.uint32, 3 * st.outTriangles).reshape(-1, 3) if ot else np.zeros((0, 3), np.uint32)
-        out_s = os_.download(np.uint32, st.outVertices) if os_ else np.zeros(0, np.uint32)
-    finally:
-        for buf in own:
-            buf.free()
-    return (out_v, out_t, st.as_dict(), out_s) if with_source else (out_v, out_t, st.as_dict())
+    with _Staging(ctx) as S:
+        dv, nv = S.triples(vertices, np.float32, num_vertices)
+        dt, nt = S.triples(triangles, np.uint32, num_triangles)
+        args = (ctx.h, _ptr(dv), nv, _ptr(dt), nt, int(flags))
+        return _size_then_write(S, lib().mlsgpu_hip_mesh_repair, args, RepairStats(), True, with_source)
 
 
 def mesh_deviation(ctx, points, vertices, triangles, max_distance, want_distances=True, want_nearest=True, num_points=None,
@@ -1472,32 +1348,17 @@ def mesh_deviation(ctx, points, vertices, triangles, max_distance, want_distance
     `triangles` are numpy arrays (uploaded for the call) or DeviceBuffers of packed float32 xyz / uint32 triples.  Returns
     (squared distances float64 [P] or None, nearest triangles uint32 [P] or None, the report as a dict): a point beyond
     max_distance has +inf and 0xFFFFFFFF."""
-    own = []
-
-    def on_device(a, dtype, count):
-        if isinstance(a, DeviceBuffer):
-            return a, (a.nbytes // 12 if count is None else count)
-        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
-        buf = DeviceBuffer(ctx, array=a) if a.size else None
-        if buf is not None:
-            own.append(buf)
-        return buf, (len(a) if count is None else count)
-
     st = Deviation()
-    try:
-        dp, n = on_device(points, np.float32, num_points)
-        dv, nv = on_device(vertices, np.float32, num_vertices)
-        dt, nt = on_device(triangles, np.uint32, num_triangles)
-        od = DeviceBuffer(ctx, nbytes=8 * n) if want_distances and n else None
-        on = DeviceBuffer(ctx, nbytes=4 * n) if want_nearest and n else None
-        own.extend(x for x in (od, on) if x is not None)
-        check(lib().mlsgpu_hip_mesh_deviation(ctx.h, dp.ptr if dp else None, n, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt,
-                                              float(max_distance), od.ptr if od else None, on.ptr if on else None, C.byref(st)))
+    with _Staging(ctx) as S:
+        dp, n = S.triples(points, np.float32, num_points)
+        dv, nv = S.triples(vertices, np.float32, num_vertices)
+        dt, nt = S.triples(triangles, np.uint32, num_triangles)
+        od = S.out(8 * n) if want_distances else None
+        on = S.out(4 * n) if want_nearest else None
+        check(lib().mlsgpu_hip_mesh_deviation(ctx.h, _ptr(dp), n, _ptr(dv), nv, _ptr(dt), nt, float(max_distance), _ptr(od), _ptr(on),
+                                              C.byref(st)))
         distance2 = (od.download(np.float64, n) if od else np.zeros(0, np.float64)) if want_distances else None
         nearest = (on.download(np.uint32, n) if on else np.zeros(0, np.uint32)) if want_nearest else None
-    finally:
-        for buf in own:
-            buf.free()
     return distance2, nearest, st.as_dict()
 
 
@@ -1512,37 +1373,20 @@ def mesh_self_intersections(ctx, vertices, triangles, want_partners=True, want_p
     answer whatever the schedule.  `vertices` / `triangles` are numpy arrays (uploaded for the call) or DeviceBuffers of packed
     float32 xyz / uint32 triples.  With want_pairs and a crossing, one call asks for the number of pairs and a second one
     writes them.  Returns (partners uint32 [T] or None, pairs uint32 [N, 2] sorted or None, the report as a dict)."""
-    own = []
-
-    def on_device(a, dtype, count):
-        if isinstance(a, DeviceBuffer):
-            return a, (a.nbytes // 12 if count is None else count)
-        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
-        buf = DeviceBuffer(ctx, array=a) if a.size else None
-        if buf is not None:
-            own.append(buf)
-        return buf, (len(a) if count is None else count)
-
     st = SelfIntersections()
-    try:
-        dv, nv = on_device(vertices, np.float32, num_vertices)
-        dt, nt = on_device(triangles, np.uint32, num_triangles)
-        op = DeviceBuffer(ctx, nbytes=4 * nt) if want_partners and nt else None
-        if op is not None:
-            own.append(op)
-        args = (ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, op.ptr if op else None)
+    with _Staging(ctx) as S:
+        dv, nv = S.triples(vertices, np.float32, num_vertices)
+        dt, nt = S.triples(triangles, np.uint32, num_triangles)
+        op = S.out(4 * nt) if want_partners else None
+        args = (ctx.h, _ptr(dv), nv, _ptr(dt), nt, _ptr(op))
         check(lib().mlsgpu_hip_mesh_self_intersections(*args, None, 0, C.byref(st)))
         pairs = np.zeros((0, 2), np.uint32) if want_pairs else None
         if want_pairs and st.crossingPairs:
             n = int(st.crossingPairs)
-            ol = DeviceBuffer(ctx, nbytes=8 * n)
-            own.append(ol)
+            ol = S.out(8 * n)
             check(lib().mlsgpu_hip_mesh_self_intersections(*args, ol.ptr, n, C.byref(st)))
             pairs = ol.download(np.uint32, 2 * n).reshape(-1, 2)
         partners = (op.download(np.uint32, nt) if op else np.zeros(0, np.uint32)) if want_partners else None
-    finally:
-        for buf in own:
-            buf.free()
     return partners, pairs, st.as_dict()
 
 
@@ -1556,33 +1400,17 @@ def mesh_compact(ctx, vertices, triangles, vertex_bits=32, num_vertices=None, nu
     vertex_bits = 32 and quantised to 8..24 bits otherwise.  `vertices` / `triangles` are numpy arrays (uploaded for the call) or
     DeviceBuffers of packed float32 xyz / uint32 triples.  One call asks for the size, a second one writes.  Returns (the blob as
     a uint32 array, the statistics as a dict)."""
-    own = []
-
-    def on_device(a, dtype, count):
-        if isinstance(a, DeviceBuffer):
-            return a, (a.nbytes // 12 if count is None else count)
-        a = np.ascontiguousarray(a, dtype).reshape(-1, 3)
-        buf = DeviceBuffer(ctx, array=a) if a.size else None
-        if buf is not None:
-            own.append(buf)
-        return buf, (len(a) if count is None else count)
-
     st = CompactStats()
-    try:
-        dv, nv = on_device(vertices, np.float32, num_vertices)
-        dt, nt = on_device(triangles, np.uint32, num_triangles)
-        args = (ctx.h, dv.ptr if dv else None, nv, dt.ptr if dt else None, nt, vertex_bits)
+    with _Staging(ctx) as S:
+        dv, nv = S.triples(vertices, np.float32, num_vertices)
+        dt, nt = S.triples(triangles, np.uint32, num_triangles)
+        args = (ctx.h, _ptr(dv), nv, _ptr(dt), nt, vertex_bits)
         rc = lib().mlsgpu_hip_mesh_compact(*args, None, 0, C.byref(st))
-        if rc != 2:                 # the size query ends in MLSGPU_ERR_LENGTH
+        if rc != _LENGTH:           # the size query ends in MLSGPU_ERR_LENGTH
             check(rc)
-        out = DeviceBuffer(ctx, nbytes=int(st.blobBytes))
-        own.append(out)
+        out = S.out(st.blobBytes)   # never empty: a blob has a header
         check(lib().mlsgpu_hip_mesh_compact(*args, out.ptr, out.nbytes, C.byref(st)))
-        blob = out.download(np.uint32, int(st.blobBytes) // 4)
-    finally:
-        for buf in own:
-            buf.free()
-    return blob, st.as_dict()
+        return out.download(np.uint32, int(st.blobBytes) // 4), st.as_dict()
 
 
 def compact_info(blob):

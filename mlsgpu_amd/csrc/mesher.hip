@@ -1204,20 +1204,176 @@ MLSGPU_API int mlsgpu_hip_mesher_chunk_topology(mlsgpu_mesher *m, uint32_t i, ml
     return mlsgpu_hip_mesh_topology(m->ctx, m->outTriangles + 3 * s.t0, s.nt, s.nv, out);
 }
 
-/* Every output chunk through mlsgpu_hip_mesh_simplify or, where `quadric` is given, mlsgpu_hip_mesh_simplify_quadric
- * (simplify.hip), into buffers of the chunk's size and from there to the front of the output arrays: a result is never larger
- * than its chunk, so chunk c's lands at or before where chunk c began and never on a chunk that is still to be read.  The
- * caller holds the lock of a finalized sink.  *stats and the last four fields of *quadric: the chunks added up, scaleExponent
- * the largest among the chunks that have one. */
-static int simplifyChunks(mlsgpu_mesher *m, const float origin[3], float cellSize, mlsgpu_simplify_stats *stats,
-                          mlsgpu_simplify_quadric_stats *quadric)
+/* ---- the stages that work on the finished chunks: their statistics' folds, then the three routes a stage takes ---- */
+
+using Span = mlsgpu_mesher::Span;
+
+/* accumulate(total, one, first): the statistics of one chunk join the sink's; `first` says that no chunk was folded before.
+ * The counts add up.  What does not start at zero (converged, the smallest lengths, smooth's passes) is preset by the entry
+ * point, where it can be seen. */
+
+/* the largest exponent among the chunks that have one: `first` among those */
+static void foldExponent(int64_t &total, int64_t one, bool first) { total = first ? one : std::max(total, one); }
+
+/* the six counts that mlsgpu_simplify_stats and mlsgpu_simplify_quadric_stats share */
+template<typename Stats>
+static void addSimplifyCounts(Stats &total, const Stats &one)
+{
+    total.inVertices += one.inVertices;
+    total.inTriangles += one.inTriangles;
+    total.outVertices += one.outVertices;
+    total.outTriangles += one.outTriangles;
+    total.collapsedTriangles += one.collapsedTriangles;
+    total.duplicateTriangles += one.duplicateTriangles;
+}
+
+static void accumulate(mlsgpu_simplify_stats &total, const mlsgpu_simplify_stats &one, bool) { addSimplifyCounts(total, one); }
+
+static void accumulate(mlsgpu_simplify_quadric_stats &total, const mlsgpu_simplify_quadric_stats &one, bool)
+{
+    /* a chunk has a scale where M != 0: where it solved or escaped */
+    const bool scaledBefore = total.solvedVertices + total.escapedVertices > 0;
+    addSimplifyCounts(total, one);
+    total.solvedVertices += one.solvedVertices;
+    total.flatVertices += one.flatVertices;
+    total.escapedVertices += one.escapedVertices;
+    if (one.solvedVertices + one.escapedVertices > 0)
+        foldExponent(total.scaleExponent, one.scaleExponent, !scaledBefore);
+}
+
+static void accumulate(mlsgpu_smooth_stats &total, const mlsgpu_smooth_stats &one, bool first)
+{
+    total.numVertices += one.numVertices;
+    total.numTriangles += one.numTriangles;
+    total.outOfRangeTriangles += one.outOfRangeTriangles;
+    total.degenerateTriangles += one.degenerateTriangles;
+    total.numEdges += one.numEdges;
+    total.boundaryEdges += one.boundaryEdges;
+    total.boundaryVertices += one.boundaryVertices;
+    total.isolatedVertices += one.isolatedVertices;
+    total.passes = one.passes;          /* the last chunk's: the same for all of them */
+    foldExponent(total.scaleExponent, one.scaleExponent, first);
+    total.maxMove = std::max(total.maxMove, one.maxMove);
+    total.maxCoordinate = std::max(total.maxCoordinate, one.maxCoordinate);
+}
+
+/* what mlsgpu_flip_stats and mlsgpu_collapse_stats share: the input's counts, the rounds (the most of any chunk, converged if
+ * all did) and the quality report, whose minima have no neutral start value */
+template<typename Stats>
+static void addEdgeRounds(Stats &total, const Stats &one, bool first)
+{
+    total.numVertices += one.numVertices;
+    total.numTriangles += one.numTriangles;
+    total.outOfRangeTriangles += one.outOfRangeTriangles;
+    total.degenerateTriangles += one.degenerateTriangles;
+    total.numEdges += one.numEdges;
+    total.interiorEdges += one.interiorEdges;
+    total.rounds = std::max(total.rounds, one.rounds);
+    total.converged &= one.converged;
+    total.blockedAfter += one.blockedAfter;
+    total.minQualityBefore = first ? one.minQualityBefore : std::min(total.minQualityBefore, one.minQualityBefore);
+    total.minQualityAfter = first ? one.minQualityAfter : std::min(total.minQualityAfter, one.minQualityAfter);
+    for (int k = 0; k < 16; k++)
+    {
+        total.qualityBefore[k] += one.qualityBefore[k];
+        total.qualityAfter[k] += one.qualityAfter[k];
+    }
+}
+
+static void accumulate(mlsgpu_flip_stats &total, const mlsgpu_flip_stats &one, bool first)
+{
+    addEdgeRounds(total, one, first);
+    total.flips += one.flips;
+    total.nonDelaunayBefore += one.nonDelaunayBefore;
+    total.nonDelaunayAfter += one.nonDelaunayAfter;
+}
+
+static void accumulate(mlsgpu_collapse_stats &total, const mlsgpu_collapse_stats &one, bool first)
+{
+    addEdgeRounds(total, one, first);
+    total.fixedVertices += one.fixedVertices;
+    total.collapses += one.collapses;
+    total.shortBefore += one.shortBefore;
+    total.shortAfter += one.shortAfter;
+    total.unusedVertices += one.unusedVertices;
+    total.outVertices += one.outVertices;
+    total.outTriangles += one.outTriangles;
+    total.minLengthSqBefore = std::min(total.minLengthSqBefore, one.minLengthSqBefore);
+    total.minLengthSqAfter = std::min(total.minLengthSqAfter, one.minLengthSqAfter);
+}
+
+static void accumulate(mlsgpu_fill_stats &total, const mlsgpu_fill_stats &one, bool first)
+{
+    total.numVertices += one.numVertices;
+    total.numTriangles += one.numTriangles;
+    total.outOfRangeTriangles += one.outOfRangeTriangles;
+    total.degenerateTriangles += one.degenerateTriangles;
+    total.boundaryEdges += one.boundaryEdges;
+    total.irregularEdges += one.irregularEdges;
+    total.loops += one.loops;
+    total.filledLoops += one.filledLoops;
+    total.longLoops += one.longLoops;
+    total.pinnedLoops += one.pinnedLoops;
+    total.filledEdges += one.filledEdges;
+    total.longestLoop = std::max(total.longestLoop, one.longestLoop);
+    total.outVertices += one.outVertices;
+    total.outTriangles += one.outTriangles;
+    foldExponent(total.scaleExponent, one.scaleExponent, first);
+}
+
+static void accumulate(mlsgpu_repair_stats &total, const mlsgpu_repair_stats &one, bool)
+{
+    total.numVertices += one.numVertices;
+    total.numTriangles += one.numTriangles;
+    total.outOfRangeTriangles += one.outOfRangeTriangles;
+    total.degenerateTriangles += one.degenerateTriangles;
+    total.repeatedSides += one.repeatedSides;
+    total.droppedTriangles += one.droppedTriangles;
+    total.unusedVertices += one.unusedVertices;
+    total.splitVertices += one.splitVertices;
+    total.addedVertices += one.addedVertices;
+    total.outVertices += one.outVertices;
+    total.outTriangles += one.outTriangles;
+}
+
+/* *total += the report of dense chunk c: the counts add, the maximum and the lowest (chunk, point) that attains it are kept.
+ * The chunks come in ascending order, so a later chunk takes the maximum over only by exceeding it. */
+static void addDeviation(mlsgpu_deviation *total, const mlsgpu_deviation &one, uint64_t c)
+{
+    total->numPoints += one.numPoints;
+    total->numVertices += one.numVertices;
+    total->numTriangles += one.numTriangles;
+    total->outOfRangeTriangles += one.outOfRangeTriangles;
+    total->degenerateTriangles += one.degenerateTriangles;
+    total->beyond += one.beyond;
+    for (int k = 0; k < 16; k++)
+        total->histogram[k] += one.histogram[k];
+    total->sumQ += one.sumQ;
+    if (one.numPoints > 0)
+        total->scaleExponent = one.scaleExponent;       /* D is the same for every chunk, hence e */
+    if (one.within > 0 && (total->within == 0 || one.maxDistance2 > total->maxDistance2))
+    {
+        total->maxDistance2 = one.maxDistance2;
+        total->farthestChunk = c;
+        total->farthestPoint = one.farthestPoint;
+    }
+    total->within += one.within;
+}
+
+/* The three routes.  Each is for the holder of the lock of a finalized sink, after the entry point has checked the stage's
+ * parameters (a refused parameter costs no results) and preset *total; each hands every dense chunk that has triangles to
+ * `stage`, which calls the mesh function on the chunk where it lies, and folds what it reports into *total.  A chunk without
+ * triangles has no output (finalize), is skipped and keeps nothing. */
+
+/* To the front (simplify): stage(chunk, outVertices, outTriangles, &one) writes into buffers of the largest chunk's size, and from
+ * there the result goes to the front of the output arrays: it is never larger than its chunk, so chunk c's lands at or before
+ * where chunk c began and never on a chunk that is still to be read.  A failure after the first chunk costs the results. */
+template<typename Stats, typename Stage>
+static int simplifyChunks(mlsgpu_mesher *m, Stats *total, Stage stage)
 {
     mlsgpu_ctx *const ctx = m->ctx;
     HIP_CHECK(hipSetDevice(ctx->device));
     m->dropNormals();           /* the chunks change and move */
-    std::memset(stats, 0, sizeof(*stats));
-    if (quadric != nullptr)
-        std::memset(quadric, 0, sizeof(*quadric));
     const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
     uint64_t maxV = 0, maxT = 0;
     for (size_t c = 0; c < nc; c++)
@@ -1230,24 +1386,12 @@ static int simplifyChunks(mlsgpu_mesher *m, const float origin[3], float cellSiz
     PROPAGATE(tmpV.alloc(3 * maxV));
     PROPAGATE(tmpT.alloc(3 * maxT));
     uint64_t vAt = 0, tAt = 0;
-    bool scaled = false;        /* a chunk before this one had a scale */
     for (size_t c = 0; c < nc; c++)
     {
-        const auto [v0, t0, nv, nt] = m->span(c);
-        mlsgpu_simplify_stats one;
-        mlsgpu_simplify_quadric_stats oneQuadric;
+        const Span s = m->span(c);
+        Stats one;
         std::memset(&one, 0, sizeof(one));
-        std::memset(&oneQuadric, 0, sizeof(oneQuadric));
-        int rc = MLSGPU_OK;
-        if (nt > 0 && quadric == nullptr)       /* a chunk without triangles has no output (finalize), and keeps none */
-            rc = mlsgpu_hip_mesh_simplify(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, origin, cellSize, tmpV, tmpT, &one);
-        else if (nt > 0)
-        {
-            rc = mlsgpu_hip_mesh_simplify_quadric(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, origin, cellSize, tmpV,
-                                                  tmpT, &oneQuadric);
-            one = mlsgpu_simplify_stats{oneQuadric.inVertices, oneQuadric.inTriangles, oneQuadric.outVertices, oneQuadric.outTriangles,
-                                        oneQuadric.collapsedTriangles, oneQuadric.duplicateTriangles};
-        }
+        int rc = s.nt > 0 ? stage(s, tmpV.get(), tmpT.get(), &one) : MLSGPU_OK;
         if (rc == MLSGPU_OK && one.outVertices > 0
             && hipMemcpyAsync(m->outVertices + 3 * vAt, tmpV, one.outVertices * 12, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
             rc = setError(MLSGPU_ERR_HIP, "mesher simplify: the copy of a chunk's vertices failed");
@@ -1264,27 +1408,85 @@ static int simplifyChunks(mlsgpu_mesher *m, const float origin[3], float cellSiz
         m->chunkTStart[c] = tAt;
         vAt += one.outVertices;
         tAt += one.outTriangles;
-        stats->inVertices += one.inVertices;
-        stats->inTriangles += one.inTriangles;
-        stats->outVertices += one.outVertices;
-        stats->outTriangles += one.outTriangles;
-        stats->collapsedTriangles += one.collapsedTriangles;
-        stats->duplicateTriangles += one.duplicateTriangles;
-        if (quadric != nullptr)
-        {
-            quadric->solvedVertices += oneQuadric.solvedVertices;
-            quadric->flatVertices += oneQuadric.flatVertices;
-            quadric->escapedVertices += oneQuadric.escapedVertices;
-            if (oneQuadric.solvedVertices + oneQuadric.escapedVertices > 0)     /* this chunk has a scale: M != 0 */
-            {
-                quadric->scaleExponent = scaled ? std::max(quadric->scaleExponent, oneQuadric.scaleExponent) : oneQuadric.scaleExponent;
-                scaled = true;
-            }
-        }
+        accumulate(*total, one, c == 0);
     }
     m->chunkVStart[nc] = vAt;
     m->chunkTStart[nc] = tAt;
     HIP_CHECK(hipStreamSynchronize(ctx->stream));       /* the temporaries go with the call */
+    return MLSGPU_OK;
+}
+
+/* In place (smooth, flip): stage(chunk, &one) writes over the chunk.  A failure costs the results: earlier chunks are changed
+ * already, and the one that failed holds what it reached. */
+template<typename Stats, typename Stage>
+static int stageInPlace(mlsgpu_mesher *m, Stats *total, Stage stage)
+{
+    m->dropNormals();           /* the positions or the triangles change */
+    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
+    bool first = true;
+    for (size_t c = 0; c < nc; c++)
+    {
+        const Span s = m->span(c);
+        if (s.nt == 0)
+            continue;
+        Stats one;
+        const int rc = stage(s, &one);
+        if (rc != MLSGPU_OK)
+        {
+            m->dropResults();
+            return rc;
+        }
+        accumulate(*total, one, first);
+        first = false;
+    }
+    return MLSGPU_OK;
+}
+
+/* Into a new generation (fill, repair, collapse): the chunks change size and may grow, so they cannot stay where they lie.
+ * stage(chunk, outVertices, vertexCapacity, outTriangles, triangleCapacity, &one) is called twice per chunk: without room
+ * at all it stops at its capacity check with the sizes in `one` (MLSGPU_ERR_LENGTH; MLSGPU_OK where it keeps nothing, and is
+ * done), then it writes into new arrays, behind the chunk before.  Nothing of the sink changes before the last chunk is done:
+ * a failure leaves the results as they were. */
+template<typename Stats, typename Stage>
+static int stageIntoNewGeneration(mlsgpu_mesher *m, Stats *total, Stage stage)
+{
+    HIP_CHECK(hipSetDevice(m->ctx->device));
+    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
+    std::vector<Stats> one(nc);
+    std::vector<uint64_t> vStart(nc + 1, 0), tStart(nc + 1, 0);
+    for (size_t c = 0; c < nc; c++)
+    {
+        std::memset(&one[c], 0, sizeof(one[c]));
+        if (m->span(c).nt > 0)
+        {
+            const int rc = stage(m->span(c), nullptr, 0, nullptr, 0, &one[c]);
+            if (rc != MLSGPU_ERR_LENGTH && rc != MLSGPU_OK)
+                return rc;
+        }
+        vStart[c + 1] = vStart[c] + one[c].outVertices;
+        tStart[c + 1] = tStart[c] + one[c].outTriangles;
+    }
+    DeviceArray<float> newVertices;
+    DeviceArray<uint32_t> newTriangles;
+    PROPAGATE(newVertices.alloc(std::max<uint64_t>(3 * vStart[nc], 1)));
+    PROPAGATE(newTriangles.alloc(std::max<uint64_t>(3 * tStart[nc], 1)));
+    bool first = true;
+    for (size_t c = 0; c < nc; c++)
+    {
+        if (m->span(c).nt == 0)
+            continue;
+        if (one[c].outTriangles > 0)
+            PROPAGATE(stage(m->span(c), newVertices + 3 * vStart[c], one[c].outVertices, newTriangles + 3 * tStart[c], one[c].outTriangles,
+                            &one[c]));
+        accumulate(*total, one[c], first);
+        first = false;
+    }
+    /* the new generation takes the old one's place (which goes with this call) */
+    m->outVertices = std::move(newVertices);
+    m->outTriangles = std::move(newTriangles);
+    m->chunkVStart = vStart;
+    m->chunkTStart = tStart;
+    m->dropNormals();           /* the chunks have changed and moved */
     return MLSGPU_OK;
 }
 
@@ -1293,7 +1495,11 @@ MLSGPU_API int mlsgpu_hip_mesher_simplify(mlsgpu_mesher *m, const float origin[3
     REQUIRE(m != nullptr && origin != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
     std::lock_guard<std::mutex> lock(m->mutex);
     REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
-    return simplifyChunks(m, origin, cellSize, stats, nullptr);
+    std::memset(stats, 0, sizeof(*stats));
+    return simplifyChunks(m, stats, [&](const Span &s, float *outV, uint32_t *outT, mlsgpu_simplify_stats *one) {
+        return mlsgpu_hip_mesh_simplify(m->ctx, m->outVertices + 3 * s.v0, s.nv, m->outTriangles + 3 * s.t0, s.nt, origin, cellSize, outV,
+                                        outT, one);
+    });
 }
 
 MLSGPU_API int mlsgpu_hip_mesher_simplify_quadric(mlsgpu_mesher *m, const float origin[3], float cellSize,
@@ -1302,15 +1508,11 @@ MLSGPU_API int mlsgpu_hip_mesher_simplify_quadric(mlsgpu_mesher *m, const float 
     REQUIRE(m != nullptr && origin != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
     std::lock_guard<std::mutex> lock(m->mutex);
     REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
-    mlsgpu_simplify_stats shared = mlsgpu_simplify_stats();
-    const int rc = simplifyChunks(m, origin, cellSize, &shared, stats);
-    stats->inVertices = shared.inVertices;
-    stats->inTriangles = shared.inTriangles;
-    stats->outVertices = shared.outVertices;
-    stats->outTriangles = shared.outTriangles;
-    stats->collapsedTriangles = shared.collapsedTriangles;
-    stats->duplicateTriangles = shared.duplicateTriangles;
-    return rc;
+    std::memset(stats, 0, sizeof(*stats));
+    return simplifyChunks(m, stats, [&](const Span &s, float *outV, uint32_t *outT, mlsgpu_simplify_quadric_stats *one) {
+        return mlsgpu_hip_mesh_simplify_quadric(m->ctx, m->outVertices + 3 * s.v0, s.nv, m->outTriangles + 3 * s.t0, s.nt, origin, cellSize,
+                                                outV, outT, one);
+    });
 }
 
 /* Every output chunk through mlsgpu_hip_mesh_smooth (smooth.hip), in place: only the positions change. */
@@ -1323,40 +1525,12 @@ MLSGPU_API int mlsgpu_hip_mesher_smooth(mlsgpu_mesher *m, uint32_t iterations, f
     /* mlsgpu_hip_mesh_smooth's own checks, here so that a refused parameter costs no results */
     REQUIRE(std::isfinite(lambda) && lambda > 0.0f && lambda <= 1.0f && std::isfinite(mu) && mu >= -1.0f && mu <= 0.0f, MLSGPU_ERR_INVALID);
     REQUIRE(boundary == MLSGPU_SMOOTH_BOUNDARY_FIXED || boundary == MLSGPU_SMOOTH_BOUNDARY_CURVE, MLSGPU_ERR_INVALID);
-    mlsgpu_ctx *const ctx = m->ctx;
-    m->dropNormals();           /* the positions change */
     std::memset(stats, 0, sizeof(*stats));
     stats->passes = (uint64_t) iterations * (mu != 0.0f ? 2 : 1);
-    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
-    bool first = true;
-    for (size_t c = 0; c < nc; c++)
-    {
-        const auto [v0, t0, nv, nt] = m->span(c);
-        if (nt == 0)
-            continue;           /* a chunk without triangles has no output (finalize) */
-        mlsgpu_smooth_stats one;
-        const int rc = mlsgpu_hip_mesh_smooth(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, iterations, lambda, mu,
-                                              boundary, m->outVertices + 3 * v0, &one);
-        if (rc != MLSGPU_OK)
-        {
-            m->dropResults();   /* earlier chunks are smoothed already, and a chunk that diverged holds what it reached */
-            return rc;
-        }
-        stats->numVertices += one.numVertices;
-        stats->numTriangles += one.numTriangles;
-        stats->outOfRangeTriangles += one.outOfRangeTriangles;
-        stats->degenerateTriangles += one.degenerateTriangles;
-        stats->numEdges += one.numEdges;
-        stats->boundaryEdges += one.boundaryEdges;
-        stats->boundaryVertices += one.boundaryVertices;
-        stats->isolatedVertices += one.isolatedVertices;
-        stats->passes = one.passes;
-        stats->scaleExponent = first ? one.scaleExponent : std::max(stats->scaleExponent, one.scaleExponent);
-        stats->maxMove = std::max(stats->maxMove, one.maxMove);
-        stats->maxCoordinate = std::max(stats->maxCoordinate, one.maxCoordinate);
-        first = false;
-    }
-    return MLSGPU_OK;
+    return stageInPlace(m, stats, [&](const Span &s, mlsgpu_smooth_stats *one) {
+        return mlsgpu_hip_mesh_smooth(m->ctx, m->outVertices + 3 * s.v0, s.nv, m->outTriangles + 3 * s.t0, s.nt, iterations, lambda, mu,
+                                      boundary, m->outVertices + 3 * s.v0, one);
+    });
 }
 
 /* Every output chunk through mlsgpu_hip_mesh_flip_edges (flip.hip), in place: only the triangles change. */
@@ -1367,52 +1541,15 @@ MLSGPU_API int mlsgpu_hip_mesher_flip_edges(mlsgpu_mesher *m, uint32_t maxRounds
     REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
     /* mlsgpu_hip_mesh_flip_edges's own checks, here so that a refused parameter costs no results */
     REQUIRE(std::isfinite(minGain) && minGain >= 0.0 && minCos >= -1.0 && minCos <= 1.0, MLSGPU_ERR_INVALID);
-    mlsgpu_ctx *const ctx = m->ctx;
-    m->dropNormals();           /* the triangles change */
     std::memset(stats, 0, sizeof(*stats));
     stats->converged = maxRounds > 0 ? 1 : 0;       /* the AND over the chunks starts where a mesh without triangles ends */
-    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
-    bool first = true;
-    for (size_t c = 0; c < nc; c++)
-    {
-        const auto [v0, t0, nv, nt] = m->span(c);
-        if (nt == 0)
-            continue;           /* a chunk without triangles has no output (finalize) */
-        mlsgpu_flip_stats one;
-        const int rc = mlsgpu_hip_mesh_flip_edges(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, maxRounds, minGain, minCos,
-                                                  m->outTriangles + 3 * t0, &one);
-        if (rc != MLSGPU_OK)
-        {
-            m->dropResults();   /* earlier chunks are flipped already */
-            return rc;
-        }
-        stats->numVertices += one.numVertices;
-        stats->numTriangles += one.numTriangles;
-        stats->outOfRangeTriangles += one.outOfRangeTriangles;
-        stats->degenerateTriangles += one.degenerateTriangles;
-        stats->numEdges += one.numEdges;
-        stats->interiorEdges += one.interiorEdges;
-        stats->rounds = std::max(stats->rounds, one.rounds);
-        stats->flips += one.flips;
-        stats->converged &= one.converged;
-        stats->nonDelaunayBefore += one.nonDelaunayBefore;
-        stats->nonDelaunayAfter += one.nonDelaunayAfter;
-        stats->blockedAfter += one.blockedAfter;
-        stats->minQualityBefore = first ? one.minQualityBefore : std::min(stats->minQualityBefore, one.minQualityBefore);
-        stats->minQualityAfter = first ? one.minQualityAfter : std::min(stats->minQualityAfter, one.minQualityAfter);
-        for (int k = 0; k < 16; k++)
-        {
-            stats->qualityBefore[k] += one.qualityBefore[k];
-            stats->qualityAfter[k] += one.qualityAfter[k];
-        }
-        first = false;
-    }
-    return MLSGPU_OK;
+    return stageInPlace(m, stats, [&](const Span &s, mlsgpu_flip_stats *one) {
+        return mlsgpu_hip_mesh_flip_edges(m->ctx, m->outVertices + 3 * s.v0, s.nv, m->outTriangles + 3 * s.t0, s.nt, maxRounds, minGain,
+                                          minCos, m->outTriangles + 3 * s.t0, one);
+    });
 }
 
-/* Every output chunk that has triangles through mlsgpu_hip_mesh_fill_holes (fill.hip).  The chunks grow, so they cannot stay
- * where they lie: a first round asks every chunk for its sizes, a second fills it into new arrays, behind the chunk before.
- * Nothing of the sink changes before the last chunk is done: an error leaves the results as they were. */
+/* Every output chunk that has triangles through mlsgpu_hip_mesh_fill_holes (fill.hip), into a new generation: the chunks grow. */
 MLSGPU_API int mlsgpu_hip_mesher_fill_holes(mlsgpu_mesher *m, uint32_t maxEdges, mlsgpu_fill_stats *stats)
 {
     REQUIRE(m != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
@@ -1423,74 +1560,23 @@ MLSGPU_API int mlsgpu_hip_mesher_fill_holes(mlsgpu_mesher *m, uint32_t maxEdges,
     mlsgpu_ctx *const ctx = m->ctx;
     HIP_CHECK(hipSetDevice(ctx->device));
     std::memset(stats, 0, sizeof(*stats));
-    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
     /* the seams: with several chunks, a vertex that another chunk has too is pinned */
     DeviceArray<uint8_t> pinned;
     if (m->outChunks.size() > 1)
     {
+        const size_t nc = m->chunkVStart.size() - 1;    /* finalize sized the tables: [chunks + 1] */
         PROPAGATE(pinned.alloc(m->chunkVStart[nc]));
         PROPAGATE(seamMask(ctx, m->outVertices, m->chunkVStart[nc], m->chunkVStart.data(), (uint32_t) nc, pinned));
     }
-    std::vector<mlsgpu_fill_stats> one(nc);
-    std::vector<uint64_t> vStart(nc + 1, 0), tStart(nc + 1, 0);
-    for (size_t c = 0; c < nc; c++)
-    {
-        const auto [v0, t0, nv, nt] = m->span(c);
-        std::memset(&one[c], 0, sizeof(one[c]));
-        if (nt > 0)     /* a chunk without triangles has no output (finalize), and keeps none */
-        {
-            /* no room at all: the call stops at its capacity check, with the sizes */
-            const int rc = mlsgpu_hip_mesh_fill_holes(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, maxEdges,
-                                                      pinned.get() != nullptr ? pinned + v0 : nullptr, nullptr, 0, nullptr, 0, &one[c]);
-            if (rc != MLSGPU_ERR_LENGTH)
-                return rc != MLSGPU_OK ? rc : setError(MLSGPU_ERR_HIP, "mesher fill holes: a chunk with triangles has an empty result");
-        }
-        vStart[c + 1] = vStart[c] + one[c].outVertices;
-        tStart[c + 1] = tStart[c] + one[c].outTriangles;
-    }
-    DeviceArray<float> newVertices;
-    DeviceArray<uint32_t> newTriangles;
-    PROPAGATE(newVertices.alloc(std::max<uint64_t>(3 * vStart[nc], 1)));
-    PROPAGATE(newTriangles.alloc(std::max<uint64_t>(3 * tStart[nc], 1)));
-    bool first = true;
-    for (size_t c = 0; c < nc; c++)
-    {
-        const auto [v0, t0, nv, nt] = m->span(c);
-        if (nt == 0)
-            continue;
-        PROPAGATE(mlsgpu_hip_mesh_fill_holes(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, maxEdges,
-                                             pinned.get() != nullptr ? pinned + v0 : nullptr, newVertices + 3 * vStart[c],
-                                             one[c].outVertices, newTriangles + 3 * tStart[c], one[c].outTriangles, &one[c]));
-        const mlsgpu_fill_stats &s = one[c];
-        stats->numVertices += s.numVertices;
-        stats->numTriangles += s.numTriangles;
-        stats->outOfRangeTriangles += s.outOfRangeTriangles;
-        stats->degenerateTriangles += s.degenerateTriangles;
-        stats->boundaryEdges += s.boundaryEdges;
-        stats->irregularEdges += s.irregularEdges;
-        stats->loops += s.loops;
-        stats->filledLoops += s.filledLoops;
-        stats->longLoops += s.longLoops;
-        stats->pinnedLoops += s.pinnedLoops;
-        stats->filledEdges += s.filledEdges;
-        stats->longestLoop = std::max(stats->longestLoop, s.longestLoop);
-        stats->outVertices += s.outVertices;
-        stats->outTriangles += s.outTriangles;
-        stats->scaleExponent = first ? s.scaleExponent : std::max(stats->scaleExponent, s.scaleExponent);
-        first = false;
-    }
-    /* the new generation takes the old one's place (which goes with this call) */
-    m->outVertices = std::move(newVertices);
-    m->outTriangles = std::move(newTriangles);
-    m->chunkVStart = vStart;
-    m->chunkTStart = tStart;
-    m->dropNormals();           /* the chunks have changed and moved */
-    return MLSGPU_OK;
+    return stageIntoNewGeneration(m, stats, [&](const Span &s, float *outV, uint64_t capV, uint32_t *outT, uint64_t capT,
+                                                mlsgpu_fill_stats *one) {
+        return mlsgpu_hip_mesh_fill_holes(ctx, m->outVertices + 3 * s.v0, s.nv, m->outTriangles + 3 * s.t0, s.nt, maxEdges,
+                                          pinned.get() != nullptr ? pinned + s.v0 : nullptr, outV, capV, outT, capT, one);
+    });
 }
 
-/* Every output chunk that has triangles through mlsgpu_hip_mesh_repair (repair.hip), by the route of the hole filling above: a
- * chunk can grow in vertices, so a first round asks every chunk for its sizes and a second repairs it into new arrays, behind
- * the chunk before.  Nothing of the sink changes before the last chunk is done: an error leaves the results as they were. */
+/* Every output chunk that has triangles through mlsgpu_hip_mesh_repair (repair.hip), into a new generation: a chunk can grow
+ * in vertices. */
 MLSGPU_API int mlsgpu_hip_mesher_repair(mlsgpu_mesher *m, uint32_t flags, mlsgpu_repair_stats *stats)
 {
     REQUIRE(m != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
@@ -1498,64 +1584,15 @@ MLSGPU_API int mlsgpu_hip_mesher_repair(mlsgpu_mesher *m, uint32_t flags, mlsgpu
     REQUIRE((flags & ~(uint32_t) MLSGPU_REPAIR_SPLIT_PINCHES) == 0, MLSGPU_ERR_INVALID);
     std::lock_guard<std::mutex> lock(m->mutex);
     REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
-    mlsgpu_ctx *const ctx = m->ctx;
-    HIP_CHECK(hipSetDevice(ctx->device));
     std::memset(stats, 0, sizeof(*stats));
-    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
-    std::vector<mlsgpu_repair_stats> one(nc);
-    std::vector<uint64_t> vStart(nc + 1, 0), tStart(nc + 1, 0);
-    for (size_t c = 0; c < nc; c++)
-    {
-        const auto [v0, t0, nv, nt] = m->span(c);
-        std::memset(&one[c], 0, sizeof(one[c]));
-        if (nt > 0)     /* a chunk without triangles has no output (finalize), and keeps none */
-        {
-            /* no room at all: the call stops at its capacity check, with the sizes (or keeps nothing, and is done) */
-            const int rc = mlsgpu_hip_mesh_repair(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, flags, nullptr, 0, nullptr, 0,
-                                                  nullptr, &one[c]);
-            if (rc != MLSGPU_ERR_LENGTH && rc != MLSGPU_OK)
-                return rc;
-        }
-        vStart[c + 1] = vStart[c] + one[c].outVertices;
-        tStart[c + 1] = tStart[c] + one[c].outTriangles;
-    }
-    DeviceArray<float> newVertices;
-    DeviceArray<uint32_t> newTriangles;
-    PROPAGATE(newVertices.alloc(std::max<uint64_t>(3 * vStart[nc], 1)));
-    PROPAGATE(newTriangles.alloc(std::max<uint64_t>(3 * tStart[nc], 1)));
-    for (size_t c = 0; c < nc; c++)
-    {
-        const auto [v0, t0, nv, nt] = m->span(c);
-        if (nt == 0)
-            continue;
-        if (one[c].outTriangles > 0)
-            PROPAGATE(mlsgpu_hip_mesh_repair(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, flags, newVertices + 3 * vStart[c],
-                                             one[c].outVertices, newTriangles + 3 * tStart[c], one[c].outTriangles, nullptr, &one[c]));
-        const mlsgpu_repair_stats &s = one[c];
-        stats->numVertices += s.numVertices;
-        stats->numTriangles += s.numTriangles;
-        stats->outOfRangeTriangles += s.outOfRangeTriangles;
-        stats->degenerateTriangles += s.degenerateTriangles;
-        stats->repeatedSides += s.repeatedSides;
-        stats->droppedTriangles += s.droppedTriangles;
-        stats->unusedVertices += s.unusedVertices;
-        stats->splitVertices += s.splitVertices;
-        stats->addedVertices += s.addedVertices;
-        stats->outVertices += s.outVertices;
-        stats->outTriangles += s.outTriangles;
-    }
-    /* the new generation takes the old one's place (which goes with this call) */
-    m->outVertices = std::move(newVertices);
-    m->outTriangles = std::move(newTriangles);
-    m->chunkVStart = vStart;
-    m->chunkTStart = tStart;
-    m->dropNormals();           /* the chunks have changed and moved */
-    return MLSGPU_OK;
+    return stageIntoNewGeneration(m, stats, [&](const Span &s, float *outV, uint64_t capV, uint32_t *outT, uint64_t capT,
+                                                mlsgpu_repair_stats *one) {
+        return mlsgpu_hip_mesh_repair(m->ctx, m->outVertices + 3 * s.v0, s.nv, m->outTriangles + 3 * s.t0, s.nt, flags, outV, capV, outT,
+                                      capT, nullptr, one);
+    });
 }
 
-/* Every output chunk that has triangles through mlsgpu_hip_mesh_collapse_edges (collapse.hip), by the route of the repair
- * above: a first round asks every chunk for its sizes, a second collapses it into new arrays, behind the chunk before.  Nothing
- * of the sink changes before the last chunk is done: an error leaves the results as they were. */
+/* Every output chunk that has triangles through mlsgpu_hip_mesh_collapse_edges (collapse.hip), into a new generation. */
 MLSGPU_API int mlsgpu_hip_mesher_collapse_edges(mlsgpu_mesher *m, uint32_t maxRounds, double maxLength, double minCos,
                                                 mlsgpu_collapse_stats *stats)
 {
@@ -1564,78 +1601,14 @@ MLSGPU_API int mlsgpu_hip_mesher_collapse_edges(mlsgpu_mesher *m, uint32_t maxRo
     REQUIRE(std::isfinite(maxLength) && maxLength >= 0.0 && minCos >= 0.0 && minCos <= 1.0, MLSGPU_ERR_INVALID);
     std::lock_guard<std::mutex> lock(m->mutex);
     REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
-    mlsgpu_ctx *const ctx = m->ctx;
-    HIP_CHECK(hipSetDevice(ctx->device));
     std::memset(stats, 0, sizeof(*stats));
     stats->converged = maxRounds > 0 ? 1 : 0;       /* the AND over the chunks starts where a mesh without triangles ends */
     stats->minLengthSqBefore = stats->minLengthSqAfter = INFINITY;
-    const size_t nc = m->chunkVStart.size() - 1;        /* finalize sized the tables: [chunks + 1] */
-    std::vector<mlsgpu_collapse_stats> one(nc);
-    std::vector<uint64_t> vStart(nc + 1, 0), tStart(nc + 1, 0);
-    for (size_t c = 0; c < nc; c++)
-    {
-        const auto [v0, t0, nv, nt] = m->span(c);
-        std::memset(&one[c], 0, sizeof(one[c]));
-        if (nt > 0)     /* a chunk without triangles has no output (finalize), and keeps none */
-        {
-            /* no room at all: the call stops at its capacity check, with the sizes (or keeps nothing, and is done) */
-            const int rc = mlsgpu_hip_mesh_collapse_edges(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, maxRounds, maxLength,
-                                                          minCos, nullptr, 0, nullptr, 0, nullptr, &one[c]);
-            if (rc != MLSGPU_ERR_LENGTH && rc != MLSGPU_OK)
-                return rc;
-        }
-        vStart[c + 1] = vStart[c] + one[c].outVertices;
-        tStart[c + 1] = tStart[c] + one[c].outTriangles;
-    }
-    DeviceArray<float> newVertices;
-    DeviceArray<uint32_t> newTriangles;
-    PROPAGATE(newVertices.alloc(std::max<uint64_t>(3 * vStart[nc], 1)));
-    PROPAGATE(newTriangles.alloc(std::max<uint64_t>(3 * tStart[nc], 1)));
-    bool first = true;
-    for (size_t c = 0; c < nc; c++)
-    {
-        const auto [v0, t0, nv, nt] = m->span(c);
-        if (nt == 0)
-            continue;
-        if (one[c].outTriangles > 0)
-            PROPAGATE(mlsgpu_hip_mesh_collapse_edges(ctx, m->outVertices + 3 * v0, nv, m->outTriangles + 3 * t0, nt, maxRounds, maxLength, minCos,
-                                                     newVertices + 3 * vStart[c], one[c].outVertices, newTriangles + 3 * tStart[c],
-                                                     one[c].outTriangles, nullptr, &one[c]));
-        const mlsgpu_collapse_stats &s = one[c];
-        stats->numVertices += s.numVertices;
-        stats->numTriangles += s.numTriangles;
-        stats->outOfRangeTriangles += s.outOfRangeTriangles;
-        stats->degenerateTriangles += s.degenerateTriangles;
-        stats->numEdges += s.numEdges;
-        stats->interiorEdges += s.interiorEdges;
-        stats->fixedVertices += s.fixedVertices;
-        stats->rounds = std::max(stats->rounds, s.rounds);
-        stats->collapses += s.collapses;
-        stats->converged &= s.converged;
-        stats->shortBefore += s.shortBefore;
-        stats->shortAfter += s.shortAfter;
-        stats->blockedAfter += s.blockedAfter;
-        stats->unusedVertices += s.unusedVertices;
-        stats->outVertices += s.outVertices;
-        stats->outTriangles += s.outTriangles;
-        stats->minQualityBefore = first ? s.minQualityBefore : std::min(stats->minQualityBefore, s.minQualityBefore);
-        stats->minQualityAfter = first ? s.minQualityAfter : std::min(stats->minQualityAfter, s.minQualityAfter);
-        stats->minLengthSqBefore = std::min(stats->minLengthSqBefore, s.minLengthSqBefore);
-        stats->minLengthSqAfter = std::min(stats->minLengthSqAfter, s.minLengthSqAfter);
-        for (int k = 0; k < 16; k++)
-        {
-            stats->qualityBefore[k] += s.qualityBefore[k];
-            stats->qualityAfter[k] += s.qualityAfter[k];
-        }
-        first = false;
-    }
-    /* the new generation takes the old one's place (which goes with this call) */
-    m->outVertices = std::move(newVertices);
-    m->outTriangles = std::move(newTriangles);
-    m->chunkVStart = vStart;
-    m->chunkTStart = tStart;
-    m->dropNormals();           /* the chunks have changed and moved */
-    return MLSGPU_OK;
+    return stageIntoNewGeneration(m, stats, [&](const Span &s, float *outV, uint64_t capV, uint32_t *outT, uint64_t capT,
+                                                mlsgpu_collapse_stats *one) {
+        return mlsgpu_hip_mesh_collapse_edges(m->ctx, m->outVertices + 3 * s.v0, s.nv, m->outTriangles + 3 * s.t0, s.nt, maxRounds,
+                                              maxLength, minCos, outV, capV, outT, capT, nullptr, one);
+    });
 }
 
 /* ---- the deviation report of the sink against a kept copy of itself (deviation.hip) ---- */
@@ -1668,30 +1641,6 @@ MLSGPU_API int mlsgpu_hip_mesher_drop_reference(mlsgpu_mesher *m)
     std::lock_guard<std::mutex> lock(m->mutex);
     m->dropReference();
     return MLSGPU_OK;
-}
-
-/* *total += the report of dense chunk c: the counts add, the maximum and the lowest (chunk, point) that attains it are kept.
- * The chunks come in ascending order, so a later chunk takes the maximum over only by exceeding it. */
-static void addDeviation(mlsgpu_deviation *total, const mlsgpu_deviation &one, uint64_t c)
-{
-    total->numPoints += one.numPoints;
-    total->numVertices += one.numVertices;
-    total->numTriangles += one.numTriangles;
-    total->outOfRangeTriangles += one.outOfRangeTriangles;
-    total->degenerateTriangles += one.degenerateTriangles;
-    total->beyond += one.beyond;
-    for (int k = 0; k < 16; k++)
-        total->histogram[k] += one.histogram[k];
-    total->sumQ += one.sumQ;
-    if (one.numPoints > 0)
-        total->scaleExponent = one.scaleExponent;       /* D is the same for every chunk, hence e */
-    if (one.within > 0 && (total->within == 0 || one.maxDistance2 > total->maxDistance2))
-    {
-        total->maxDistance2 = one.maxDistance2;
-        total->farthestChunk = c;
-        total->farthestPoint = one.farthestPoint;
-    }
-    total->within += one.within;
 }
 
 MLSGPU_API int mlsgpu_hip_mesher_deviation(mlsgpu_mesher *m, float maxDistance, mlsgpu_deviation *moved, mlsgpu_deviation *lost)
