@@ -606,6 +606,406 @@ __global__ __launch_bounds__(ENT_THREADS) __attribute__((amdgpu_waves_per_eu(ENT
     }
 }
 
+/*
+ * The last pass of the entry sort on the packed route (one word per entry, top digit << idBits | id; the key's low part is
+ * the group of the fused pass the word lies in, group g at [lowBase[g], lowBase[g + 1])): commandHistKernel counts the top
+ * digits per tile and the whole keys, commandScatterKernel sends every id to its command position.  They compute what
+ * sortHistKernel<uint32_t, true> and sortScatterKernel<uint32_t, false, 8, true> compute on these words (primitives.hpp;
+ * MLSGPU_HIP_OCTREE_LAST_PASS=0 takes those, for A/B) -- same tiles, same [digit][tile] histogram, same order -- with the
+ * work a tile of packed words does not need left out: a tile is FULL (every one but a lane's last) and lies in ONE low part
+ * (six of seven on the headline cloud) or it does not, which the workgroup finds out once, and the common tile runs
+ * straight-line code.  Digits have 8 bits at most here (the fused pass's limit), so a thread owns one bin.
+ */
+enum { CMD_BINS = 1 << ENT_BIN_BITS };
+static_assert(CMD_BINS == PRIM_BLOCK, "one bin and one group begin per thread");
+
+/* The groups the tile's first and last element lie in: counts of group begins at or before them (group 0 begins at 0; an
+ * empty group begins where the next one does, so the count lands on the group that holds the position).  Every wave counts
+ * all numLow <= 256 begins itself: nothing crosses waves, nothing waits for a barrier.  myBegin: lowBase[threadIdx.x]. */
+__device__ __forceinline__ void lowPartsOfTile(const uint32_t *lowBase, uint32_t numLow, uint32_t first, uint32_t last,
+                                               uint32_t &lowFirst, bool &oneLow, uint32_t &myBegin)
+{
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    /* lowBase has CMD_BINS + 1 words whatever numLow is (dDigitBase): all four are requested before the first is looked at */
+    uint32_t begins[PRIM_WAVES];
+#pragma unroll
+    for (uint32_t q = 0; q < PRIM_WAVES; q++)
+        begins[q] = lowBase[q * 64 + lane];
+    uint32_t c0 = 0, c1 = 0;
+    myBegin = 0xFFFFFFFFu;
+#pragma unroll
+    for (uint32_t q = 0; q < PRIM_WAVES; q++)
+    {
+        const uint32_t begin = q * 64 + lane < numLow ? begins[q] : 0xFFFFFFFFu;
+        c0 += (uint32_t) __popcll(__ballot(begin <= first));
+        c1 += (uint32_t) __popcll(__ballot(begin <= last));
+        if (q == wave)
+            myBegin = begin;
+    }
+    lowFirst = c0 - 1;
+    oneLow = c1 == c0;
+}
+
+struct CommandHistArgs
+{
+    const uint32_t *words;
+    uint32_t *hist;
+    uint32_t n;
+    const uint32_t *nDev;
+    uint32_t numTiles;
+    uint32_t *keyCounts;        /* occurrences of every whole key, (top digit << shift) | low part */
+    const uint32_t *lowBase;    /* CMD_BINS + 1 words, the first 2^shift + 1 of them written */
+};
+
+__global__ __launch_bounds__(PRIM_BLOCK) void commandHistKernel(Lanes<CommandHistArgs> lanes, uint32_t shift, uint32_t digitBits,
+                                                                uint32_t idBits)
+{
+    const CommandHistArgs A = lanes.a[blockIdx.y];
+    if (blockIdx.x >= A.numTiles)
+        return;
+    uint32_t n = A.n;
+    if (A.nDev != nullptr && *A.nDev < n)
+        n = *A.nDev;
+    __shared__ uint32_t bins[CMD_BINS];
+    __shared__ uint32_t keyBins[KEY_COUNT_SLOTS * CMD_BINS];
+    __shared__ uint32_t sLow[CMD_BINS];
+    const uint32_t numBins = 1u << digitBits, numLow = 1u << shift;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t tile = tileOfWorkgroup(blockIdx.x, A.numTiles);
+    const uint32_t tileFirst = tile * SORT_TILE;
+    /* (0: a tile behind nDev still reports its histogram, all zeros) */
+    const uint32_t tileCount = tileFirst >= n ? 0u : n - tileFirst < SORT_TILE ? n - tileFirst : (uint32_t) SORT_TILE;
+    const bool full = tileCount == SORT_TILE;
+    const uint32_t at = wave * SORT_WAVE_SPAN + lane;           /* the thread's first element in the tile */
+    const uint32_t *const words = A.words + tileFirst + at;
+    /* all of the thread's words are requested before the first is counted, and the group begins with them */
+    uint32_t mine[SORT_ITEMS];
+    if (full)
+    {
+        /* (four words to a load, a wave's load one KB, was measured and changed nothing: 40.9 against 40.2 us) */
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++)
+            mine[j] = words[j * 64];
+    }
+    else
+    {
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++)
+            mine[j] = at + j * 64 < tileCount ? words[j * 64] : 0u;
+    }
+    uint32_t lowFirst = 0, myBegin;
+    bool oneLow = true;
+    lowPartsOfTile(A.lowBase, numLow, tileFirst, tileFirst + (tileCount != 0 ? tileCount - 1 : 0u), lowFirst, oneLow, myBegin);
+    bins[threadIdx.x] = 0;
+    if (!oneLow)        /* (uniform over the workgroup) */
+    {
+        sLow[threadIdx.x] = myBegin;
+#pragma unroll
+        for (uint32_t d = threadIdx.x; d < KEY_COUNT_SLOTS * CMD_BINS; d += PRIM_BLOCK)
+            keyBins[d] = 0;
+    }
+    __syncthreads();
+    if (full && oneLow)
+    {
+        /* the common tile: the digit bins ARE the key counts */
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++)
+            atomicAdd(&bins[__builtin_amdgcn_ubfe(mine[j], idBits, digitBits)], 1u);
+    }
+    else
+    {
+        /* a lane's last tile, or one across low parts: the counts are gathered per (low part, top digit) for the first
+         * KEY_COUNT_SLOTS low parts of the tile; keys of further ones (tiny groups) go straight to memory */
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++)
+            if (at + j * 64 < tileCount)
+            {
+                const uint32_t digit = __builtin_amdgcn_ubfe(mine[j], idBits, digitBits);
+                atomicAdd(&bins[digit], 1u);
+                if (!oneLow)
+                {
+                    const uint32_t low = lowPartAt(sLow, lowFirst, numLow, tileFirst + at + j * 64);
+                    const uint32_t slot = low - lowFirst;
+                    if (slot < KEY_COUNT_SLOTS)
+                        atomicAdd(&keyBins[slot * CMD_BINS + digit], 1u);
+                    else
+                        atomicAdd(&A.keyCounts[(digit << shift) | low], 1u);
+                }
+            }
+    }
+    __syncthreads();
+    const uint32_t d = threadIdx.x;
+    if (d < numBins)
+    {
+        const uint32_t c = bins[d];
+        A.hist[(uint64_t) d * A.numTiles + tile] = c;
+        if (oneLow && c != 0)
+            atomicAdd(&A.keyCounts[(d << shift) | lowFirst], c);
+    }
+    if (!oneLow)
+#pragma unroll
+        for (uint32_t k = threadIdx.x; k < KEY_COUNT_SLOTS * CMD_BINS; k += PRIM_BLOCK)
+        {
+            const uint32_t c = keyBins[k];
+            if (c != 0)
+                atomicAdd(&A.keyCounts[((k & (CMD_BINS - 1u)) << shift) | (lowFirst + (k >> ENT_BIN_BITS))], c);
+        }
+}
+
+struct CommandScatterArgs
+{
+    const uint32_t *words;
+    uint32_t *commands;
+    const uint32_t *hist;
+    const uint32_t *digitTotals;
+    uint32_t n;
+    const uint32_t *nDev;
+    uint32_t numTiles;
+    const uint32_t *keyBase;    /* the id of sorted rank r with key k goes to commands[1 + r + keyBase[k]] */
+    const uint32_t *lowBase;
+    uint32_t numKeys;           /* keyBase[0 .. numKeys) */
+    uint32_t valueBias;         /* what goes out is id + valueBias */
+};
+
+/* The ranking and the tile in its new order live in the same 16 KB: the match words and runs are dead once every element
+ * knows its place.  With the small tables 18 KB: eight workgroups to a CU, where the template's 30 KB allowed five. */
+struct CommandTileLds
+{
+    union
+    {
+        struct
+        {
+            unsigned long long match[PRIM_WAVES][CMD_BINS];    /* per wave and digit: the lanes that hold the digit this round */
+            uint32_t run[PRIM_WAVES][CMD_BINS];                 /* ... the wave's elements with the digit so far; then where its
+                                                                 * first goes in the tile */
+        } rank;
+        uint32_t tile[SORT_TILE];
+    };
+    uint32_t tileBase[CMD_BINS];        /* what takes a place in the tile to a command position */
+    uint32_t low[CMD_BINS];             /* group begins, for tiles across low parts */
+    uint32_t waveTotals[PRIM_WAVES], waveTotalsAll[PRIM_WAVES];
+};
+
+/* The stable rank of each of the wave's elements among the wave's elements with the same digit, round by round: every lane
+ * ORs its bit into the digit's match word and reads the word back (LDS operations of a wave execute in order); the lanes
+ * below it in the word come before it, and the run so far before them.  The first lane of a peer group stores the run's new
+ * end and the cleared match word.  The kernel is bound by the LDS, more than half of whose cycles are bank conflicts between
+ * the digits of a round (profiles/NOTES_last_pass.md), so what counts is how many lanes touch how many banks: a lane ORs its
+ * bit into its HALF of the match word, a 32-bit operation (63.1 -> 61.1 us per launch against the 64-bit one), and every lane
+ * of the group storing the same two values, with no divergent part, lost to the one lane per digit (65.6 against 63.1).
+ * COUNTING IS RANKING: the runs start from zero, so after the last round run[digit] is the wave's count of the digit, and
+ * no separate counting phase runs before the scan over the bins.  left: elements of the wave's span that exist (!FULL). */
+template<bool FULL>
+__device__ __forceinline__ void commandRounds(CommandTileLds &s, const uint32_t (&word)[SORT_ITEMS], uint32_t (&rank)[SORT_ITEMS],
+                                              uint32_t idBits, uint32_t digitBits, uint32_t left)
+{
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long *const match = s.rank.match[wave];
+    uint32_t *const run = s.rank.run[wave];
+    const uint32_t half = lane >> 5, bit = 1u << (lane & 31u);
+#pragma unroll
+    for (int j = 0; j < SORT_ITEMS; j++)
+    {
+        const uint32_t digit = __builtin_amdgcn_ubfe(word[j], idBits, digitBits);
+        const bool valid = FULL || (uint32_t) j * 64 + lane < left;
+        if (valid)
+            atomicOr(reinterpret_cast<uint32_t *>(&match[digit]) + half, bit);
+        __builtin_amdgcn_wave_barrier();
+        rank[j] = 0;
+        if (valid)
+        {
+            const unsigned long long peers = match[digit];
+            const uint32_t before = run[digit];
+            const uint32_t below = popcBelow(peers);
+            rank[j] = before + below;
+            if (below == 0)
+            {
+                run[digit] = before + (uint32_t) __popcll(peers);
+                match[digit] = 0ull;
+            }
+        }
+        /* LDS operations of one wave complete in program order, so the next round sees the update */
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+/* ids out in tile-sorted order, each digit's run one contiguous burst; the tile lies in ONE low part, whose share of the
+ * command position is in tileBase already */
+template<bool FULL>
+__device__ __forceinline__ void commandOut(const CommandTileLds &s, uint32_t *commands, uint32_t tileCount, uint32_t idBits,
+                                           uint32_t digitBits, uint32_t valueBias)
+{
+    const uint32_t idMask = (1u << idBits) - 1u;
+#pragma unroll
+    for (int k = 0; k < SORT_ITEMS; k++)
+    {
+        const uint32_t p = threadIdx.x + k * PRIM_BLOCK;
+        if (FULL || p < tileCount)
+        {
+            const uint32_t w = s.tile[p];
+            commands[s.tileBase[__builtin_amdgcn_ubfe(w, idBits, digitBits)] + p] = (w & idMask) + valueBias;
+        }
+    }
+}
+
+__global__ __launch_bounds__(PRIM_BLOCK) void commandScatterKernel(Lanes<CommandScatterArgs> lanes, uint32_t shift,
+                                                                   uint32_t digitBits, uint32_t idBits)
+{
+    __shared__ CommandTileLds s;
+    const CommandScatterArgs A = lanes.a[blockIdx.y];
+    if (blockIdx.x >= A.numTiles)
+        return;
+    uint32_t n = A.n;
+    if (A.nDev != nullptr && *A.nDev < n)
+        n = *A.nDev;
+    const uint32_t tile = tileOfWorkgroup(blockIdx.x, A.numTiles);     /* its words of the [digit][tile] array: one L2's */
+    const uint32_t tileFirst = tile * SORT_TILE;
+    if (tileFirst >= n)
+        return;
+    const uint32_t tileCount = n - tileFirst < SORT_TILE ? n - tileFirst : (uint32_t) SORT_TILE;
+    const bool full = tileCount == SORT_TILE;
+    const uint32_t numBins = 1u << digitBits, numLow = 1u << shift;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t at = wave * SORT_WAVE_SPAN + lane;           /* the thread's first element in the tile */
+    const uint32_t left = tileCount > wave * SORT_WAVE_SPAN ? tileCount - wave * SORT_WAVE_SPAN : 0u;
+    /* Everything the workgroup reads that does not depend on another read is requested here, together: the group begins
+     * (first: the one read that depends on another waits for them alone), its words, and the digit total and tile offset of
+     * the bin this thread owns in the scan below. */
+    uint32_t lowFirst, myBegin;
+    bool oneLow;
+    const uint32_t *const words = A.words + tileFirst + at;
+    uint32_t word[SORT_ITEMS];
+    const uint32_t d = threadIdx.x;
+    const bool myBin = d < numBins;
+    lowPartsOfTile(A.lowBase, numLow, tileFirst, tileFirst + tileCount - 1, lowFirst, oneLow, myBegin);
+    if (full)
+    {
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++)
+            word[j] = words[j * 64];
+    }
+    else
+    {
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++)
+            word[j] = (uint32_t) j * 64 + lane < left ? words[j * 64] : 0u;
+    }
+    const uint32_t totalOf = myBin ? A.digitTotals[d] : 0u;
+    const uint32_t histOf = myBin ? A.hist[(uint64_t) d * A.numTiles + tile] : 0u;
+    /* a tile in one low part: a digit is a key, and 1 + keyBase[key] is folded into the digit's base -- 256 loads per tile
+     * instead of one per element.  (Keys at or above numKeys are no node's: no element has them.) */
+    const uint32_t myKey = (d << shift) | lowFirst;
+    const uint32_t keyBaseOf = A.keyBase[myKey < A.numKeys ? myKey : 0u];
+    const uint32_t fold = oneLow ? 1u + keyBaseOf : 0u;
+    /* every wave clears its own rows: no barrier before the rounds */
+#pragma unroll
+    for (uint32_t k = lane; k < CMD_BINS; k += 64)
+    {
+        s.rank.match[wave][k] = 0ull;
+        s.rank.run[wave][k] = 0u;
+    }
+    s.low[threadIdx.x] = myBegin;
+    __builtin_amdgcn_wave_barrier();
+    uint32_t rank[SORT_ITEMS];
+    if (full)
+        commandRounds<true>(s, word, rank, idBits, digitBits, left);
+    else
+        commandRounds<false>(s, word, rank, idBits, digitBits, left);
+    __syncthreads();
+    /* tile-local exclusive prefix over the digits (thread d owns bin d), and of every (wave, digit) */
+    {
+        uint32_t c[PRIM_WAVES], mine = 0;
+#pragma unroll
+        for (int w = 0; w < PRIM_WAVES; w++)
+        {
+            c[w] = s.rank.run[w][d];
+            mine += c[w];
+        }
+        const uint32_t incl = waveInclusiveScan(mine), inclAll = waveInclusiveScan(totalOf);
+        if (lane == 63)
+        {
+            s.waveTotals[wave] = incl;
+            s.waveTotalsAll[wave] = inclAll;
+        }
+        __syncthreads();
+        uint32_t run = incl - mine, base = inclAll - totalOf;
+        for (uint32_t w = 0; w < wave; w++)
+        {
+            run += s.waveTotals[w];
+            base += s.waveTotalsAll[w];
+        }
+        s.tileBase[d] = base + histOf - run + fold;
+#pragma unroll
+        for (int w = 0; w < PRIM_WAVES; w++)
+        {
+            s.rank.run[w][d] = run;
+            run += c[w];
+        }
+    }
+    __syncthreads();
+    /* every element's place in the tile-sorted sequence: its (wave, digit)'s first + its rank among them */
+    uint32_t dst[SORT_ITEMS];
+#pragma unroll
+    for (int j = 0; j < SORT_ITEMS; j++)
+        dst[j] = s.rank.run[wave][__builtin_amdgcn_ubfe(word[j], idBits, digitBits)] + rank[j];
+    __syncthreads();
+    /* ... and the words go there, over the ranking's tables */
+    if (full)
+    {
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++)
+            s.tile[dst[j]] = word[j];
+    }
+    else
+    {
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++)
+            if ((uint32_t) j * 64 + lane < left)
+                s.tile[dst[j]] = word[j];
+    }
+    __syncthreads();
+    if (oneLow)         /* (uniform over the workgroup) */
+    {
+        if (full)
+            commandOut<true>(s, A.commands, tileCount, idBits, digitBits, A.valueBias);
+        else
+            commandOut<false>(s, A.commands, tileCount, idBits, digitBits, A.valueBias);
+        return;
+    }
+    /* A tile across low parts: what travels behind the words through the tile's reorder is the low part of every element's
+     * key, and the command position takes one gather per element. */
+    const uint32_t idMask = (1u << idBits) - 1u;
+#pragma unroll
+    for (int k = 0; k < SORT_ITEMS; k++)
+    {
+        const uint32_t p = threadIdx.x + k * PRIM_BLOCK;
+        word[k] = p < tileCount ? s.tile[p] : 0u;
+    }
+    __syncthreads();
+    {
+        uint32_t low = lowFirst;
+#pragma unroll
+        for (int j = 0; j < SORT_ITEMS; j++)
+            if ((uint32_t) j * 64 + lane < left)
+            {
+                low = lowPartAt(s.low, low, numLow, tileFirst + at + (uint32_t) j * 64);
+                s.tile[dst[j]] = low;
+            }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < SORT_ITEMS; k++)
+    {
+        const uint32_t p = threadIdx.x + k * PRIM_BLOCK;
+        if (p < tileCount)
+        {
+            const uint32_t digit = __builtin_amdgcn_ubfe(word[k], idBits, digitBits);
+            const uint32_t key = (digit << shift) | s.tile[p];
+            A.commands[s.tileBase[digit] + p + 1u + A.keyBase[key]] = (word[k] & idMask) + A.valueBias;
+        }
+    }
+}
+
 /* countCommands (kernels/octree.cl:230-239) as the scan's producer.  The reference leaves the
  * last indicator unwritten; an exclusive scan never reads it, so any value serves. */
 struct IndicatorIn
@@ -654,11 +1054,12 @@ struct SplatIdsOut
  * writeSplatIds (kernels/octree.cl:256-279) puts the id of sorted rank r at command position 1 + r + 2 * (non-empty nodes
  * before the id's node): the scan of countCommands' 1 / 3 indicators (src/splat_tree_cl.cpp:310-317) is that sum, entry by
  * entry.  With the number of entries of every node at hand -- the last pass's histogram kernel counts whole keys on the way
- * (sortHistKernel<KEY_COUNTS>) -- a scan over the NODES (37 449 of them for the default tree, not 7 million entries) gives
- * each node its first rank and the number of non-empty nodes before it, hence start[] and the jump slots of the non-empty
- * nodes (NodeOut below), and the last scatter pass of the sort writes every id straight to its command position
- * (sortScatterKernel<SPREAD>): the sorted (key, id) arrays are never written and countCommands / scan / writeSplatIds do
- * not run.  `commands` and `start` are the reference's, word for word (tests/test_gpu_tree.py).
+ * (commandHistKernel above; sortHistKernel<KEY_COUNTS> for entries of two words) -- a scan over the NODES (37 449 of them
+ * for the default tree, not 7 million entries) gives each node its first rank and the number of non-empty nodes before it,
+ * hence start[] and the jump slots of the non-empty nodes (NodeOut below), and the last scatter pass of the sort writes
+ * every id straight to its command position (commandScatterKernel; sortScatterKernel<SPREAD> for two words): the sorted
+ * (key, id) arrays are never written and countCommands / scan / writeSplatIds do not run.  `commands` and `start` are the
+ * reference's, word for word (tests/test_gpu_tree.py, tests/test_gpu_last_pass.py).
  */
 struct NodeIn
 {
@@ -872,6 +1273,11 @@ static int treeBuildBatch(mlsgpu_tree *const *trees, const mlsgpu_tree_build *re
         if (direct && !packedOff && (keyBits - perPass) + bits <= 32)
             idBits = bits;
     }
+    /* packed words take the last pass's own kernels (commandHistKernel); "0": the sort's templates, as before (tests, A/B).
+     * A top digit of zero bits (trees of one to three levels) is served by the same kernels: one bin. */
+    bool lastPass = idBits != 0;
+    if (const char *const env = getenv("MLSGPU_HIP_OCTREE_LAST_PASS"))
+        lastPass = lastPass && atoi(env) != 0;
     for (uint32_t k = 0; k < count; k++)
     {
         mlsgpu_tree *t = trees[k];
@@ -981,11 +1387,20 @@ static int treeBuildBatch(mlsgpu_tree *const *trees, const mlsgpu_tree_build *re
             const auto d = packLanes<SortDigitScanArgs>(na, [&](uint32_t a) {
                 return SortDigitScanArgs{sortJobs[a].dHist, sortDigitTotals(sortJobs[a]), sortTiles(sortJobs[a].n)};
             });
+            const auto ch = packLanes<CommandHistArgs>(na, [&](uint32_t a) {
+                const SortJob<uint32_t> &j = sortJobs[a];
+                return CommandHistArgs{j.keysA, j.dHist, (uint32_t) j.n, j.nDev, sortTiles(j.n), trees[act[a]]->dNodeCounts,
+                                       trees[act[a]]->dDigitBase};
+            });
             const uint32_t maxTiles = mostOfLanes(na, [&](uint32_t a) { return sortTiles(sortJobs[a].n); });
             if (maxTiles > 0)
             {
-                LAUNCH(ctx, "kernel.octree.sort.time", (sortHistKernel<uint32_t, true>), dim3(maxTiles, na), dim3(PRIM_BLOCK), h, shift,
-                       digitBits);
+                if (lastPass)
+                    LAUNCH(ctx, "kernel.octree.sort.time", commandHistKernel, dim3(maxTiles, na), dim3(PRIM_BLOCK), ch, shift, digitBits,
+                           idBits);
+                else
+                    LAUNCH(ctx, "kernel.octree.sort.time", (sortHistKernel<uint32_t, true>), dim3(maxTiles, na), dim3(PRIM_BLOCK), h,
+                           shift, digitBits);
                 LAUNCH(ctx, "kernel.octree.sort.time", (sortDigitScanKernel<uint32_t>), dim3(1u << digitBits, na), dim3(PRIM_BLOCK), d);
             }
         }
@@ -1029,8 +1444,18 @@ static int treeBuildBatch(mlsgpu_tree *const *trees, const mlsgpu_tree_build *re
                                                  sortDigitTotals(j), j.n, j.nDev, sortTiles(j.n), t->dNodeBase, t->dDigitBase, idBits,
                                                  (uint32_t) reqs[act[a]].firstSplat};
             });
+            const auto cs = packLanes<CommandScatterArgs>(na, [&](uint32_t a) {
+                const SortJob<uint32_t> &j = sortJobs[a];
+                mlsgpu_tree *t = trees[act[a]];
+                return CommandScatterArgs{j.keysA, reinterpret_cast<uint32_t *>(t->dCommands.get()), j.dHist, sortDigitTotals(j),
+                                          (uint32_t) j.n, j.nDev, sortTiles(j.n), t->dNodeBase, t->dDigitBase, numStart,
+                                          (uint32_t) reqs[act[a]].firstSplat};
+            });
             const uint32_t maxTiles = mostOfLanes(na, [&](uint32_t a) { return sortTiles(sortJobs[a].n); });
-            if (maxTiles > 0)
+            if (maxTiles > 0 && lastPass)
+                LAUNCH(ctx, "kernel.octree.sort.time", commandScatterKernel, dim3(maxTiles, na), dim3(PRIM_BLOCK), cs, shift, digitBits,
+                       idBits);
+            else if (maxTiles > 0)
                 LAUNCH(ctx, "kernel.octree.sort.time", (sortScatterKernel<uint32_t, false, 8, true>), dim3(maxTiles, na), dim3(PRIM_BLOCK), sc,
                        shift, digitBits);
         }

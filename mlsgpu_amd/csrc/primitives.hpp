@@ -576,7 +576,8 @@ enum { KEY_COUNT_SLOTS = 4 };   /* low parts of the key a tile may span and stil
  * bits already, so a tile of 4096 keys holds one low part, sometimes two: the counts are gathered in LDS per (low part, top
  * digit) and leave as one global atomic per non-empty bin -- a sixteenth of the atomics a key-by-key count would take
  * (~16 keys per bin on the octree's entries).  Keys of a tile beyond KEY_COUNT_SLOTS low parts (tiny groups) go straight
- * to memory.
+ * to memory.  The octree's default route (packed words) has a kernel of its own for this, commandHistKernel (octree.hip);
+ * this one serves it with MLSGPU_HIP_OCTREE_LAST_PASS=0, and the entries of two words (idBits == 0).
  */
 template<typename K, bool KEY_COUNTS = false>
 __global__ __launch_bounds__(PRIM_BLOCK) void sortHistKernel(Lanes<SortHistArgs<K> > lanes, uint32_t shift, uint32_t digitBits)
@@ -778,7 +779,8 @@ struct SortScatterArgs
  *
  * SPREAD (the last pass of the octree's entry sort): the sorted keys are not written at all, and a value does not go to its
  * sorted rank r but to 1 + r + keyBase[key] -- the runs of equal keys keep their order and open up by keyBase, which is how
- * the octree's command list interleaves its per-node markers with the splat ids (octree.hip).
+ * the octree's command list interleaves its per-node markers with the splat ids (octree.hip).  Packed words go through
+ * commandScatterKernel there by default; through this kernel with MLSGPU_HIP_OCTREE_LAST_PASS=0.
  */
 template<typename K, bool IOTA, int BIN_BITS, bool SPREAD = false>
 __global__ __launch_bounds__(PRIM_BLOCK) void sortScatterKernel(Lanes<SortScatterArgs<K> > lanes, uint32_t shift, uint32_t digitBits)
