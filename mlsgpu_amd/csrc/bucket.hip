@@ -13,7 +13,8 @@
  *                          summed and swept up by two small kernels -- no scattered global atomics;
  *      either way the count is the only pass that reads the splats: it leaves every element's microblock range as an
  *      8-byte note (RegionView::packNote) for step 3;
- *   2. host: pickNodes on the few hundred counters (same traversal order, so regions are numbered alike); the regions'
+ *   2. host: pickNodes on the few hundred counters (same traversal order, so regions are numbered alike; the level's
+ *      geometry, the chunks' layouts, the pick and the regions' boxes are plain host arithmetic: bucketplan.hpp); the regions'
  *      counters are also the lengths of their member lists, so the lists' starts are known here;
  *   3. a scan whose producer counts the regions a splat joins ("once per node", bucket.cpp:291-301) and whose
  *      consumer writes (region, splat id) pairs, and a STABLE radix sort by region (one digit for up to 1024 regions,
@@ -23,6 +24,7 @@
  * them and transforms them into the full grid's vertex coordinates (BucketLoader, src/bucket_loader.cpp:77-85)
  * ready for mlsgpu_hip_worker_process -- no host round trip of splat data at all.
  */
+#include "bucketplan.hpp"
 #include "common.hpp"
 #include "primitives.hpp"
 
@@ -39,7 +41,7 @@ static int foldBbox(mlsgpu_ctx *ctx, const mlsgpu_splat *dSplats, uint64_t numSp
 namespace
 {
 
-enum { MAX_LEVELS = 32, LDS_NODES = 8192 };
+enum { LDS_NODES = 8192 };
 
 /* what a kernel needs to map a splat to the microblocks of one chunk's region */
 struct RegionView
@@ -151,13 +153,6 @@ struct RegionView
         }
         return true;
     }
-};
-
-struct LevelLayout
-{
-    uint32_t levels;
-    uint32_t dims[MAX_LEVELS][3];
-    uint32_t offset[MAX_LEVELS + 1];
 };
 
 /* countSplats + upsweepCounts (src/bucket.cpp:161-174, 207-246) without the delta encoding.
@@ -524,16 +519,6 @@ struct BatchCopyOut
 };
 __global__ void addCountKernel(uint32_t *base, const uint32_t *add) { *base += *add; }
 
-/* first pair of every region in the region-sorted list (every region has at least one member) */
-__global__ void regionStartsKernel(const uint32_t *keys, uint64_t n, uint32_t *starts)
-{
-    const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    if (i == 0 || keys[i] != keys[i - 1])
-        starts[keys[i]] = (uint32_t) i;
-}
-
 /* BucketLoader, src/bucket_loader.cpp:77-85 with Grid::worldToVertex (src/grid.cpp:99-106) */
 __global__ void bucketLoadKernel(const mlsgpu_splat *splats, const uint32_t *ids, uint64_t n, float rx, float ry, float rz,
                                  float invSpacing, float lx, float ly, float lz, mlsgpu_splat *out)
@@ -615,46 +600,12 @@ uint32_t bitsForCount(uint32_t count)
     return b;
 }
 
-uint64_t mulSat(uint64_t a, uint64_t b)
-{
-    if (a == 0 || b == 0)
-        return 0;
-    return a > UINT64_MAX / b ? UINT64_MAX : a * b;
-}
-
-/* chooseMicroSize, src/bucket.cpp:354-377 */
-uint32_t chooseMicroSize(const uint32_t dims[3], uint64_t maxSplit, uint64_t numSplats, uint64_t maxSplats, uint32_t maxCells)
-{
-    uint32_t microSize = 1;
-    auto blocks = [&]()
-    {
-        uint64_t b = 1;
-        for (int i = 0; i < 3; i++)
-            b = mulSat(b, divUp(dims[i], microSize));
-        return b;
-    };
-    uint64_t microBlocks = blocks();
-    const double target = 0.5 * std::min(std::min(dims[0], dims[1]), dims[2]) * std::sqrt((double) maxSplats / (double) numSplats);
-    while (microBlocks > maxSplit || (microBlocks > 8 && microSize < target * 0.5 && (uint64_t) microSize * 2 <= maxCells))
-    {
-        microSize *= 2;
-        microBlocks = blocks();
-    }
-    return microSize;
-}
-
-struct GridBox
-{
-    int32_t lo[3], hi[3];
-    uint32_t cells(int i) const { return (uint32_t) (hi[i] - lo[i]); }
-};
-
 /* device scratch of one recursion depth; a level's sorted member lists must outlive the recursion below it */
 struct DepthBuffers
 {
     DeviceArray<uint32_t> keysA, valsA, keysB, valsB, hist, tileSums;
     uint64_t pairCap = 0;               /* pairs that keysA, valsA, valsB, hist and tileSums are ALL good for */
-    DeviceArray<uint32_t> counts, table, starts, total, scanSums;
+    DeviceArray<uint32_t> counts, table, total, scanSums;
     DeviceArray<uint2> notes;           /* RegionView::packNote of every element of the level being split */
     DeviceArray<uint32_t> slices;       /* bucketCountPrivateKernel's per-workgroup counters */
     /* events of callbacks that still read member lists of this level (mlsgpu_bucket::consumed): whatever overwrites the
@@ -709,144 +660,223 @@ struct Bucketer
             level->readers.clear();
         }
     }
+    DepthBuffers &buffers(uint32_t depth)
+    {
+        while (depthList->size() <= depth)
+            depthList->emplace_back(new DepthBuffers);
+        return *(*depthList)[depth];
+    }
+
+    /* the steps of one level, shared by the two routes below (the host arithmetic is bucketplan.hpp's) */
+    int planOf(const GridBox &grid, uint64_t n, uint32_t chunkCells, uint32_t microCells, LevelPlan *plan);
+    RegionView viewOf(const LevelPlan &plan, const ChunkLayout &C, const GridBox &grid, const mlsgpu_splat *splats, const uint32_t *ids) const;
+    int pickLevel(DepthBuffers &B, const ChunkLayout &C, uint32_t microSize, std::vector<Region> *regions, std::vector<uint32_t> *table);
+    int memberLists(DepthBuffers &B, const RegionView &V, uint64_t n, const std::vector<Region> &regions, uint32_t r0, uint32_t r1,
+                    std::vector<uint32_t> *starts, const uint32_t **members);
+    int recurseRegions(const std::vector<Region> &regions, uint32_t r0, uint32_t r1, uint32_t microSize, const GridBox &sub,
+                       const std::vector<uint32_t> &starts, const uint32_t *members, uint32_t depth, const uint64_t chunk[3]);
+    int emitLeaf(const uint32_t *dIds, uint64_t n, const GridBox &grid, uint32_t depth, const uint64_t chunk[3]);
 
     int recurse(const uint32_t *dIds, uint64_t n, bool isSubset, const GridBox &grid, uint32_t chunkCells, uint32_t microCells,
                 uint32_t depth, const uint64_t chunkIn[3]);
     /* the top level over a splat set that is NOT resident: see mlsgpu_hip_bucket_stream */
     int recurseStream(mlsgpu_fileset *files, uint64_t n, const GridBox &grid, uint64_t budget, uint64_t chunkSplats,
                       uint32_t readerThreads, uint64_t stats[4]);
+
+    /* what the two C entry points share: route(bucketer, whole grid) does the bucketing */
+    template<typename Route>
+    static int run(mlsgpu_ctx *ctx, const mlsgpu_splat *dSplats, uint64_t numSplats, const mlsgpu_grid *region,
+                   const mlsgpu_bucket_params *params, mlsgpu_bucket_fn fn, void *user, uint64_t *cellSplats, Route route)
+    {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        std::shared_ptr<void> &cached = ctx->scratchCache["bucket"];
+        if (!cached)
+            cached = std::shared_ptr<void>(new DepthList, [](void *p) { delete static_cast<DepthList *>(p); });
+        Bucketer b;
+        b.depthList = static_cast<DepthList *>(cached.get());
+        b.ctx = ctx;
+        b.dSplats = dSplats;
+        b.numSplats = numSplats;
+        b.full = *region;
+        b.P = *params;
+        b.fn = fn;
+        b.user = user;
+        GridBox g;
+        for (int i = 0; i < 3; i++)
+        {
+            g.lo[i] = region->extents[2 * i];
+            g.hi[i] = region->extents[2 * i + 1];
+        }
+        const int rc = route(b, g);
+        if (cellSplats != nullptr)
+            *cellSplats = b.cellSplats;
+        b.settleReaders();
+        (void) hipStreamSynchronize(ctx->stream);
+        return rc;
+    }
 };
+
+/* the level's geometry; a grid of one cell cannot be split */
+int Bucketer::planOf(const GridBox &grid, uint64_t n, uint32_t chunkCells, uint32_t microCells, LevelPlan *plan)
+{
+    const uint32_t cellDims[3] = {grid.cells(0), grid.cells(1), grid.cells(2)};
+    if (std::max(std::max(cellDims[0], cellDims[1]), cellDims[2]) == 1)
+    {
+        cellSplats = n;
+        return setError(MLSGPU_ERR_DENSITY, "Too many splats covering one cell (%llu)", (unsigned long long) n);
+    }
+    REQUIRE(planLevel(cellDims, n, P, chunkCells, microCells, plan), MLSGPU_ERR_LENGTH);    /* macroLevels <= MAX_LEVELS */
+    return MLSGPU_OK;
+}
+
+RegionView Bucketer::viewOf(const LevelPlan &plan, const ChunkLayout &C, const GridBox &grid, const mlsgpu_splat *splats,
+                            const uint32_t *ids) const
+{
+    RegionView V;
+    V.splats = splats;
+    V.ids = ids;
+    V.invSpacing = 1.0f / full.spacing;
+    V.setMicroSize(plan.microSize);
+    for (int i = 0; i < 3; i++)
+    {
+        V.ref[i] = full.reference[i];
+        V.first[i] = grid.lo[i];
+        V.bias[i] = (int32_t) C.bias[i];
+        V.dims[i] = C.dims[i];
+    }
+    return V;
+}
+
+/* The chunk's counters come to the host, which picks the regions from them (same traversal as the reference, so regions are
+ * numbered alike) and sends their table back.  The upload is not waited for: `table` lives with the caller. */
+int Bucketer::pickLevel(DepthBuffers &B, const ChunkLayout &C, uint32_t microSize, std::vector<Region> *regions,
+                        std::vector<uint32_t> *table)
+{
+    std::vector<uint32_t> counts(C.totalNodes);
+    HIP_CHECK(hipMemcpyAsync(counts.data(), B.counts, C.totalNodes * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    REQUIRE(pickRegions(counts.data(), C.L, C.dims, microSize, P.maxCells, P.maxSplats, regions, table), MLSGPU_ERR_LENGTH);
+    if (!regions->empty())
+        HIP_CHECK(hipMemcpyAsync(B.table, table->data(), (size_t) C.n0 * 4, hipMemcpyHostToDevice, ctx->stream));
+    return MLSGPU_OK;
+}
+
+/* The member lists of regions [r0, r1) among the n elements of V, ids ascending: region r's is
+ * members[starts[r - r0] .. starts[r - r0 + 1]).  A region's counter is the number of splats that join it -- the length of
+ * its member list: the lists' starts and the pair total are known here, without a word from the device.  The (region, id)
+ * pairs are counted by a 32-bit scan and addressed by 32-bit positions (10^9 uniform splats in 252-cell regions: 1.06 * 10^9). */
+int Bucketer::memberLists(DepthBuffers &B, const RegionView &V, uint64_t n, const std::vector<Region> &regions, uint32_t r0,
+                          uint32_t r1, std::vector<uint32_t> *starts, const uint32_t **members)
+{
+    const uint32_t numRegions = r1 - r0;
+    starts->assign(numRegions + 1, 0);
+    uint64_t pairs = 0;
+    for (uint32_t r = 0; r < numRegions; r++)
+    {
+        (*starts)[r] = (uint32_t) pairs;
+        pairs += regions[r0 + r].count;
+        REQUIRE(pairs < 0xFFFFFFFFull, MLSGPU_ERR_LENGTH);
+    }
+    (*starts)[numRegions] = (uint32_t) pairs;
+    const uint32_t totalPairs = (uint32_t) pairs;
+
+    const RegionCountIn in{V, B.table, r0, r1};
+    PROPAGATE(B.scanSums.reserve(scanTiles(n)));
+    uint32_t *tileSums = B.scanSums;
+    PROPAGATE(B.reservePairs(totalPairs));
+    PROPAGATE((scanPhase1<uint32_t, RegionCountIn>(ctx, "bucket.members.time", in, n, 0u, tileSums, B.total)));
+    PROPAGATE((scanPhase2<uint32_t, RegionCountIn, RegionEmitOut>(ctx, "bucket.members.time", in,
+                                                                RegionEmitOut{V, B.table, B.keysA, B.valsA, r0, r1}, n,
+                                                                (const uint32_t *) tileSums)));
+    SortResult<uint32_t> sorted{B.keysA, B.valsA};
+    /* one digit (region numbers of up to 10 bits) leaves the values in valsB and needs no sorted keys at all;
+     * more digits ping-pong the keys, so both key buffers exist then */
+    const uint32_t regionBits = bitsForCount(numRegions);
+    const bool oneDigit = regionBits <= SortCaps<uint32_t>::MAX_DIGIT_BITS && getenv("MLSGPU_HIP_SORT_DIGIT_BITS") == nullptr;
+    if (!oneDigit)
+        PROPAGATE(B.keysB.reserve(B.pairCap));
+    PROPAGATE(radixSort<uint32_t>(ctx, "bucket.members.time", B.keysA, B.valsA, B.keysB, B.valsB, totalPairs,
+                                  regionBits, false, B.hist, B.tileSums, &sorted, nullptr, 0, false));
+    /* the callbacks may read the lists from any stream */
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    *members = sorted.vals;
+    return MLSGPU_OK;
+}
+
+/* doCallbacks, src/bucket_impl.h:258-294: into each region (depth first, in region order) with its member list */
+int Bucketer::recurseRegions(const std::vector<Region> &regions, uint32_t r0, uint32_t r1, uint32_t microSize, const GridBox &sub,
+                             const std::vector<uint32_t> &starts, const uint32_t *members, uint32_t depth, const uint64_t chunk[3])
+{
+    for (uint32_t r = r0; r < r1; r++)
+        PROPAGATE(recurse(members + starts[r - r0], starts[r - r0 + 1] - starts[r - r0], true, regionBox(regions[r], microSize, sub),
+                          0, 0, depth, chunk));
+    return MLSGPU_OK;
+}
+
+int Bucketer::emitLeaf(const uint32_t *dIds, uint64_t n, const GridBox &grid, uint32_t depth, const uint64_t chunk[3])
+{
+    mlsgpu_bucket b;
+    for (int i = 0; i < 3; i++)
+    {
+        b.extents[2 * i] = grid.lo[i];
+        b.extents[2 * i + 1] = grid.hi[i];
+        b.chunk[i] = chunk[i];
+    }
+    b.depth = depth;
+    b.numSplats = n;
+    b.dIds = dIds;
+    b.dSplats = dSplats;
+    void *consumed = nullptr;
+    b.consumed = &consumed;
+    const int rc = fn(user, ctx, &b);
+    if (rc != 0)
+        return setError(MLSGPU_ERR_CALLBACK, "bucket callback failed with %d", rc);
+    /* the list lives in the buffers of the level above (a leaf at depth 0 is the caller's own list) */
+    if (consumed != nullptr && depth > 0 && depth - 1 < depthList->size())
+        (*depthList)[depth - 1]->readers.push_back(static_cast<hipEvent_t>(consumed));
+    return MLSGPU_OK;
+}
+
+/* the coarsest levels that fit bucketCountKernel's LDS table together (levels are stored finest first) */
+uint32_t ldsLevelsFrom(const ChunkLayout &C)
+{
+    uint32_t ldsFrom = C.L.levels;
+    while (ldsFrom > 0 && C.totalNodes - C.L.offset[ldsFrom - 1] <= LDS_NODES)
+        ldsFrom--;
+    return ldsFrom;
+}
 
 /* bucketRecurse, src/bucket_impl.h:439-560 */
 int Bucketer::recurse(const uint32_t *dIds, uint64_t n, bool isSubset, const GridBox &grid, uint32_t chunkCells,
                       uint32_t microCells, uint32_t depth, const uint64_t chunkIn[3])
 {
-    uint32_t cellDims[3];
-    for (int i = 0; i < 3; i++)
-        cellDims[i] = grid.cells(i);
-    const uint32_t maxCellDim = std::max(std::max(cellDims[0], cellDims[1]), cellDims[2]);
+    const uint32_t maxCellDim = std::max(std::max(grid.cells(0), grid.cells(1)), grid.cells(2));
     if (isSubset && n <= P.maxSplats && maxCellDim <= P.maxCells && (chunkCells == 0 || chunkCells >= maxCellDim))
-    {
-        mlsgpu_bucket b;
-        for (int i = 0; i < 3; i++)
-        {
-            b.extents[2 * i] = grid.lo[i];
-            b.extents[2 * i + 1] = grid.hi[i];
-            b.chunk[i] = chunkIn[i];
-        }
-        b.depth = depth;
-        b.numSplats = n;
-        b.dIds = dIds;
-        b.dSplats = dSplats;
-        void *consumed = nullptr;
-        b.consumed = &consumed;
-        const int rc = fn(user, ctx, &b);
-        if (rc != 0)
-            return setError(MLSGPU_ERR_CALLBACK, "bucket callback failed with %d", rc);
-        /* the list lives in the buffers of the level above (a leaf at depth 0 is the caller's own list) */
-        if (consumed != nullptr && depth > 0 && depth - 1 < depthList->size())
-            (*depthList)[depth - 1]->readers.push_back(static_cast<hipEvent_t>(consumed));
-        return MLSGPU_OK;
-    }
-    if (maxCellDim == 1)
-    {
-        cellSplats = n;
-        return setError(MLSGPU_ERR_DENSITY, "Too many splats covering one cell (%llu)", (unsigned long long) n);
-    }
-    uint32_t microSize = microCells;
-    if (microSize == 0 || microSize > maxCellDim)
-        microSize = chooseMicroSize(cellDims, P.maxSplit, n, P.maxSplats, P.maxCells);
-    while (true)
-    {
-        uint64_t microBlocks = 1;
-        for (int i = 0; i < 3; i++)
-            microBlocks = mulSat(microBlocks, divUp(cellDims[i], microSize));
-        if (microBlocks <= P.maxSplit)
-            break;
-        microSize *= 2;
-    }
-    if (chunkCells == 0)
-        chunkCells = maxCellDim;
-    else
-        chunkCells = std::min(maxCellDim, chunkCells);
-    if (chunkCells > P.maxCells)
-    {
-        uint64_t grain = (uint64_t) P.maxCells / microSize * microSize;
-        if (grain == 0)
-            grain = microSize;
-        chunkCells = (uint32_t) ((chunkCells + grain - 1) / grain * grain);
-    }
-    else
-        chunkCells = roundUp(chunkCells, microSize);
-    uint32_t chunks[3];
-    for (int i = 0; i < 3; i++)
-        chunks[i] = divUp(cellDims[i], chunkCells);
-    uint32_t macroLevels = 1;
-    while (((uint64_t) microSize << (macroLevels - 1)) < chunkCells)
-        macroLevels++;
-    REQUIRE(macroLevels <= MAX_LEVELS, MLSGPU_ERR_LENGTH);
-    const uint32_t chunkRatio = chunkCells / microSize;
-
-    while (depthList->size() <= depth)
-        depthList->emplace_back(new DepthBuffers);
-    DepthBuffers &B = *(*depthList)[depth];
+        return emitLeaf(dIds, n, grid, depth, chunkIn);
+    LevelPlan plan;
+    PROPAGATE(planOf(grid, n, chunkCells, microCells, &plan));
+    DepthBuffers &B = buffers(depth);
 
     /* chunks x-major as the callbacks of bucket_impl.h:548-553; the chunks' states are independent */
-    for (uint32_t cx = 0; cx < chunks[0]; cx++)
-        for (uint32_t cy = 0; cy < chunks[1]; cy++)
-            for (uint32_t cz = 0; cz < chunks[2]; cz++)
+    for (uint32_t cx = 0; cx < plan.chunks[0]; cx++)
+        for (uint32_t cy = 0; cy < plan.chunks[1]; cy++)
+            for (uint32_t cz = 0; cz < plan.chunks[2]; cz++)
             {
                 const uint32_t cc[3] = {cx, cy, cz};
-                GridBox sub;            /* BucketStateSet, src/bucket.cpp:304-331 */
-                for (int i = 0; i < 3; i++)
-                {
-                    const int64_t off = (int64_t) cc[i] * chunkCells;
-                    sub.lo[i] = (int32_t) (grid.lo[i] + off);
-                    sub.hi[i] = (int32_t) std::min<int64_t>(grid.lo[i] + off + chunkCells, grid.hi[i]);
-                }
-                RegionView V;
-                V.splats = dSplats;
-                V.ids = dIds;
-                V.invSpacing = 1.0f / full.spacing;
-                V.setMicroSize(microSize);
-                LevelLayout L;
-                L.levels = macroLevels;
-                for (int i = 0; i < 3; i++)
-                {
-                    V.ref[i] = full.reference[i];
-                    V.first[i] = grid.lo[i];
-                    V.bias[i] = (int32_t) (cc[i] * chunkRatio);
-                    V.dims[i] = divUp(sub.cells(i), microSize);
-                }
-                uint64_t totalNodes = 0;
-                for (uint32_t l = 0; l < macroLevels; l++)
-                {
-                    L.offset[l] = (uint32_t) totalNodes;
-                    uint64_t t = 1;
-                    for (int i = 0; i < 3; i++)
-                    {
-                        L.dims[l][i] = divUp(V.dims[i], (uint64_t) 1 << l);
-                        t *= L.dims[l][i];
-                    }
-                    totalNodes += t;
-                    REQUIRE(totalNodes <= (1u << 24), MLSGPU_ERR_LENGTH);      /* dense counters; the reference hashes */
-                }
-                L.offset[macroLevels] = (uint32_t) totalNodes;
-                const uint32_t n0 = V.dims[0] * V.dims[1] * V.dims[2];
-                PROPAGATE(B.reserveNodes(totalNodes));
+                ChunkLayout C;
+                REQUIRE(layoutChunk(plan, grid, cc, &C), MLSGPU_ERR_LENGTH);       /* dense counters; the reference hashes */
+                RegionView V = viewOf(plan, C, grid, dSplats, dIds);
+                PROPAGATE(B.reserveNodes(C.totalNodes));
                 /* the level's buffers are about to be overwritten: behind the callbacks that still read its lists */
                 for (hipEvent_t ev : B.readers)
                     HIP_CHECK(hipStreamWaitEvent(ctx->stream, ev, 0));
                 B.readers.clear();
                 /* 1. counts */
-                HIP_CHECK(hipMemsetAsync(B.counts, 0, totalNodes * 4, ctx->stream));
+                HIP_CHECK(hipMemsetAsync(B.counts, 0, C.totalNodes * 4, ctx->stream));
                 if (n > 0)
                 {
                     const uint32_t blocks = (uint32_t) std::min<uint64_t>(divUp(n, 256), 4096);
-                    /* the coarsest levels that fit the LDS table together (levels are stored finest first) */
-                    uint32_t ldsFrom = L.levels;
-                    while (ldsFrom > 0 && totalNodes - L.offset[ldsFrom - 1] <= LDS_NODES)
-                        ldsFrom--;
+                    const uint32_t ldsFrom = ldsLevelsFrom(C);
                     /* what the passes behind the count need of an element, kept by the count (RegionView::packNote) */
                     uint2 *notes = nullptr;
                     if (n >= notesFrom() && std::max(std::max(V.dims[0], V.dims[1]), V.dims[2]) <= 65536u)
@@ -856,9 +886,9 @@ int Bucketer::recurse(const uint32_t *dIds, uint64_t n, bool isSubset, const Gri
                         notes = B.notes;
                     }
                     /* private counters (bucketCountPrivateKernel): a big level whose finest counters miss the LDS table */
-                    const uint32_t words0 = (n0 + 1) / 2, imageWords = words0 + (uint32_t) (totalNodes - n0);
+                    const uint32_t words0 = (C.n0 + 1) / 2, imageWords = words0 + (uint32_t) (C.totalNodes - C.n0);
                     const uint64_t numSlices = divUp(n, (uint64_t) PRIV_SPAN);
-                    bool privateCounters = (ldsFrom > 0 || privateFrom() == 0) && macroLevels >= 2 && n >= privateFrom()
+                    bool privateCounters = (ldsFrom > 0 || privateFrom() == 0) && plan.macroLevels >= 2 && n >= privateFrom()
                         && (uint64_t) imageWords * 4 <= PRIV_LDS_BYTES && numSlices < (1u << 24);
                     if (privateCounters && B.slices.reserve(numSlices * imageWords) != MLSGPU_OK)
                     {
@@ -870,114 +900,28 @@ int Bucketer::recurse(const uint32_t *dIds, uint64_t n, bool isSubset, const Gri
                         HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(bucketCountPrivateKernel),
                                                       hipFuncAttributeMaxDynamicSharedMemorySize, PRIV_LDS_BYTES));
                         LAUNCH_LDS(ctx, "bucket.count.time", bucketCountPrivateKernel, dim3((uint32_t) numSlices), dim3(PRIV_THREADS),
-                                   imageWords * 4, V, L, B.slices, n, notes, words0, imageWords);
+                                   imageWords * 4, V, C.L, B.slices, n, notes, words0, imageWords);
                         LAUNCH(ctx, "bucket.count.time", bucketSliceSumKernel, dim3(divUp(imageWords, 256), (uint32_t) divUp(numSlices, (uint64_t) SLICE_GROUP)),
-                               dim3(256), (const uint32_t *) B.slices, (uint32_t) numSlices, words0, imageWords, n0, B.counts);
-                        LAUNCH(ctx, "bucket.count.time", bucketUpsweepKernel, dim3(1), dim3(1024), L, B.counts);
+                               dim3(256), (const uint32_t *) B.slices, (uint32_t) numSlices, words0, imageWords, C.n0, B.counts);
+                        LAUNCH(ctx, "bucket.count.time", bucketUpsweepKernel, dim3(1), dim3(1024), C.L, B.counts);
                     }
                     else
-                        LAUNCH(ctx, "bucket.count.time", bucketCountKernel, dim3(blocks), dim3(256), V, L, B.counts, n, ldsFrom, notes);
+                        LAUNCH(ctx, "bucket.count.time", bucketCountKernel, dim3(blocks), dim3(256), V, C.L, B.counts, n, ldsFrom, notes);
                     V.notes = notes;
                 }
-                std::vector<uint32_t> counts(totalNodes);
-                HIP_CHECK(hipMemcpyAsync(counts.data(), B.counts, totalNodes * 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_CHECK(hipStreamSynchronize(ctx->stream));
-
-                /* 2. pickNodes (src/bucket.cpp:248-269, PickNodes :333-352): depth-first, children x fastest */
-                struct Region { uint32_t c[3]; uint32_t level; };
+                /* 2. regions */
                 std::vector<Region> regions;
-                std::vector<uint32_t> table(n0, 0);
-                struct Frame { uint32_t c[3]; uint32_t level; };
-                std::vector<Frame> stack;
-                stack.push_back(Frame{{0, 0, 0}, macroLevels - 1});
-                while (!stack.empty())
-                {
-                    const Frame f = stack.back();
-                    stack.pop_back();
-                    const uint32_t count = counts[L.offset[f.level] + (f.c[2] * L.dims[f.level][1] + f.c[1]) * L.dims[f.level][0] + f.c[0]];
-                    if (count == 0)
-                        continue;
-                    if (f.level == 0 || (((uint64_t) microSize << f.level) <= P.maxCells && count <= P.maxSplats))
-                    {
-                        const uint32_t id = (uint32_t) regions.size();
-                        REQUIRE(id < (1u << 27), MLSGPU_ERR_LENGTH);
-                        regions.push_back(Region{{f.c[0], f.c[1], f.c[2]}, f.level});
-                        for (uint32_t z = f.c[2] << f.level; z < std::min(V.dims[2], (f.c[2] + 1) << f.level); z++)
-                            for (uint32_t y = f.c[1] << f.level; y < std::min(V.dims[1], (f.c[1] + 1) << f.level); y++)
-                                for (uint32_t x = f.c[0] << f.level; x < std::min(V.dims[0], (f.c[0] + 1) << f.level); x++)
-                                    table[(z * V.dims[1] + y) * V.dims[0] + x] = (id << 5) | f.level;
-                        continue;
-                    }
-                    for (int idx = 7; idx >= 0; idx--)     /* pushed in reverse so that child 0 is visited first */
-                    {
-                        const Frame ch{{f.c[0] * 2 + (idx & 1), f.c[1] * 2 + ((idx >> 1) & 1), f.c[2] * 2 + (uint32_t) (idx >> 2)}, f.level - 1};
-                        bool inside = true;
-                        for (int j = 0; j < 3; j++)
-                            if (((uint64_t) ch.c[j] << ch.level) >= V.dims[j])
-                                inside = false;
-                        if (inside)
-                            stack.push_back(ch);
-                    }
-                }
+                std::vector<uint32_t> table;
+                PROPAGATE(pickLevel(B, C, plan.microSize, &regions, &table));
                 if (regions.empty())
                     continue;
-                const uint32_t numRegions = (uint32_t) regions.size();
-                /* a region's counter is the number of splats that join it -- the length of its member list: the lists' starts
-                 * and the level's pair total are known here, without a word from the device.  The (region, id) pairs are
-                 * counted by a 32-bit scan and addressed by 32-bit positions (10^9 uniform splats in 252-cell regions:
-                 * 1.06 * 10^9) */
-                std::vector<uint32_t> starts(numRegions + 1, 0);
-                {
-                    uint64_t pairs = 0;
-                    for (uint32_t r = 0; r < numRegions; r++)
-                    {
-                        const Region &g = regions[r];
-                        starts[r] = (uint32_t) pairs;
-                        pairs += counts[L.offset[g.level] + (g.c[2] * L.dims[g.level][1] + g.c[1]) * L.dims[g.level][0] + g.c[0]];
-                        REQUIRE(pairs < 0xFFFFFFFFull, MLSGPU_ERR_LENGTH);
-                    }
-                    starts[numRegions] = (uint32_t) pairs;
-                }
-                const uint32_t totalPairs = starts[numRegions];
-                HIP_CHECK(hipMemcpyAsync(B.table, table.data(), (size_t) n0 * 4, hipMemcpyHostToDevice, ctx->stream));
-
                 /* 3. member lists */
-                const RegionCountIn in{V, B.table};
-                PROPAGATE(B.scanSums.reserve(scanTiles(n)));
-                uint32_t *tileSums = B.scanSums;
-                PROPAGATE(B.reservePairs(totalPairs));
-                PROPAGATE((scanPhase1<uint32_t, RegionCountIn>(ctx, "bucket.members.time", in, n, 0u, tileSums, B.total)));
-                PROPAGATE((scanPhase2<uint32_t, RegionCountIn, RegionEmitOut>(ctx, "bucket.members.time", in,
-                                                                            RegionEmitOut{V, B.table, B.keysA, B.valsA}, n,
-                                                                            (const uint32_t *) tileSums)));
-                SortResult<uint32_t> sorted{B.keysA, B.valsA};
-                /* one digit (region numbers of up to 10 bits) leaves the values in valsB and needs no sorted keys at all;
-                 * more digits ping-pong the keys, so both key buffers exist then */
-                const uint32_t regionBits = bitsForCount(numRegions);
-                const bool oneDigit = regionBits <= SortCaps<uint32_t>::MAX_DIGIT_BITS && getenv("MLSGPU_HIP_SORT_DIGIT_BITS") == nullptr;
-                if (!oneDigit)
-                    PROPAGATE(B.keysB.reserve(B.pairCap));
-                PROPAGATE(radixSort<uint32_t>(ctx, "bucket.members.time", B.keysA, B.valsA, B.keysB, B.valsB, totalPairs,
-                                              regionBits, false, B.hist, B.tileSums, &sorted, nullptr, 0, false));
-                /* the callbacks may read the lists from any stream */
-                HIP_CHECK(hipStreamSynchronize(ctx->stream));
-
-                /* 4. doCallbacks, src/bucket_impl.h:258-294 */
+                std::vector<uint32_t> starts;
+                const uint32_t *members = nullptr;
+                PROPAGATE(memberLists(B, V, n, regions, 0, (uint32_t) regions.size(), &starts, &members));
+                /* 4. recursion */
                 const uint64_t chunk[3] = {chunkIn[0] + cx, chunkIn[1] + cy, chunkIn[2] + cz};
-                const uint32_t *members = sorted.vals;
-                for (uint32_t r = 0; r < numRegions; r++)
-                {
-                    GridBox child;
-                    for (int i = 0; i < 3; i++)     /* Node::toCells clipped to the grid, src/bucket.cpp:113-122 */
-                    {
-                        const uint64_t lower = std::min<uint64_t>(((uint64_t) microSize * regions[r].c[i]) << regions[r].level, sub.cells(i));
-                        const uint64_t upper = std::min<uint64_t>((((uint64_t) microSize * regions[r].c[i]) << regions[r].level)
-                                                                  + ((uint64_t) microSize << regions[r].level), sub.cells(i));
-                        child.lo[i] = (int32_t) (sub.lo[i] + (int64_t) lower);
-                        child.hi[i] = (int32_t) (sub.lo[i] + (int64_t) upper);
-                    }
-                    PROPAGATE(recurse(members + starts[r], starts[r + 1] - starts[r], true, child, 0, 0, depth + 1, chunk));
-                }
+                PROPAGATE(recurseRegions(regions, 0, (uint32_t) regions.size(), plan.microSize, C.sub, starts, members, depth + 1, chunk));
             }
     return MLSGPU_OK;
 }
@@ -992,59 +936,15 @@ int Bucketer::recurse(const uint32_t *dIds, uint64_t n, bool isSubset, const Gri
  *            streamed again, a scan keeps the splats that join a region of the batch and appends them to the batch buffer
  *            IN FILE ORDER, and from there on the batch is a resident cloud: member lists, recursion, callbacks.
  * Region numbering, member order and therefore every bucket are those of the resident path (ids are positions in the
- * batch; mlsgpu_bucket::dSplats says in which array).  Passes over the files: 1 + number of batches.
+ * batch; mlsgpu_bucket::dSplats says in which array).  Passes over the files, per chunk of the grid: 1 + number of batches.
  */
 int Bucketer::recurseStream(mlsgpu_fileset *files, uint64_t n, const GridBox &grid, uint64_t budget, uint64_t chunkSplats,
                             uint32_t readerThreads, uint64_t stats[4])
 {
-    uint32_t cellDims[3];
-    for (int i = 0; i < 3; i++)
-        cellDims[i] = grid.cells(i);
-    const uint32_t maxCellDim = std::max(std::max(cellDims[0], cellDims[1]), cellDims[2]);
-    if (maxCellDim == 1)
-    {
-        cellSplats = n;
-        return setError(MLSGPU_ERR_DENSITY, "Too many splats covering one cell (%llu)", (unsigned long long) n);
-    }
-    /* the level's geometry: as recurse() for the whole set (not a subset: the top level always splits) */
-    uint32_t chunkCells = P.chunkCells;
-    uint32_t microSize = P.microCells;
-    if (microSize == 0 || microSize > maxCellDim)
-        microSize = chooseMicroSize(cellDims, P.maxSplit, n, P.maxSplats, P.maxCells);
-    while (true)
-    {
-        uint64_t microBlocks = 1;
-        for (int i = 0; i < 3; i++)
-            microBlocks = mulSat(microBlocks, divUp(cellDims[i], microSize));
-        if (microBlocks <= P.maxSplit)
-            break;
-        microSize *= 2;
-    }
-    if (chunkCells == 0)
-        chunkCells = maxCellDim;
-    else
-        chunkCells = std::min(maxCellDim, chunkCells);
-    if (chunkCells > P.maxCells)
-    {
-        uint64_t grain = (uint64_t) P.maxCells / microSize * microSize;
-        if (grain == 0)
-            grain = microSize;
-        chunkCells = (uint32_t) ((chunkCells + grain - 1) / grain * grain);
-    }
-    else
-        chunkCells = roundUp(chunkCells, microSize);
-    uint32_t chunks[3];
-    for (int i = 0; i < 3; i++)
-        chunks[i] = divUp(cellDims[i], chunkCells);
-    uint32_t macroLevels = 1;
-    while (((uint64_t) microSize << (macroLevels - 1)) < chunkCells)
-        macroLevels++;
-    REQUIRE(macroLevels <= MAX_LEVELS, MLSGPU_ERR_LENGTH);
-    const uint32_t chunkRatio = chunkCells / microSize;
-
-    while (depthList->size() <= 0)
-        depthList->emplace_back(new DepthBuffers);
-    DepthBuffers &B = *(*depthList)[0];
+    /* the whole set, not a subset: the top level always splits */
+    LevelPlan plan;
+    PROPAGATE(planOf(grid, n, P.chunkCells, P.microCells, &plan));
+    DepthBuffers &B = buffers(0);
 
     /* the chunk in flight, the batch, and two words: splats of the batch so far, splats the last chunk added */
     DeviceArray<mlsgpu_splat> dChunk, dBatch;
@@ -1099,106 +999,32 @@ int Bucketer::recurseStream(mlsgpu_fileset *files, uint64_t n, const GridBox &gr
         return MLSGPU_OK;
     };
 
-    for (uint32_t cx = 0; cx < chunks[0]; cx++)
-        for (uint32_t cy = 0; cy < chunks[1]; cy++)
-            for (uint32_t cz = 0; cz < chunks[2]; cz++)
+    for (uint32_t cx = 0; cx < plan.chunks[0]; cx++)
+        for (uint32_t cy = 0; cy < plan.chunks[1]; cy++)
+            for (uint32_t cz = 0; cz < plan.chunks[2]; cz++)
             {
                 const uint32_t cc[3] = {cx, cy, cz};
-                GridBox sub;
-                for (int i = 0; i < 3; i++)
-                {
-                    const int64_t off = (int64_t) cc[i] * chunkCells;
-                    sub.lo[i] = (int32_t) (grid.lo[i] + off);
-                    sub.hi[i] = (int32_t) std::min<int64_t>(grid.lo[i] + off + chunkCells, grid.hi[i]);
-                }
-                RegionView V;
-                V.splats = dChunk;
-                V.ids = nullptr;
-                V.invSpacing = 1.0f / full.spacing;
-                V.setMicroSize(microSize);
-                LevelLayout L;
-                L.levels = macroLevels;
-                for (int i = 0; i < 3; i++)
-                {
-                    V.ref[i] = full.reference[i];
-                    V.first[i] = grid.lo[i];
-                    V.bias[i] = (int32_t) (cc[i] * chunkRatio);
-                    V.dims[i] = divUp(sub.cells(i), microSize);
-                }
-                uint64_t totalNodes = 0;
-                for (uint32_t l = 0; l < macroLevels; l++)
-                {
-                    L.offset[l] = (uint32_t) totalNodes;
-                    uint64_t t = 1;
-                    for (int i = 0; i < 3; i++)
-                    {
-                        L.dims[l][i] = divUp(V.dims[i], (uint64_t) 1 << l);
-                        t *= L.dims[l][i];
-                    }
-                    totalNodes += t;
-                    REQUIRE(totalNodes <= (1u << 24), MLSGPU_ERR_LENGTH);
-                }
-                L.offset[macroLevels] = (uint32_t) totalNodes;
-                const uint32_t n0 = V.dims[0] * V.dims[1] * V.dims[2];
-                PROPAGATE(B.reserveNodes(totalNodes));
+                ChunkLayout C;
+                REQUIRE(layoutChunk(plan, grid, cc, &C), MLSGPU_ERR_LENGTH);
+                const RegionView V = viewOf(plan, C, grid, dChunk, nullptr);
+                PROPAGATE(B.reserveNodes(C.totalNodes));
                 /* pass 1: the counters of the whole set, chunk after chunk */
-                HIP_CHECK(hipMemsetAsync(B.counts, 0, totalNodes * 4, ctx->stream));
-                uint32_t ldsFrom = L.levels;
-                while (ldsFrom > 0 && totalNodes - L.offset[ldsFrom - 1] <= LDS_NODES)
-                    ldsFrom--;
+                HIP_CHECK(hipMemsetAsync(B.counts, 0, C.totalNodes * 4, ctx->stream));
+                const uint32_t ldsFrom = ldsLevelsFrom(C);
                 PROPAGATE(forEachFileChunk(nullptr, [&](uint64_t cnt) -> int
                 {
                     const uint32_t blocks = (uint32_t) std::min<uint64_t>(divUp(cnt, 256), 4096);
-                    LAUNCH(ctx, "bucket.count.time", bucketCountKernel, dim3(blocks), dim3(256), V, L, B.counts, cnt, ldsFrom, (uint2 *) nullptr);
+                    LAUNCH(ctx, "bucket.count.time", bucketCountKernel, dim3(blocks), dim3(256), V, C.L, B.counts, cnt, ldsFrom, (uint2 *) nullptr);
                     /* the next load overwrites the chunk buffer on another stream-ordered path: finish first */
                     HIP_CHECK(hipStreamSynchronize(ctx->stream));
                     return MLSGPU_OK;
                 }));
-                std::vector<uint32_t> counts(totalNodes);
-                HIP_CHECK(hipMemcpyAsync(counts.data(), B.counts, totalNodes * 4, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_CHECK(hipStreamSynchronize(ctx->stream));
-
-                /* pickNodes (src/bucket.cpp:248-269, PickNodes :333-352): depth-first, children x fastest -- as recurse() */
-                struct Region { uint32_t c[3]; uint32_t level; uint32_t count; };
                 std::vector<Region> regions;
-                std::vector<uint32_t> table(n0, 0);
-                struct Frame { uint32_t c[3]; uint32_t level; };
-                std::vector<Frame> stack;
-                stack.push_back(Frame{{0, 0, 0}, macroLevels - 1});
-                while (!stack.empty())
-                {
-                    const Frame f = stack.back();
-                    stack.pop_back();
-                    const uint32_t count = counts[L.offset[f.level] + (f.c[2] * L.dims[f.level][1] + f.c[1]) * L.dims[f.level][0] + f.c[0]];
-                    if (count == 0)
-                        continue;
-                    if (f.level == 0 || (((uint64_t) microSize << f.level) <= P.maxCells && count <= P.maxSplats))
-                    {
-                        const uint32_t id = (uint32_t) regions.size();
-                        REQUIRE(id < (1u << 27), MLSGPU_ERR_LENGTH);
-                        regions.push_back(Region{{f.c[0], f.c[1], f.c[2]}, f.level, count});
-                        for (uint32_t z = f.c[2] << f.level; z < std::min(V.dims[2], (f.c[2] + 1) << f.level); z++)
-                            for (uint32_t y = f.c[1] << f.level; y < std::min(V.dims[1], (f.c[1] + 1) << f.level); y++)
-                                for (uint32_t x = f.c[0] << f.level; x < std::min(V.dims[0], (f.c[0] + 1) << f.level); x++)
-                                    table[(z * V.dims[1] + y) * V.dims[0] + x] = (id << 5) | f.level;
-                        continue;
-                    }
-                    for (int idx = 7; idx >= 0; idx--)
-                    {
-                        const Frame ch{{f.c[0] * 2 + (idx & 1), f.c[1] * 2 + ((idx >> 1) & 1), f.c[2] * 2 + (uint32_t) (idx >> 2)}, f.level - 1};
-                        bool inside = true;
-                        for (int j = 0; j < 3; j++)
-                            if (((uint64_t) ch.c[j] << ch.level) >= V.dims[j])
-                                inside = false;
-                        if (inside)
-                            stack.push_back(ch);
-                    }
-                }
+                std::vector<uint32_t> table;
+                PROPAGATE(pickLevel(B, C, plan.microSize, &regions, &table));
                 if (regions.empty())
                     continue;
                 const uint32_t numRegions = (uint32_t) regions.size();
-                HIP_CHECK(hipMemcpyAsync(B.table, table.data(), (size_t) n0 * 4, hipMemcpyHostToDevice, ctx->stream));
-                HIP_CHECK(hipStreamSynchronize(ctx->stream));          /* `table` is a local */
 
                 const uint64_t chunk[3] = {cx, cy, cz};
                 for (uint32_t r0 = 0; r0 < numRegions;)
@@ -1223,8 +1049,8 @@ int Bucketer::recurseStream(mlsgpu_fileset *files, uint64_t n, const GridBox &gr
                     for (uint32_t r = r0; r < r1; r++)
                         for (int i = 0; i < 3; i++)
                         {
-                            const int64_t lowerCell = (int64_t) sub.lo[i] + (((int64_t) microSize * regions[r].c[i]) << regions[r].level);
-                            const int64_t upperCell = lowerCell + ((int64_t) microSize << regions[r].level);
+                            const int64_t lowerCell = (int64_t) C.sub.lo[i] + (((int64_t) plan.microSize * regions[r].c[i]) << regions[r].level);
+                            const int64_t upperCell = lowerCell + ((int64_t) plan.microSize << regions[r].level);
                             want[i] = std::min(want[i], full.reference[i] + full.spacing * (float) (lowerCell - 1));
                             want[3 + i] = std::max(want[3 + i], full.reference[i] + full.spacing * (float) (upperCell + 1));
                         }
@@ -1244,51 +1070,15 @@ int Bucketer::recurseStream(mlsgpu_fileset *files, uint64_t n, const GridBox &gr
                     REQUIRE(nb <= budget, MLSGPU_ERR_LENGTH);
                     stats[2] += nb;
 
-                    /* from here the batch is a resident cloud: member lists of regions [r0, r1) and the recursion, as recurse() */
+                    /* from here the batch is a resident cloud: member lists of regions [r0, r1) and the recursion */
                     RegionView VB = V;
                     VB.splats = dBatch;
-                    const uint32_t nr = r1 - r0;
-                    PROPAGATE(B.starts.reserve(nr + 1));
-                    const RegionCountIn in{VB, B.table, r0, r1};
-                    PROPAGATE(B.scanSums.reserve(scanTiles(nb)));
-                    PROPAGATE((scanPhase1<uint32_t, RegionCountIn>(ctx, "bucket.members.time", in, nb, 0u, B.scanSums, B.total)));
-                    uint32_t totalPairs = 0;
-                    HIP_CHECK(hipMemcpyAsync(&totalPairs, B.total, 4, hipMemcpyDeviceToHost, ctx->stream));
-                    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                    PROPAGATE(B.reservePairs(totalPairs));
-                    PROPAGATE(B.keysB.reserve(B.pairCap));
-                    PROPAGATE((scanPhase2<uint32_t, RegionCountIn, RegionEmitOut>(ctx, "bucket.members.time", in,
-                                                                                   RegionEmitOut{VB, B.table, B.keysA, B.valsA, r0, r1}, nb,
-                                                                                   (const uint32_t *) B.scanSums)));
-                    SortResult<uint32_t> sorted{B.keysA, B.valsA};
-                    PROPAGATE(radixSort<uint32_t>(ctx, "bucket.members.time", B.keysA, B.valsA, B.keysB, B.valsB, totalPairs,
-                                                  bitsForCount(nr), false, B.hist, B.tileSums, &sorted));
-                    std::vector<uint32_t> starts(nr + 1, 0);
-                    if (totalPairs > 0)
-                    {
-                        hipLaunchKernelGGL(regionStartsKernel, dim3(divUp(totalPairs, 256)), dim3(256), 0, ctx->stream,
-                                           (const uint32_t *) sorted.keys, (uint64_t) totalPairs, B.starts);
-                        HIP_CHECK(hipMemcpyAsync(starts.data(), B.starts, (size_t) nr * 4, hipMemcpyDeviceToHost, ctx->stream));
-                        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                    }
-                    starts[nr] = totalPairs;
+                    std::vector<uint32_t> starts;
+                    const uint32_t *members = nullptr;
+                    PROPAGATE(memberLists(B, VB, nb, regions, r0, r1, &starts, &members));
                     const mlsgpu_splat *const saved = dSplats;
                     dSplats = dBatch;
-                    int rc = MLSGPU_OK;
-                    const uint32_t *members = sorted.vals;
-                    for (uint32_t r = r0; r < r1 && rc == MLSGPU_OK; r++)
-                    {
-                        GridBox child;
-                        for (int i = 0; i < 3; i++)     /* Node::toCells clipped to the grid, src/bucket.cpp:113-122 */
-                        {
-                            const uint64_t lower = std::min<uint64_t>(((uint64_t) microSize * regions[r].c[i]) << regions[r].level, sub.cells(i));
-                            const uint64_t upper = std::min<uint64_t>((((uint64_t) microSize * regions[r].c[i]) << regions[r].level)
-                                                                      + ((uint64_t) microSize << regions[r].level), sub.cells(i));
-                            child.lo[i] = (int32_t) (sub.lo[i] + (int64_t) lower);
-                            child.hi[i] = (int32_t) (sub.lo[i] + (int64_t) upper);
-                        }
-                        rc = recurse(members + starts[r - r0], starts[r - r0 + 1] - starts[r - r0], true, child, 0, 0, 1, chunk);
-                    }
+                    const int rc = recurseRegions(regions, r0, r1, plan.microSize, C.sub, starts, members, 1, chunk);
                     dSplats = saved;
                     PROPAGATE(rc);
                     /* the batch buffer and this level's member lists are refilled next: behind the callbacks' own reads
@@ -1313,33 +1103,12 @@ MLSGPU_API int mlsgpu_hip_bucket(mlsgpu_ctx *ctx, const mlsgpu_splat *dSplats, u
     REQUIRE(region->spacing > 0.0f && params->maxCells >= 1 && params->maxSplats >= 1 && params->maxSplit >= 8, MLSGPU_ERR_INVALID);
     for (int i = 0; i < 3; i++)
         REQUIRE(region->extents[2 * i] < region->extents[2 * i + 1], MLSGPU_ERR_INVALID);   /* at least one cell per axis */
-    HIP_CHECK(hipSetDevice(ctx->device));
-    std::shared_ptr<void> &cached = ctx->scratchCache["bucket"];
-    if (!cached)
-        cached = std::shared_ptr<void>(new Bucketer::DepthList, [](void *p) { delete static_cast<Bucketer::DepthList *>(p); });
-    Bucketer b;
-    b.depthList = static_cast<Bucketer::DepthList *>(cached.get());
-    b.ctx = ctx;
-    b.dSplats = dSplats;
-    b.numSplats = numSplats;
-    b.full = *region;
-    b.P = *params;
-    b.fn = fn;
-    b.user = user;
-    GridBox g;
-    for (int i = 0; i < 3; i++)
+    return Bucketer::run(ctx, dSplats, numSplats, region, params, fn, user, cellSplats, [&](Bucketer &b, const GridBox &g)
     {
-        g.lo[i] = region->extents[2 * i];
-        g.hi[i] = region->extents[2 * i + 1];
-    }
-    const uint64_t chunk[3] = {0, 0, 0};
-    /* the whole set is not a subset type: the top level always splits (bucket_impl.h:400-418) */
-    const int rc = b.recurse(nullptr, numSplats, false, g, params->chunkCells, params->microCells, 0, chunk);
-    if (cellSplats != nullptr)
-        *cellSplats = b.cellSplats;
-    b.settleReaders();
-    hipStreamSynchronize(ctx->stream);
-    return rc;
+        const uint64_t chunk[3] = {0, 0, 0};
+        /* the whole set is not a subset type: the top level always splits (bucket_impl.h:400-418) */
+        return b.recurse(nullptr, numSplats, false, g, params->chunkCells, params->microCells, 0, chunk);
+    });
 }
 
 /* detail::Bbox of device-resident splats folded into lo / hi (min and max are exact in any order) */
@@ -1459,31 +1228,12 @@ MLSGPU_API int mlsgpu_hip_bucket_stream(mlsgpu_ctx *ctx, mlsgpu_fileset *files, 
     REQUIRE(budgetSplats >= 1 && budgetSplats < 0xFFFFFFFFull && chunkSplats >= 1 && chunkSplats < 0xFFFFFFFFull, MLSGPU_ERR_INVALID);
     for (int i = 0; i < 3; i++)
         REQUIRE(region->extents[2 * i] < region->extents[2 * i + 1], MLSGPU_ERR_INVALID);
-    HIP_CHECK(hipSetDevice(ctx->device));
-    std::shared_ptr<void> &cached = ctx->scratchCache["bucket"];
-    if (!cached)
-        cached = std::shared_ptr<void>(new Bucketer::DepthList, [](void *p) { delete static_cast<Bucketer::DepthList *>(p); });
-    Bucketer b;
-    b.depthList = static_cast<Bucketer::DepthList *>(cached.get());
-    b.ctx = ctx;
-    b.dSplats = nullptr;
-    b.numSplats = mlsgpu_hip_fileset_num_splats(files);
-    b.full = *region;
-    b.P = *params;
-    b.fn = fn;
-    b.user = user;
-    GridBox g;
-    for (int i = 0; i < 3; i++)
+    const uint64_t numSplats = mlsgpu_hip_fileset_num_splats(files);
+    return Bucketer::run(ctx, nullptr, numSplats, region, params, fn, user, cellSplats, [&](Bucketer &b, const GridBox &g)
     {
-        g.lo[i] = region->extents[2 * i];
-        g.hi[i] = region->extents[2 * i + 1];
-    }
-    uint64_t local[4] = {0, 0, 0, 0};
-    const int rc = b.numSplats == 0 ? MLSGPU_OK
-        : b.recurseStream(files, b.numSplats, g, budgetSplats, chunkSplats, readerThreads, stats != nullptr ? stats : local);
-    if (cellSplats != nullptr)
-        *cellSplats = b.cellSplats;
-    b.settleReaders();
-    hipStreamSynchronize(ctx->stream);
-    return rc;
+        uint64_t local[4] = {0, 0, 0, 0};
+        return numSplats == 0 ? MLSGPU_OK
+            : b.recurseStream(files, numSplats, g, budgetSplats, chunkSplats, readerThreads, stats != nullptr ? stats : local);
+    });
 }
+

@@ -242,9 +242,16 @@ def test_cfg5_shape_files_to_welded_mesh(tmp_path):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("budget,chunk,coherent", [(60_000, 25_000, False), (400_000, 64, False), (5_000, 300_000, False),
-                                                  (60_000, 10_000, True)])
-def test_streamed_bucketing_equals_resident(tmp_path, budget, chunk, coherent):
+@pytest.mark.parametrize("budget,chunk,coherent,geometry", [
+    pytest.param(60_000, 25_000, False, None, id="60000-25000-False"), pytest.param(400_000, 64, False, None, id="400000-64-False"),
+    pytest.param(5_000, 300_000, False, None, id="5000-300000-False"), pytest.param(60_000, 10_000, True, None, id="60000-10000-True"),
+    # a grid of several chunks and requested microblock sizes (the CPU oracle: 136 leaves in 27 chunks; 55 leaves in 8 chunks,
+    # the largest top-level region, 14 511 splats, above max_splats and so split again at depth 2)
+    pytest.param(30_000, 25_000, False, dict(chunk_cells=40, micro_cells=8, max_split=1 << 20, chunks=27, leaves=136, depth=1),
+                 id="30000-25000-chunks40-micro8"),
+    pytest.param(20_000, 25_000, False, dict(chunk_cells=57, micro_cells=19, max_split=64, chunks=8, leaves=55, depth=2),
+                 id="20000-25000-chunks57-micro19")])
+def test_streamed_bucketing_equals_resident(tmp_path, budget, chunk, coherent, geometry):
     """mlsgpu_hip_bucket_stream (a splat set that does not fit the device: the files streamed through a chunk buffer, once
     to count and once per batch of top-level regions) makes the buckets mlsgpu_hip_bucket makes of the same set resident --
     extents, order and member splats in file order -- whatever the budget and the chunk size; a budget below the largest
@@ -265,6 +272,9 @@ def test_streamed_bucketing_equals_resident(tmp_path, budget, chunk, coherent):
     reference, _, ext = mb.bounding_grid(ctx, raw, len(fs), spacing, bucket_size)
     assert mb.bounding_grid_files(ctx, fs, spacing, bucket_size, chunk)[2] == ext
     bp = dict(max_splats=12_000, max_cells=bucket_size, chunk_cells=0, micro_cells=0, max_split=1 << 20)
+    expect = dict(chunks=1, leaves=None, depth=None)
+    for key, value in (geometry or {}).items():
+        (expect if key in expect else bp)[key] = value
 
     def gather(store):
         def take(leaf, d_splats, d_ids):
@@ -289,7 +299,11 @@ def test_streamed_bucketing_equals_resident(tmp_path, budget, chunk, coherent):
         [(l["extents"], l["chunk"], l["depth"], l["num_splats"]) for l in resident]
     for a, b in zip(got, want):
         np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
-    assert stats["file_passes"] == 1 + stats["batches"] and stats["batch_splats"] >= len(fs)
+    assert len({tuple(l["chunk"]) for l in leaves}) == expect["chunks"]
+    if geometry is not None:
+        assert (len(leaves), max(l["depth"] for l in leaves)) == (expect["leaves"], expect["depth"])
+    # one pass to count per chunk of the grid, one per batch
+    assert stats["file_passes"] == expect["chunks"] + stats["batches"] and stats["batch_splats"] >= len(fs)
     if budget < len(fs):
         assert stats["batches"] >= 2
     assert (stats["chunks_skipped"] > 0) == coherent
