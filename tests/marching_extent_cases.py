@@ -6,6 +6,7 @@ widths are the ones at which a marching kernel changes what it does (WIDTHS belo
 are one that the triangle-route rule sends by rows (hash noise, over three quarters of the cells occupied) and one that it
 sends by cells (a tube, an eighth).  The oracle's run of a case is computed once and shared (oracle_run)."""
 import functools
+import time
 
 import numpy as np
 
@@ -98,8 +99,9 @@ class Case:
     def memory(self, which):
         """ "ample": the cells of a slice times maxDepth, enough for the volume and no more (the 400 slices used elsewhere
         are gigabytes at these widths); "tight": two slices, at which every case overflows and is split but those that
-        the space of a single slice already holds (the tube on W x 17 x 13: test_marching_extents_oracle.py)."""
-        slices = {"ample": self.dims[2], "tight": 2}[which]
+        the space of a single slice already holds (the tube on W x 17 x 13: test_marching_extents_oracle.py); "floor": one
+        slice, the least the constructor accepts (marching_key_cases.py)."""
+        slices = {"ample": self.dims[2], "tight": 2, "floor": 1}[which]
         return (self.dims[0] - 1) * (self.dims[1] - 1) * MAX_CELL_BYTES * slices
 
 
@@ -153,10 +155,15 @@ BATCHES = {"a": BATCH_A, "b": BATCH_B,
            "a_reversed": BATCH_A[::-1]}                              # the narrow rows-route lane ahead of the wide one
 
 
+ORACLE_SECONDS = {}          # the arguments of _oracle_run: what the run took
+
+
 @functools.lru_cache(maxsize=None)
 def _oracle_run(fn, size, dims, swathe, mesh_memory, key_offset):
+    t = time.perf_counter()
     oracle = ob.MarchingOracle(dims[0], dims[1], dims[2], swathe, mesh_memory, ALIGNMENT)
     batches = oracle.generate(host_generator(fn), size, key_offset)
+    ORACLE_SECONDS[fn, size, dims, swathe, mesh_memory, key_offset] = time.perf_counter() - t
     for b in batches:
         for a in b.values():
             if isinstance(a, np.ndarray):
@@ -165,8 +172,14 @@ def _oracle_run(fn, size, dims, swathe, mesh_memory, key_offset):
 
 
 def oracle_run(case, memory, key_offset=KEY_OFFSET):
-    """(batches, stats) of the oracle on a case with "ample" or "tight" mesh memory; computed once, read-only."""
+    """(batches, stats) of the oracle on a case with "ample", "tight" or "floor" mesh memory; computed once, read-only."""
     return _oracle_run(case.fn, case.size, case.dims, case.swathe, case.memory(memory), tuple(key_offset))
+
+
+def oracle_seconds(case, memory, key_offset=KEY_OFFSET):
+    """What that run took when it was made (not a later look into the cache)"""
+    oracle_run(case, memory, key_offset)
+    return ORACLE_SECONDS[case.fn, case.size, case.dims, case.swathe, case.memory(memory), tuple(key_offset)]
 
 
 def field_array(fn, size):

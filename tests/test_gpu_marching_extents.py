@@ -10,9 +10,10 @@ conditions test_marching_extents_oracle.py asserts on the CPU) put every one of 
 Every run is held to the oracle's run of the same bucket: batches bit for bit (NaN positions compared first, as
 test_gpu_fp64.py does) and the counters.  The device's own output on 2049-long grids is held to float64 as well.
 
-Not covered here: 64-bit weld keys (wideKeys, a key layout of more than 32 bits) need (2 W)(2 H)(2 D) >= 2^32; with mesh
-memory of at least one slice the smallest such grid, 4097 x 4097 x 5, needs a 14.6 GB arena and a 336 MB field, which is no
-test of a few seconds."""
+64-bit weld keys (wideKeys, a key layout of more than 32 bits) are in test_gpu_marching_keys.py.  The layout is bit fields
+plus a flag bit, bitsFor(2 (W - 1)) + bitsFor(2 (H - 1)) + bitsFor(2 (D - 1)) + 1 > 32, not the product (2 W)(2 H)(2 D): a
+side of 2^(b - 2) + 1 corners takes b bits, so the route begins at 2^26 corners, 257 x 257 x 1025 for one; the case there is
+257 x 257 x 1033 (internal vertices with the top bit of the z field), at a mesh-memory floor of 58 MB."""
 import numpy as np
 import pytest
 
