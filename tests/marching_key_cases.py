@@ -23,7 +23,7 @@ MEMORY = "floor"
 
 
 def bits_for(max_value):
-    """bitsFor of marching.hip"""
+    """bitsFor of marchingplan.hpp"""
     b = 1
     while (max_value >> b) != 0:
         b += 1

@@ -107,6 +107,31 @@ def test_regimes_routes_and_welds(ctx, field, width, memory, monkeypatch):
     monkeypatch.delenv("MLSGPU_HIP_TRIANGLES_BY_CELLS", raising=False)
 
 
+@pytest.mark.parametrize("width", (32, 33, 96, 130))
+@pytest.mark.parametrize("field", ["noise", "tube"])
+def test_mask_kernels_agree(ctx, field, width, monkeypatch):
+    """latticeMaskWordKernel (the rule's choice up to nw 64) and latticeMaskKernel (MLSGPU_HIP_LATTICE_MASK_ROWS=1) on the
+    same object, lattice weld, ample memory: both runs equal the oracle's, so the two kernels write the same lattice.  nw 1,
+    2, 3 and 5 are the smallest rows at which they differ in structure: a wave of the word kernel shared by 64, 32, 21 and
+    12 rows of corners, a last word that is nearly empty, the top column in word 0 and in the last word."""
+    monkeypatch.delenv("MLSGPU_HIP_TRIANGLES_BY_CELLS", raising=False)
+    monkeypatch.delenv("MLSGPU_HIP_WELD", raising=False)
+    case = mx.width_case(field, width)
+    assert mx.lattice_words(width) == {32: 1, 33: 2, 96: 3, 130: 5}[width]
+    exp, st = mx.oracle_run(case, "ample")
+    mc = make(ctx, case, "ample")
+    cnt = None
+    for by_rows in (None, "1"):
+        if by_rows is None:
+            monkeypatch.delenv("MLSGPU_HIP_LATTICE_MASK_ROWS", raising=False)
+        else:
+            monkeypatch.setenv("MLSGPU_HIP_LATTICE_MASK_ROWS", by_rows)
+        what = (case, "mask by rows", by_rows)
+        assert_same(generate(ctx, mc, case), exp, what)
+        cnt = assert_counters(mc, st, what, cnt)
+    monkeypatch.delenv("MLSGPU_HIP_LATTICE_MASK_ROWS", raising=False)
+
+
 @pytest.mark.parametrize("memory", MEMORIES)
 @pytest.mark.parametrize("case", mx.EXTENT_CASES, ids=repr)
 def test_tall_deep_and_wide_swathes(ctx, case, memory, monkeypatch):
