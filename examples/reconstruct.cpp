@@ -12,7 +12,7 @@
  *                        prune there); --weld host: every ship-out read back through the pinned circular buffer and welded
  *                        by mlsgpu::hip::OOCMesher on the mesher thread (the reference's route)
  *
- * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--collapse-edges F] [--flip-edges R] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
+ * usage: reconstruct [--devices 0,1,...] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--split-edges F] [--collapse-edges F] [--flip-edges R] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] <in.ply> [more.ply ...] <out.ply>
  *                    <spacing> [smooth=4] [levels=6] [subsampling=3] [prune=0.02] [maxSplats=2097152]
  * (defaults as src/mlsgpu_core.cpp:86-135: --fit-smooth 4, --levels 6, --subsampling 3, --fit-prune 0.02)
  * --check (device weld only): after the write, Manifold::isManifold on every output chunk where it lies, one line each.
@@ -28,6 +28,12 @@
  *   with a repeated directed side are dropped and pinched vertices split (with `pinches`: every umbrella of a vertex becomes a
  *   vertex of its own), so that --check says `manifold yes` -- after --simplify, which can make a chunk non-manifold, and
  *   before --flip-edges, --smooth, --normals and --check; one line with the statistics.
+ * --split-edges F (device weld only, F > 0 in grid spacings): before the write, the edges of every output chunk that are
+ *   longer than F spacings are halved where the chunk lies, the longest side of a triangle first (at most 64 rounds, a chunk
+ *   grows to at most 16 times its triangles): the refine step that gives the fans of --fill-holes and the cells of --simplify
+ *   an even triangle size; with several chunks the seams stay as they are -- after --fill-holes, --simplify and --repair,
+ *   before --collapse-edges, --flip-edges, --smooth, --deviation and --normals; one line with the statistics, the smallest
+ *   triangle quality and the longest edge before and after.
  * --collapse-edges F (device weld only, F > 0 in grid spacings): before the write, the interior edges of every output chunk
  *   that are at most F spacings long are collapsed where the chunk lies (minCos 0.5, at most 64 rounds): a vertex and two
  *   triangles go per edge -- the needles that marching leaves where the surface passes close to a lattice vertex --, the
@@ -41,7 +47,7 @@
  *   where it lies, the vertices on a chunk's boundary held fixed -- after --simplify and --flip-edges when they are given; one line with the
  *   statistics.
  * --deviation D (device weld only, D > 0 in world units): the chunks are kept as the weld left them, and after the last of
- *   --fill-holes, --simplify, --repair, --collapse-edges, --flip-edges and --smooth two lines say how far the output lies from them: `moved`, the output's
+ *   --fill-holes, --simplify, --repair, --split-edges, --collapse-edges, --flip-edges and --smooth two lines say how far the output lies from them: `moved`, the output's
  *   vertices against the kept surface, and `lost`, the kept vertices against the output's surface -- the points within and
  *   beyond D, the largest and the RMS distance, and the distances that 50 % and 90 % of the points within stay under, read
  *   off a histogram of 16 bins.  Without such a stage `moved` is all zeros.
@@ -101,8 +107,8 @@ int main(int argc, char **argv)
     bool simplifyGiven = false, quadricGiven = false, smoothGiven = false, fillGiven = false, repairGiven = false;
     std::uint32_t repairFlags = 0;
     long smoothIterations = 0, fillEdges = 0, flipRounds = 0;
-    bool flipGiven = false, collapseGiven = false;
-    double collapseSpacings = 0.0;
+    bool flipGiven = false, collapseGiven = false, splitGiven = false;
+    double collapseSpacings = 0.0, splitSpacings = 0.0;
     float deviationDistance = 0.0f;
     bool deviationGiven = false, intersectionsGiven = false;
     long compactBits = 0;
@@ -144,6 +150,11 @@ int main(int argc, char **argv)
         {
             flipRounds = atol(argv[++i]);
             flipGiven = true;
+        }
+        else if (a == "--split-edges" && i + 1 < argc)
+        {
+            splitSpacings = atof(argv[++i]);
+            splitGiven = true;
         }
         else if (a == "--collapse-edges" && i + 1 < argc)
         {
@@ -193,7 +204,7 @@ int main(int argc, char **argv)
     }
     if (plys.size() < 2 || rest.empty() || devices.empty())
     {
-        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--collapse-edges F] [--flip-edges R] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
+        std::cerr << "usage: reconstruct [--devices 0,1] [--weld device|host] [--check] [--fill-holes N] [--simplify N | --simplify-quadric N] [--repair [pinches]] [--split-edges F] [--collapse-edges F] [--flip-edges R] [--smooth N] [--deviation D] [--self-intersections] [--compact BITS] [--normals] [--tmp-dir DIR] [--buffer BYTES] [--hbm-splats N] in.ply [more.ply ...] out.ply "
                      "spacing [smooth] [levels] [subsampling] [prune] [maxSplats]\n";
         return 2;
     }
@@ -240,6 +251,16 @@ int main(int argc, char **argv)
     if (flipGiven && hostWeld)
     {
         std::cerr << "--flip-edges needs --weld device: the host welder's output is not on the device\n";
+        return 2;
+    }
+    if (splitGiven && !(splitSpacings > 0.0 && splitSpacings <= std::numeric_limits<float>::max()))
+    {
+        std::cerr << "--split-edges takes a number of grid spacings > 0\n";
+        return 2;
+    }
+    if (splitGiven && hostWeld)
+    {
+        std::cerr << "--split-edges needs --weld device: the host welder's output is not on the device\n";
         return 2;
     }
     if (collapseGiven && !(collapseSpacings > 0.0 && collapseSpacings <= std::numeric_limits<float>::max()))
@@ -362,6 +383,8 @@ int main(int argc, char **argv)
         std::size_t repairedChunks = 0;
         mlsgpu_collapse_stats collapsed = mlsgpu_collapse_stats();
         std::size_t collapsedChunks = 0;
+        mlsgpu_split_stats split = mlsgpu_split_stats();
+        std::size_t splitChunks = 0;
         mlsgpu_flip_stats flipped = mlsgpu_flip_stats();
         std::size_t flippedChunks = 0;
         std::pair<mlsgpu_deviation, mlsgpu_deviation> deviated;
@@ -419,6 +442,11 @@ int main(int argc, char **argv)
             {
                 repaired = deviceMesher.repair(repairFlags);
                 repairedChunks = chunks;
+            }
+            if (splitGiven)
+            {
+                split = deviceMesher.splitEdges(64, splitSpacings * spacing, 16);
+                splitChunks = chunks;
             }
             if (collapseGiven)
             {
@@ -501,6 +529,17 @@ int main(int argc, char **argv)
                         (unsigned long long) repaired.unusedVertices, (unsigned long long) repaired.splitVertices,
                         (unsigned long long) repaired.numVertices, (unsigned long long) repaired.outVertices,
                         (unsigned long long) repaired.numTriangles, (unsigned long long) repaired.outTriangles);
+        if (splitGiven)
+            std::printf("split-edges chunks %zu interior-edges %llu boundary-edges %llu rounds %llu splits %llu boundary %llu "
+                        "long %llu -> %llu blocked %llu limited %llu vertices %llu -> %llu triangles %llu -> %llu "
+                        "min-quality %.9g -> %.9g max-length %.9g -> %.9g\n",
+                        splitChunks, (unsigned long long) split.interiorEdges, (unsigned long long) split.boundaryEdges,
+                        (unsigned long long) split.rounds, (unsigned long long) split.splits, (unsigned long long) split.boundarySplits,
+                        (unsigned long long) split.longBefore, (unsigned long long) split.longAfter,
+                        (unsigned long long) split.blockedAfter, (unsigned long long) split.limited,
+                        (unsigned long long) split.numVertices, (unsigned long long) split.outVertices,
+                        (unsigned long long) split.numTriangles, (unsigned long long) split.outTriangles, split.minQualityBefore,
+                        split.minQualityAfter, std::sqrt(split.maxLengthSqBefore), std::sqrt(split.maxLengthSqAfter));
         if (collapseGiven)
             std::printf("collapse-edges chunks %zu interior-edges %llu fixed %llu rounds %llu collapses %llu short %llu -> %llu "
                         "blocked %llu vertices %llu -> %llu triangles %llu -> %llu min-quality %.9g -> %.9g\n",

@@ -1107,6 +1107,111 @@ int mlsgpu_hip_mesh_collapse_edges(mlsgpu_ctx *ctx, const float *dVertices, uint
 int mlsgpu_hip_mesher_collapse_edges(mlsgpu_mesher *mesher, uint32_t maxRounds, double maxLength, double minCos,
                                      mlsgpu_collapse_stats *stats);
 
+/* ---- long-edge split of a device-resident mesh, with the flips' triangle quality report: the refine step next to collapse,
+ *      flip and smooth.  A fan that caps a hole has spokes as long as the hole's radius and no vertex inside to flip or
+ *      smooth with, and a simplify leaves edges of its cell size; halving every edge above maxLength, longest first, evens
+ *      the sampling out and leaves the surface where it was, piecewise.  The reference has no counterpart.  Deterministic in
+ *      the flips' sense: every floating-point operation below is ONE correctly rounded IEEE double operation on exactly
+ *      converted floats (no contraction), in the order written, every statistic is a count, a minimum or a maximum, and the
+ *      output depends neither on the schedule nor -- up to the order of its rows -- on the order of the triangles or of a
+ *      triangle's corners.  u - v, dot, cross, face and q are those of the flips.  T = maxLength * maxLength.
+ *      1. Participation is step 1 of the flips, decided once on the input: outOfRangeTriangles, degenerateTriangles.  A row
+ *         that takes no part keeps its bits and its place in the output, as in the hole filling.
+ *      2. The SIDES are the directed sides of the participating triangles.  An undirected edge {a, b}, a < b, is INTERIOR
+ *         REGULAR as in step 3 of the flips (exactly one side a -> b, exactly one b -> a, c != d), BOUNDARY if exactly one
+ *         side names it in either direction, and IRREGULAR otherwise.  numEdges, interiorEdges and boundaryEdges are those of
+ *         the first classification.
+ *      3. L2 = dot(pb - pa, pb - pa): a sum of squares in a fixed axis order, the same whichever end is called a.  The edge is
+ *         LONG if L2 > T (never for a NaN).  maxLengthSq* is the largest L2 of all edges, 0 if there is none.
+ *      4. A long edge is SPLITTABLE if it is interior regular or boundary and its two ends are not both pinned, and BLOCKED
+ *         otherwise.  dPinned is NULL or one byte per INPUT vertex (not zero: pinned); a vertex that a split made is never
+ *         pinned.
+ *      5. Order within a triangle: side x comes before side y if L2x > L2y, or if they are equal and x has the smaller
+ *         (lo, hi) pair of vertex numbers.  A triangle's three sides have three different pairs: every participating triangle
+ *         has exactly one FIRST side.
+ *      6. A splittable edge is a CANDIDATE if it is the first side of every triangle that holds it (one for a boundary edge,
+ *         two for an interior one); blocked and short sides are compared like any other.  This is Rivara's longest-edge
+ *         bisection.  Two candidates never share a triangle, so a round needs no arbitration and the order of its splits does
+ *         not matter.  A triangle whose first side is blocked is frozen, and so are the long edges behind it.  The longest
+ *         splittable long edge that is first in its triangles always is a candidate: a round without one is the end.
+ *      7. A round, on V_r vertices and T_r rows.  The candidates are numbered j = 0, 1, ... in ascending (a, b).  Candidate
+ *         j's new vertex is m = V_r + j, at (float) (((double) pa + (double) pb) * 0.5) per coordinate.  With T1 = (a, b, c)
+ *         the triangle that holds a -> b and T2 = (b, a, d) the one that holds b -> a (each up to rotation): in each of
+ *         their rows the corner b becomes m, every other corner stays where it is; the new rows are (m, b, c) for T1 and
+ *         (b, m, d) for T2, at T_r + o_j and behind it, T1's first where both exist, o_j the number of triangles of the
+ *         candidates before j.  A boundary candidate has only one of the two.
+ *      8. Rounds, as step 8 of the flips: the mesh is classified; then, while fewer than maxRounds rounds have run: a round
+ *         without a candidate counts, sets converged = 1 and ends the rounds; otherwise it splits every candidate (rounds
+ *         counts it, splits and boundarySplits its edges) and the mesh is classified again.  maxRounds = 0 is a pure report.
+ *         A mesh in which no triangle takes part has rounds = converged = 1 unless maxRounds = 0.  The limit: a round whose
+ *         new rows would take the mesh above maxOutTriangles != 0, or would break outVertices < 2^32 or
+ *         3 * outTriangles < 2^32, does not run and is not counted: limited = 1, converged = 0, and the rounds end -- a round
+ *         is all or nothing, so the result is that of a call with maxRounds = rounds.  longBefore is the first
+ *         classification's number of long edges; longAfter and blockedAfter are the last one's long and blocked edges.  After
+ *         convergence longAfter - blockedAfter edges are frozen behind a blocked one.
+ *      9. Output.  The V input vertices bit for bit, then the new ones in the order they were made (outVertices); rows
+ *         0 .. T - 1 are the input's rows, or what is left of them, in their places, and the new rows follow in the order
+ *         they were made (outTriangles).  dOutEnds, if not NULL, gets two uint32 per NEW vertex: the ends a < b of the edge
+ *         it halved, in output numbers -- what a caller interpolates normals or colours with.
+ *     10. Quality: q of step 9 of the flips, *Before of the input, *After of the output.
+ *      What follows: no T-junction is ever made; an input that mlsgpu_hip_mesh_topology calls manifold gives an output with
+ *      the same manifold flag, components, boundaries and Euler characteristic, and boundarySplits more boundary edges; after
+ *      convergence without pins and irregular edges maxLengthSqAfter <= T; splitting a converged output again returns it bit
+ *      for bit; scaling the coordinates and maxLength by a power of two scales the output and changes no count (as long as
+ *      nothing leaves the floats' and doubles' normal range). ---- */
+typedef struct mlsgpu_split_stats
+{
+    uint64_t numVertices, numTriangles;
+    uint64_t outOfRangeTriangles;   /* an index >= numVertices */
+    uint64_t degenerateTriangles;   /* in range, two indices equal */
+    uint64_t numEdges;              /* undirected, of the participating triangles */
+    uint64_t interiorEdges;         /* step 2 */
+    uint64_t boundaryEdges;
+    uint64_t rounds, splits, boundarySplits, converged, limited;    /* step 8 */
+    uint64_t longBefore, longAfter, blockedAfter;
+    uint64_t outVertices, outTriangles;                     /* step 9 */
+    double minQualityBefore, minQualityAfter;               /* step 10 */
+    double maxLengthSqBefore, maxLengthSqAfter;             /* step 3 */
+    uint64_t qualityBefore[16], qualityAfter[16];
+} mlsgpu_split_stats;
+#ifdef __cplusplus
+static_assert(sizeof(mlsgpu_split_stats) == 424, "mlsgpu_split_stats is part of the ABI");
+#else
+typedef char mlsgpu_split_stats_size_is_424[sizeof(mlsgpu_split_stats) == 424 ? 1 : -1];
+#endif
+/* numVertices packed float xyz and numTriangles uint32 index triples on ctx's device -> dOutVertices / dOutTriangles (and
+ * dOutEnds, two uint32 per new vertex, or NULL), with room for capVertices / capTriangles rows (dOutEnds: capVertices -
+ * numVertices pairs); no overlap with the inputs, which are left alone.  The capacity rule and the size query are
+ * mlsgpu_hip_mesh_repair's: MLSGPU_ERR_LENGTH, with *stats complete and the outputs untouched, if a capacity is below
+ * outVertices / outTriangles -- NULL outputs with zero capacities ask for the sizes (and come back MLSGPU_OK if the result is
+ * empty).  MLSGPU_ERR_INVALID, before anything touches the device, unless maxLength is finite and > 0, stats is not NULL and
+ * maxOutTriangles is 0 or >= numTriangles; MLSGPU_ERR_INVALID for a coordinate that is not finite (counted on the device).
+ * MLSGPU_ERR_LENGTH, before anything is allocated, unless numVertices < 2^32 and 3 * numTriangles < 2^32.  No vertices or no
+ * triangles is not an error.  Scratch is allocated for the call, grows with the mesh (to at least twice its room whenever a
+ * round needs more, by a device-to-device copy, with both copies held while it is made) and is freed on return: per triangle
+ * of that room 84 bytes (three side records: the two sides of the sort's 64-bit keys and 32-bit values 72 -- the side the sort
+ * leaves free holds the rows a record's split adds and the places of its edge's two sides --, the row's working copy 12), per
+ * vertex 12 bytes (the position's working copy) and 8 per new vertex (its ends), the sort's histogram and the scan's tile
+ * sums; MLSGPU_ERR_NOMEM if the device does not have it.  Blocks until the statistics are there: one stream synchronisation
+ * per classification, to read its counts -- rounds + 1 of them, or rounds where the last round had no candidate or the limit
+ * ended them --, one behind each copy of a growing array, one for the sizes and one behind the output. */
+int mlsgpu_hip_mesh_split_edges(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices, const uint32_t *dTriangles,
+                                uint64_t numTriangles, uint32_t maxRounds, double maxLength, uint64_t maxOutTriangles,
+                                const uint8_t *dPinned, float *dOutVertices, uint64_t capVertices, uint32_t *dOutTriangles,
+                                uint64_t capTriangles, uint32_t *dOutEnds, mlsgpu_split_stats *stats);
+/* The same for every output chunk of a finalized device sink, on the mesher's context, by the route of
+ * mlsgpu_hip_mesher_fill_holes: every chunk is sized first and then split into new arrays, each chunk behind the one before,
+ * and the new generation takes the old one's place only when all chunks are done -- an error leaves the results as they
+ * were.  The chunks' normals are dropped.  A chunk's limit is maxGrowth times its triangles; 0 means none.  Chunks are split
+ * INDEPENDENTLY.  With more than one chunk a vertex that another chunk has too is pinned, as for the hole filling: an edge of
+ * the seam has both ends pinned and is blocked in both chunks, so the seams stay closed bit for bit.  The price is a band of
+ * frozen long edges along a seam: they are counted in blockedAfter and longAfter.  *stats: the counts and histograms summed
+ * over the chunks, rounds the largest, converged the AND over the chunks that have triangles (without one: as for a mesh
+ * without triangles), limited the OR, the two minima the minima and the two maxima the maxima over them.
+ * MLSGPU_ERR_INVALID before finalize and unless maxLength is finite and > 0; may be called again. */
+int mlsgpu_hip_mesher_split_edges(mlsgpu_mesher *mesher, uint32_t maxRounds, double maxLength, uint32_t maxGrowth,
+                                  mlsgpu_split_stats *stats);
+
 /* ---- hole filling of a device-resident mesh: every small boundary loop is capped by a fan of triangles to the mean of its
  *      vertices, before the mesh crosses the link.  An MLS surface stops where the splats get sparse, and
  *      mlsgpu_hip_mesh_topology counts the holes that leaves (numBoundaries); this closes them.  The reference has no

@@ -7,8 +7,9 @@ fallback: importing :mod:`mlsgpu_amd.binding` without the built library raises.
 """
 from .binding import (BucketFarm, CollapseStats, CompactStats, Context, DensityError, Deviation, DeviceBuffer, FillStats, FlipStats, FormatError, HipError, HostMesher, InvalidArgument, LengthError, Marching, Mesher, MlsError,
                       MlsFunctor, NormalsStats, REPAIR_SPLIT_PINCHES, RepairStats, SPLAT_DTYPE, SelfIntersections, SimplifyQuadricStats, SimplifyStats, SmoothStats, SplatTree, Swathe, Topology, Worker, WorkerConfig, lib, library_path, compact_decode, compact_info, mesh_collapse_edges, mesh_compact, mesh_deviation, mesh_fill_holes, mesh_flip_edges,
-                      mesh_normals, mesh_repair, mesh_self_intersections, mesh_simplify, mesh_simplify_quadric, mesh_smooth, mesh_topology, mesher_deviation, mesher_fill_holes, mesher_repair, mesher_self_intersections)
+                      mesh_normals, mesh_repair, mesh_self_intersections, mesh_simplify, mesh_simplify_quadric, mesh_smooth, mesh_split_edges, mesh_topology, mesher_deviation, mesher_fill_holes, mesher_repair, mesher_self_intersections)
+from .split_stats import SplitStats
 
 __all__ = ["BucketFarm", "CollapseStats", "CompactStats", "Context", "DensityError", "Deviation", "DeviceBuffer", "FillStats", "FlipStats", "FormatError", "HipError", "HostMesher", "InvalidArgument", "LengthError", "Marching", "Mesher", "MlsError",
-           "MlsFunctor", "NormalsStats", "REPAIR_SPLIT_PINCHES", "RepairStats", "SPLAT_DTYPE", "SelfIntersections", "SimplifyQuadricStats", "SimplifyStats", "SmoothStats", "SplatTree", "Swathe", "Topology", "Worker", "WorkerConfig", "lib", "library_path", "compact_decode", "compact_info", "mesh_collapse_edges", "mesh_compact", "mesh_deviation", "mesh_fill_holes", "mesh_flip_edges",
-           "mesh_normals", "mesh_repair", "mesh_self_intersections", "mesh_simplify", "mesh_simplify_quadric", "mesh_smooth", "mesh_topology", "mesher_deviation", "mesher_fill_holes", "mesher_repair", "mesher_self_intersections"]
+           "MlsFunctor", "NormalsStats", "REPAIR_SPLIT_PINCHES", "RepairStats", "SPLAT_DTYPE", "SelfIntersections", "SimplifyQuadricStats", "SimplifyStats", "SmoothStats", "SplatTree", "SplitStats", "Swathe", "Topology", "Worker", "WorkerConfig", "lib", "library_path", "compact_decode", "compact_info", "mesh_collapse_edges", "mesh_compact", "mesh_deviation", "mesh_fill_holes", "mesh_flip_edges",
+           "mesh_normals", "mesh_repair", "mesh_self_intersections", "mesh_simplify", "mesh_simplify_quadric", "mesh_smooth", "mesh_split_edges", "mesh_topology", "mesher_deviation", "mesher_fill_holes", "mesher_repair", "mesher_self_intersections"]

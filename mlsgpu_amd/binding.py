@@ -462,6 +462,9 @@ def lib():
     sig("mlsgpu_hip_mesh_collapse_edges", C.c_int, vp, vp, u64, vp, u64, u32, C.c_double, C.c_double, vp, u64, vp, u64, vp,
         P(CollapseStats))
     sig("mlsgpu_hip_mesher_collapse_edges", C.c_int, vp, u32, C.c_double, C.c_double, P(CollapseStats))
+    # the statistics (split_stats.SplitStats) go by address: byref() is accepted
+    sig("mlsgpu_hip_mesh_split_edges", C.c_int, vp, vp, u64, vp, u64, u32, C.c_double, u64, vp, vp, u64, vp, u64, vp, vp)
+    sig("mlsgpu_hip_mesher_split_edges", C.c_int, vp, u32, C.c_double, u32, vp)
     sig("mlsgpu_hip_mesh_fill_holes", C.c_int, vp, vp, u64, vp, u64, u32, vp, vp, u64, vp, u64, P(FillStats))
     sig("mlsgpu_hip_mesher_fill_holes", C.c_int, vp, u32, P(FillStats))
     sig("mlsgpu_hip_mesh_repair", C.c_int, vp, vp, u64, vp, u64, u32, vp, u64, vp, u64, vp, P(RepairStats))
@@ -1035,6 +1038,17 @@ class Mesher:
         check(lib().mlsgpu_hip_mesher_collapse_edges(self.h, int(max_rounds), float(max_length), float(min_cos), C.byref(st)))
         return st.as_dict()
 
+    def split_edges(self, max_rounds, max_length, max_growth=0):
+        """Every output chunk of the finalized sink with its edges above max_length halved, longest first (mesh_split_edges);
+        a chunk stops before the round that would take it above max_growth times its triangles (0: no limit), and with
+        several chunks the seams are pinned and stay closed.  The chunks grow into new arrays: addresses from an earlier
+        chunk() are gone.  Returns the statistics: counts and histograms summed over the chunks, rounds the largest, converged
+        the AND, limited the OR, the minima the minima and the maxima the maxima."""
+        from .split_stats import SplitStats
+        st = SplitStats()
+        check(lib().mlsgpu_hip_mesher_split_edges(self.h, int(max_rounds), float(max_length), int(max_growth), C.byref(st)))
+        return st.as_dict()
+
     def smooth(self, iterations, lam=0.5, mu=-0.53, boundary=SMOOTH_BOUNDARY_FIXED):
         """Every output chunk of the finalized sink smoothed in place (mesh_smooth): positions only, the triangles and the
         chunk layout stay.  Returns the statistics: counts summed over the chunks, exponent and maxima the largest."""
@@ -1305,6 +1319,40 @@ def mesh_collapse_edges(ctx, vertices, triangles, max_rounds, max_length, min_co
         dt, nt = S.triples(triangles, np.uint32, num_triangles)
         args = (ctx.h, _ptr(dv), nv, _ptr(dt), nt, int(max_rounds), float(max_length), float(min_cos))
         return _size_then_write(S, lib().mlsgpu_hip_mesh_collapse_edges, args, CollapseStats(), True, with_source)
+
+
+def mesh_split_edges(ctx, vertices, triangles, max_rounds, max_length, max_out_triangles=0, pinned=None, num_vertices=None,
+                     num_triangles=None):
+    """Long-edge split on the device (mlsgpu_hip_mesh_split_edges), with the triangle quality before and after: every edge
+    above max_length that is the longest side of its triangles is halved, round after round, until none is left, max_rounds
+    have run or the next round would take the mesh above max_out_triangles (0: no limit); an edge with both ends pinned
+    stays.  Bit-reproducible whatever the schedule.  `vertices` / `triangles` are numpy arrays (uploaded for the call) or
+    DeviceBuffers of packed float32 xyz / uint32 triples, which are left alone; `pinned` is None, a numpy array of one flag
+    per vertex or a DeviceBuffer of one byte per vertex.  One call asks for the sizes, a second one writes.  Returns (vertices
+    float32 [V', 3], triangles uint32 [T', 3], statistics as a dict, ends uint32 [V' - V, 2]), the arrays downloaded: the
+    input's rows first, then the new ones, and for every new vertex the two ends of the edge it halved."""
+    from .split_stats import SplitStats
+    st = SplitStats()
+    entry = lib().mlsgpu_hip_mesh_split_edges
+    with _Staging(ctx) as S:
+        dv, nv = S.triples(vertices, np.float32, num_vertices)
+        dt, nt = S.triples(triangles, np.uint32, num_triangles)
+        dp = pinned
+        if pinned is not None and not isinstance(pinned, DeviceBuffer):
+            mask = np.ascontiguousarray(np.asarray(pinned) != 0, np.uint8).reshape(-1)
+            if len(mask) != nv:
+                raise InvalidArgument("pinned has %d entries for %d vertices" % (len(mask), nv))
+            dp = S.upload(mask) if nv else None
+        args = (ctx.h, _ptr(dv), nv, _ptr(dt), nt, int(max_rounds), float(max_length), int(max_out_triangles), _ptr(dp))
+        rc = entry(*args, None, 0, None, 0, None, C.byref(st))
+        if rc != 0 and not (rc == _LENGTH and st.outVertices + st.outTriangles > 0):
+            check(rc)
+        added = st.outVertices - st.numVertices
+        ov, ot, oe = S.out(12 * st.outVertices), S.out(12 * st.outTriangles), S.out(8 * added)
+        if rc != 0:
+            check(entry(*args, _ptr(ov), st.outVertices, _ptr(ot), st.outTriangles, _ptr(oe), C.byref(st)))
+        ends = oe.download(np.uint32, 2 * added).reshape(-1, 2) if oe and added else np.zeros((0, 2), np.uint32)
+        return _rows(ov, np.float32, st.outVertices), _rows(ot, np.uint32, st.outTriangles), st.as_dict(), ends
 
 
 def mesh_fill_holes(ctx, vertices, triangles, max_edges, pinned=None, num_vertices=None, num_triangles=None):

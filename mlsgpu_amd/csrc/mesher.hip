@@ -1257,7 +1257,7 @@ static void accumulate(mlsgpu_smooth_stats &total, const mlsgpu_smooth_stats &on
     total.maxCoordinate = std::max(total.maxCoordinate, one.maxCoordinate);
 }
 
-/* what mlsgpu_flip_stats and mlsgpu_collapse_stats share: the input's counts, the rounds (the most of any chunk, converged if
+/* what mlsgpu_flip_stats, mlsgpu_collapse_stats and mlsgpu_split_stats share: the input's counts, the rounds (the most of any chunk, converged if
  * all did) and the quality report, whose minima have no neutral start value */
 template<typename Stats>
 static void addEdgeRounds(Stats &total, const Stats &one, bool first)
@@ -1300,6 +1300,21 @@ static void accumulate(mlsgpu_collapse_stats &total, const mlsgpu_collapse_stats
     total.outTriangles += one.outTriangles;
     total.minLengthSqBefore = std::min(total.minLengthSqBefore, one.minLengthSqBefore);
     total.minLengthSqAfter = std::min(total.minLengthSqAfter, one.minLengthSqAfter);
+}
+
+static void accumulate(mlsgpu_split_stats &total, const mlsgpu_split_stats &one, bool first)
+{
+    addEdgeRounds(total, one, first);
+    total.boundaryEdges += one.boundaryEdges;
+    total.splits += one.splits;
+    total.boundarySplits += one.boundarySplits;
+    total.limited |= one.limited;
+    total.longBefore += one.longBefore;
+    total.longAfter += one.longAfter;
+    total.outVertices += one.outVertices;
+    total.outTriangles += one.outTriangles;
+    total.maxLengthSqBefore = std::max(total.maxLengthSqBefore, one.maxLengthSqBefore);
+    total.maxLengthSqAfter = std::max(total.maxLengthSqAfter, one.maxLengthSqAfter);
 }
 
 static void accumulate(mlsgpu_fill_stats &total, const mlsgpu_fill_stats &one, bool first)
@@ -1442,7 +1457,7 @@ static int stageInPlace(mlsgpu_mesher *m, Stats *total, Stage stage)
     return MLSGPU_OK;
 }
 
-/* Into a new generation (fill, repair, collapse): the chunks change size and may grow, so they cannot stay where they lie.
+/* Into a new generation (fill, repair, collapse, split): the chunks change size and may grow, so they cannot stay where they lie.
  * stage(chunk, outVertices, vertexCapacity, outTriangles, triangleCapacity, &one) is called twice per chunk: without room
  * at all it stops at its capacity check with the sizes in `one` (MLSGPU_ERR_LENGTH; MLSGPU_OK where it keeps nothing, and is
  * done), then it writes into new arrays, behind the chunk before.  Nothing of the sink changes before the last chunk is done:
@@ -1608,6 +1623,36 @@ MLSGPU_API int mlsgpu_hip_mesher_collapse_edges(mlsgpu_mesher *m, uint32_t maxRo
                                                 mlsgpu_collapse_stats *one) {
         return mlsgpu_hip_mesh_collapse_edges(m->ctx, m->outVertices + 3 * s.v0, s.nv, m->outTriangles + 3 * s.t0, s.nt, maxRounds,
                                               maxLength, minCos, outV, capV, outT, capT, nullptr, one);
+    });
+}
+
+/* Every output chunk that has triangles through mlsgpu_hip_mesh_split_edges (split.hip), into a new generation: the chunks
+ * grow.  The seams are pinned as for the hole filling. */
+MLSGPU_API int mlsgpu_hip_mesher_split_edges(mlsgpu_mesher *m, uint32_t maxRounds, double maxLength, uint32_t maxGrowth,
+                                             mlsgpu_split_stats *stats)
+{
+    REQUIRE(m != nullptr && stats != nullptr, MLSGPU_ERR_INVALID);
+    /* mlsgpu_hip_mesh_split_edges's own check, here so that a refused parameter does no work */
+    REQUIRE(std::isfinite(maxLength) && maxLength > 0.0, MLSGPU_ERR_INVALID);
+    std::lock_guard<std::mutex> lock(m->mutex);
+    REQUIRE(m->finalized, MLSGPU_ERR_INVALID);
+    mlsgpu_ctx *const ctx = m->ctx;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    std::memset(stats, 0, sizeof(*stats));
+    stats->converged = maxRounds > 0 ? 1 : 0;       /* the AND over the chunks starts where a mesh without triangles ends */
+    /* the seams: with several chunks, a vertex that another chunk has too is pinned */
+    DeviceArray<uint8_t> pinned;
+    if (m->outChunks.size() > 1)
+    {
+        const size_t nc = m->chunkVStart.size() - 1;    /* finalize sized the tables: [chunks + 1] */
+        PROPAGATE(pinned.alloc(m->chunkVStart[nc]));
+        PROPAGATE(seamMask(ctx, m->outVertices, m->chunkVStart[nc], m->chunkVStart.data(), (uint32_t) nc, pinned));
+    }
+    return stageIntoNewGeneration(m, stats, [&](const Span &s, float *outV, uint64_t capV, uint32_t *outT, uint64_t capT,
+                                                mlsgpu_split_stats *one) {
+        return mlsgpu_hip_mesh_split_edges(ctx, m->outVertices + 3 * s.v0, s.nv, m->outTriangles + 3 * s.t0, s.nt, maxRounds, maxLength,
+                                           (uint64_t) maxGrowth * s.nt, pinned.get() != nullptr ? pinned + s.v0 : nullptr, outV, capV,
+                                           outT, capT, nullptr, one);
     });
 }
 

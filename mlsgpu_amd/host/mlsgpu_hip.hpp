@@ -297,6 +297,25 @@ inline mlsgpu_collapse_stats collapseEdges(const Context &ctx, const Buffer<floa
     return *s;
 }
 
+/// Long-edge split of a mesh in device memory, with its quality report (mlsgpu_hip_mesh_split_edges): every edge above
+/// maxLength that is the longest side of its triangles is halved, round after round; maxOutTriangles (0: none) stops the
+/// rounds before the one that would pass it, pinned is NULL or one byte per input vertex.  outVertices / outTriangles have
+/// room for capVertices / capTriangles and do not overlap the inputs; outEnds is NULL or gets the two ends of every new
+/// vertex's edge.  With too little room (NULL and 0 ask for the sizes) nothing is written, *st is complete and
+/// std::length_error is thrown.
+inline mlsgpu_split_stats splitEdges(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
+                                     const Buffer<std::uint32_t> &triangles, std::uint64_t numTriangles, std::uint32_t maxRounds,
+                                     double maxLength, std::uint64_t maxOutTriangles, const std::uint8_t *pinned, float *outVertices,
+                                     std::uint64_t capVertices, std::uint32_t *outTriangles, std::uint64_t capTriangles,
+                                     std::uint32_t *outEnds = NULL, mlsgpu_split_stats *st = NULL)
+{
+    mlsgpu_split_stats own;
+    mlsgpu_split_stats *const s = st != NULL ? st : &own;
+    check(mlsgpu_hip_mesh_split_edges(ctx.get(), vertices.get(), numVertices, triangles.get(), numTriangles, maxRounds, maxLength,
+                                      maxOutTriangles, pinned, outVertices, capVertices, outTriangles, capTriangles, outEnds, s));
+    return *s;
+}
+
 /// Area-weighted vertex normals of a mesh in device memory (mlsgpu_hip_mesh_normals): outNormals has room for 3 floats per
 /// vertex and does not overlap the inputs.
 inline mlsgpu_normals_stats normals(const Context &ctx, const Buffer<float> &vertices, std::uint64_t numVertices,
@@ -863,6 +882,17 @@ public:
     {
         mlsgpu_collapse_stats st;
         check(mlsgpu_hip_mesher_collapse_edges(h, maxRounds, maxLength, minCos, &st));
+        return st;
+    }
+    /// Every output chunk of the finalized mesher with its edges above maxLength halved, longest first
+    /// (mlsgpu_hip_mesher_split_edges): behind fillHoles(), simplify() and repair(), before collapseEdges(), flipEdges() and
+    /// smooth().  A chunk stops before the round that would take it above maxGrowth times its triangles (0: no limit).  The
+    /// chunks grow into new arrays; with several chunks the seams are pinned and keep their bits.  Counts and histograms summed
+    /// over the chunks, rounds the largest, converged the AND, limited the OR, the minima the minima, the maxima the maxima.
+    mlsgpu_split_stats splitEdges(std::uint32_t maxRounds, double maxLength, std::uint32_t maxGrowth = 0)
+    {
+        mlsgpu_split_stats st;
+        check(mlsgpu_hip_mesher_split_edges(h, maxRounds, maxLength, maxGrowth, &st));
         return st;
     }
     /// Every output chunk of the finalized mesher through at most maxRounds rounds of Delaunay edge flips, in place
