@@ -1378,7 +1378,10 @@ static void addDeviation(mlsgpu_deviation *total, const mlsgpu_deviation &one, u
 /* The three routes.  Each is for the holder of the lock of a finalized sink, after the entry point has checked the stage's
  * parameters (a refused parameter costs no results) and preset *total; each hands every dense chunk that has triangles to
  * `stage`, which calls the mesh function on the chunk where it lies, and folds what it reports into *total.  A chunk without
- * triangles has no output (finalize), is skipped and keeps nothing. */
+ * triangles has no output (finalize) and is skipped.  The two routes that write the chunks anew (to the front, into a new
+ * generation) keep nothing of it; the in-place route leaves it alone, so vertices that finalize kept in it (welded to another
+ * chunk's component) stay until a stage of the other two routes runs.  Until then the seam mask and the deviation report,
+ * which walk the dense chunks, see them. */
 
 /* To the front (simplify): stage(chunk, outVertices, outTriangles, &one) writes into buffers of the largest chunk's size, and from
  * there the result goes to the front of the output arrays: it is never larger than its chunk, so chunk c's lands at or before
@@ -1431,8 +1434,8 @@ static int simplifyChunks(mlsgpu_mesher *m, Stats *total, Stage stage)
     return MLSGPU_OK;
 }
 
-/* In place (smooth, flip): stage(chunk, &one) writes over the chunk.  A failure costs the results: earlier chunks are changed
- * already, and the one that failed holds what it reached. */
+/* In place (smooth, flip): stage(chunk, &one) writes over the chunk; a chunk without triangles stays as it is, vertices
+ * included.  A failure costs the results: earlier chunks are changed already, and the one that failed holds what it reached. */
 template<typename Stats, typename Stage>
 static int stageInPlace(mlsgpu_mesher *m, Stats *total, Stage stage)
 {
