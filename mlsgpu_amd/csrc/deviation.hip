@@ -5,34 +5,26 @@
  * every field of the report a count, a minimum, a maximum or an integer sum: the result depends neither on the schedule nor on
  * anything below that the contract does not name -- the grid's cell size least of all.
  *
- *   extent     over the coordinates of the points and of the target: those that are not finite, and the target's bounding box
- *                                                                                                        -- one read-back --
- *   classify   over the triangles: which take no part (step 1), and the fixed-point sum of the bounding-box extents of the
- *              others, whose mean sizes the first cell                                                   -- one read-back --
- *   count      a thread per triangle: the cells its box, inflated by D, touches.  The host doubles the cell size and counts
- *              again until the pairs fit their budget                                          -- one read-back per size --
- *   emit       a scan over the counts, then a thread per triangle writes its (cell key, triangle) pairs
- *   sort       the pairs by cell key; the points, with their own cell's key, by that key too
+ *   grid       the target's triangles that take part (step 1), each in the cells its box, inflated by D, touches, as
+ *              (cell key, triangle) pairs sorted by cell key: meshgrid.hpp, with reach = D
+ *   sort       the points, with their own cell's key, by that key too
  *   distance   over the sorted points: the point's cell's run of pairs by binary search, step 2 and step 3 for each of them,
  *              (best, triangle) as a lexicographic minimum in registers -- one lane per point, or a power of two of
  *              neighbouring lanes that share the run and combine by shuffles: step 4 needs no atomics
  *   report     over the points' results: the counts, the histogram, the fixed-point sum and the maximum; then the lowest
  *              point that attains the maximum                                                            -- one read-back --
  *
- * Why a point needs only its own cell.  cell(x) = clamp(floor((x - origin) / h), 0, n - 1) is three correctly rounded, monotone
- * steps, hence monotone in x.  A triangle goes into every cell from cell(lo - D) to cell(hi + D) per axis, with the SAME rounded
- * doubles lo - D and hi + D that step 2 compares with.  For a candidate pair lo - D <= p <= hi + D, so cell(lo - D) <= cell(p)
- * <= cell(hi + D) on every axis: the pair is among those of the point's cell, whatever h and the origin are.  The kernel applies
- * step 2 to every pair it is handed, so a superset is all it needs.
- *
- * An index >= V is compared and counted, never used as an address; no address depends on a coordinate except through cell(),
- * which is clamped to the grid.
+ * Why a point needs only its own cell.  cell() is monotone (meshgrid.hpp), and a triangle goes into every cell from
+ * cell(lo - D) to cell(hi + D) per axis, with the SAME rounded doubles lo - D and hi + D that step 2 compares with.  For a
+ * candidate pair lo - D <= p <= hi + D, so cell(lo - D) <= cell(p) <= cell(hi + D) on every axis: the pair is among those of
+ * the point's cell, whatever h and the origin are.  The kernel applies step 2 to every pair it is handed, so a superset is all
+ * it needs.
  *
  * Scratch belongs to the call: 24 bytes per point (the two sides of the sort's 64-bit keys and 32-bit values), 8 more where the
  * caller does not take the distances, 8 bytes per triangle (its cell count and where its pairs begin), 24 bytes per grid pair,
  * the sorts' histograms (4 KB per 4096 records) and the scan's tile sums.  The pairs are at most max(2^20, 8 T).
  */
-#include "meshpost.hpp"
+#include "meshgrid.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -44,65 +36,24 @@ namespace
 
 enum
 {
-    C_BAD_POINTS = 0,           /* point coordinates that are not finite */
-    C_BAD_VERTICES = 1,         /* target coordinates that are not finite */
-    C_OUT_OF_RANGE = 2,
-    C_DEGENERATE = 3,
-    C_LIVE = 4,                 /* triangles that take part */
-    C_EXTENT = 5,               /* the fixed-point sum of their extents */
-    C_PAIRS = 6,                /* the pairs of the last count */
-    C_BOX_MIN = 7,              /* 3: the smallest target coordinate per axis, as ordered bits */
-    C_BOX_MAX = 10,             /* 3: the largest */
-    C_WITHIN = 13,
-    C_BEYOND = 14,
-    C_HISTOGRAM = 15,           /* 16 */
-    C_SUM_Q = 31,
-    C_MAX_D2 = 32,              /* the bits of the largest distance */
-    C_FARTHEST = 33,
-    C_HANDED = 34,              /* a timed call: the pairs the distance kernel was handed, and ... */
-    C_CANDIDATES = 35,          /* ... those of them that passed step 2 */
-    C_FARTHEST_TIES = 36,       /* the points that attain the maximum (tally() counts what it finds the first of) */
-    C_WORDS = 37
+    C_BAD_POINTS = G_WORDS,     /* point coordinates that are not finite */
+    C_WITHIN,
+    C_BEYOND,
+    C_HISTOGRAM,                /* 16 */
+    C_SUM_Q = C_HISTOGRAM + 16,
+    C_MAX_D2,                   /* the bits of the largest distance */
+    C_FARTHEST,
+    C_HANDED,                   /* a timed call: the pairs the distance kernel was handed, and ... */
+    C_CANDIDATES,               /* ... those of them that passed step 2 */
+    C_FARTHEST_TIES,            /* the points that attain the maximum (tally() counts what it finds the first of) */
+    C_WORDS
 };
+
+const GridNames NAMES = {"mesh deviation", "pairs", "kernel.deviation.extent", "kernel.deviation.classify", "kernel.deviation.count",
+                         "kernel.deviation.scan", "kernel.deviation.emit", "kernel.deviation.sort", "deviation.pairs", "deviation.cellsize"};
 
 const uint32_t NO_TRIANGLE = 0xFFFFFFFFu;
-const uint64_t MIN_PAIR_BUDGET = uint64_t(1) << 20;
-const uint32_t PAIRS_PER_TRIANGLE = 8;          /* the budget: what the pairs may cost per triangle of the target */
-const uint32_t CELL_CAP = 1u << 21;             /* cells per axis: simplify's 21 bits */
 const uint64_t SPREAD_THREADS = uint64_t(1) << 20;      /* a point's run is dealt out to several lanes below this many lanes in all */
-const int WAVE_LANES = 64;
-const uint32_t EXTENT_BITS = 20;                /* a triangle's extent as a fraction of the box's, in the classify sum */
-
-/* floats to integers of the same order (and back): what atomicMin / atomicMax take */
-__host__ __device__ inline uint32_t orderedBits(uint32_t bits) { return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u); }
-inline float fromOrdered(uint32_t o)
-{
-    const uint32_t bits = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-    float f;
-    std::memcpy(&f, &bits, sizeof(f));
-    return f;
-}
-
-/* The sparse grid: cell (x, y, z) has the key z << (bx + by) | y << bx | x, the axes as wide as their cell counts need. */
-struct Grid
-{
-    double origin[3];           /* the target's box, lowered by D */
-    double h;
-    uint32_t n[3];              /* cells per axis, each >= 1 and <= CELL_CAP */
-    uint32_t shiftY, shiftZ;
-    double D;
-
-    /* monotone in x: one subtraction, one division, floor, clamp */
-    __device__ __forceinline__ uint32_t cell(int axis, double x) const
-    {
-        const double c = floor((x - origin[axis]) / h);
-        return (uint32_t) fmin(fmax(c, 0.0), (double) (n[axis] - 1));
-    }
-    __device__ __forceinline__ uint64_t key(uint32_t x, uint32_t y, uint32_t z) const
-    {
-        return (uint64_t) z << shiftZ | (uint64_t) y << shiftY | x;
-    }
-};
 
 struct Corners
 {
@@ -180,151 +131,6 @@ __device__ __forceinline__ double distance2(const D3 &p, const Corners &T)
 }
 
 /* ---------------------------------------------------------------- kernels */
-
-/* A workgroup loops over the 3 P point coordinates, then over the 3 V target coordinates, and sends once: the counts of
- * those that are not finite and, of the finite target coordinates, the box. */
-__global__ __launch_bounds__(256) void extentKernel(const float *points, uint64_t numPointCoordinates, const float *vertices,
-                                                    uint64_t numVertexCoordinates, Counter *counters)
-{
-    __shared__ GroupCounts<2, 6> totals;
-    totals.clear();
-    const int at[8] = {C_BAD_POINTS, C_BAD_VERTICES, C_BOX_MAX, C_BOX_MAX + 1, C_BOX_MAX + 2, C_BOX_MIN, C_BOX_MIN + 1, C_BOX_MIN + 2};
-    const uint64_t first = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x, stride = (uint64_t) gridDim.x * blockDim.x;
-    uint32_t badPoints = 0, badVertices = 0;
-    for (uint64_t i = first; i < numPointCoordinates; i += stride)
-        badPoints += isfinite(points[i]) ? 0u : 1u;
-    /* the smallest is kept as the largest of the complements, which GroupCounts' maxima hold; 0 = none seen (the ordered bits
-     * of a finite float are neither 0 nor all ones) */
-    uint32_t most[3] = {0, 0, 0}, least[3] = {0, 0, 0};
-    for (uint64_t i = first; i < numVertexCoordinates; i += stride)
-    {
-        const float x = vertices[i];
-        const bool ok = isfinite(x);
-        badVertices += ok ? 0u : 1u;
-        const uint32_t o = orderedBits(__float_as_uint(x)), axis = (uint32_t) (i % 3);
-#pragma unroll
-        for (uint32_t k = 0; k < 3; k++)
-            if (ok && axis == k)
-            {
-                most[k] = max(most[k], o);
-                least[k] = max(least[k], ~o);
-            }
-    }
-    totals.add(0, badPoints);
-    totals.add(1, badVertices);
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-    {
-        totals.raise(k, most[k]);
-        totals.raise(3 + k, least[k]);
-    }
-    totals.flush(counters, at);
-}
-
-/* Step 1, and the sum of the extents (the longest side of a live triangle's box, as a fraction of `scale`'s unit) that sizes
- * the first cell.  A workgroup loops and sends once; the extents go through one 64-bit atomic per wave. */
-__global__ __launch_bounds__(256) void classifyKernel(const float *vertices, uint64_t numVertices, const uint32_t *tri, uint64_t numTriangles,
-                                                      double scale, Counter *counters)
-{
-    __shared__ GroupCounts<3> totals;
-    totals.clear();
-    const int at[3] = {C_OUT_OF_RANGE, C_DEGENERATE, C_LIVE};
-    uint32_t outOfRange = 0, degenerate = 0, live = 0;
-    long long extents = 0;
-    for (uint64_t t = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; t < numTriangles; t += (uint64_t) gridDim.x * blockDim.x)
-    {
-        const uint64_t i[3] = {tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]};
-        const TriangleDefect d = defectOf(i, numVertices);
-        outOfRange += d.outOfRange ? 1u : 0u;
-        degenerate += d.degenerate ? 1u : 0u;
-        if (!d.none())
-            continue;
-        live++;
-        const Corners T = cornersOf(vertices, tri, t);
-        double extent = 0.0;
-#pragma unroll
-        for (int x = 0; x < 3; x++)
-        {
-            double from, to;
-            reachOf(T, x, 0.0, &from, &to);
-            extent = fmax(extent, to - from);
-        }
-        extents += (long long) fmin(extent * scale, (double) (1u << (EXTENT_BITS + 1)));
-    }
-    totals.add(0, outOfRange);
-    totals.add(1, degenerate);
-    totals.add(2, live);
-    const long long ofWave = waveSum64(extents);
-    if (laneId() == 0 && ofWave != 0)
-        atomicAdd(&counters[C_EXTENT], (Counter) ofWave);
-    totals.flush(counters, at);
-}
-
-/* the cells of triangle t per axis, first and last; false for a triangle that takes no part */
-__device__ __forceinline__ bool cellsOf(const Grid &G, const float *vertices, uint64_t numVertices, const uint32_t *tri, uint64_t t,
-                                        uint32_t first[3], uint32_t last[3])
-{
-    const uint64_t i[3] = {tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]};
-    if (!defectOf(i, numVertices).none())
-        return false;
-    const Corners T = cornersOf(vertices, tri, t);
-#pragma unroll
-    for (int x = 0; x < 3; x++)
-    {
-        double from, to;
-        reachOf(T, x, G.D, &from, &to);
-        first[x] = G.cell(x, from);
-        last[x] = G.cell(x, to);
-    }
-    return true;
-}
-
-/* How many cells every triangle goes into: at most CELL_CAP^3 = 2^63, kept up to 2^32 (which is beyond every budget).  The
- * total goes through one 64-bit atomic per wave.  Every lane stays to the end. */
-__global__ __launch_bounds__(256) void countKernel(Grid G, const float *vertices, uint64_t numVertices, const uint32_t *tri,
-                                                   uint64_t numTriangles, uint32_t *counts, Counter *counters)
-{
-    long long pairs = 0;
-    for (uint64_t base = (uint64_t) blockIdx.x * blockDim.x; base < numTriangles; base += (uint64_t) gridDim.x * blockDim.x)
-    {
-        const uint64_t t = base + threadIdx.x;
-        if (t >= numTriangles)
-            continue;
-        uint32_t first[3], last[3];
-        uint64_t cells = 0;
-        if (cellsOf(G, vertices, numVertices, tri, t, first, last))
-            cells = (uint64_t) (last[0] - first[0] + 1) * (last[1] - first[1] + 1) * (last[2] - first[2] + 1);
-        cells = min(cells, (uint64_t) 1 << 32);
-        counts[t] = (uint32_t) min(cells, (uint64_t) 0xFFFFFFFFu);
-        pairs += (long long) cells;
-    }
-    const long long ofWave = waveSum64(pairs);
-    if (laneId() == 0 && ofWave != 0)
-        atomicAdd(&counters[C_PAIRS], (Counter) ofWave);
-}
-
-/* The pairs of triangle t, from starts[t] on: counts that passed the budget, so starts[t] + count <= numPairs.  The bound is
- * checked all the same: no store depends on the two kernels agreeing. */
-__global__ __launch_bounds__(256) void emitKernel(Grid G, const float *vertices, uint64_t numVertices, const uint32_t *tri,
-                                                  uint64_t numTriangles, const uint32_t *starts, uint64_t numPairs, uint64_t *keys,
-                                                  uint32_t *vals)
-{
-    const uint64_t t = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= numTriangles)
-        return;
-    uint32_t first[3], last[3];
-    if (!cellsOf(G, vertices, numVertices, tri, t, first, last))
-        return;
-    uint64_t at = starts[t];
-    for (uint32_t z = first[2]; z <= last[2]; z++)
-        for (uint32_t y = first[1]; y <= last[1]; y++)
-            for (uint32_t x = first[0]; x <= last[0]; x++, at++)
-                if (at < numPairs)
-                {
-                    keys[at] = G.key(x, y, z);
-                    vals[at] = (uint32_t) t;
-                }
-}
 
 __global__ __launch_bounds__(256) void pointKeysKernel(Grid G, const float *points, uint64_t numPoints, uint64_t *keys)
 {
@@ -508,26 +314,6 @@ __global__ __launch_bounds__(256) void farthestKernel(const double *distance2In,
     tally(hit, &counters[C_FARTHEST_TIES], i, &counters[C_FARTHEST]);
 }
 
-/* the grid of cell size h over [lo, hi] per axis, or false if an axis would need more than CELL_CAP cells */
-bool layGrid(const double lo[3], const double hi[3], double h, double D, Grid *G)
-{
-    G->h = h;
-    G->D = D;
-    uint32_t bits[3];
-    for (int x = 0; x < 3; x++)
-    {
-        G->origin[x] = lo[x];
-        const double cells = std::floor((hi[x] - lo[x]) / h) + 1.0;
-        if (!(cells <= (double) CELL_CAP))
-            return false;
-        G->n[x] = (uint32_t) std::max(cells, 1.0);
-        bits[x] = bitLength(G->n[x] - 1);
-    }
-    G->shiftY = bits[0];
-    G->shiftZ = bits[0] + bits[1];
-    return true;
-}
-
 } // namespace
 
 MLSGPU_API int mlsgpu_hip_mesh_deviation(mlsgpu_ctx *ctx, const float *dPoints, uint64_t numPoints, const float *dVertices,
@@ -557,54 +343,16 @@ MLSGPU_API int mlsgpu_hip_mesh_deviation(mlsgpu_ctx *ctx, const float *dPoints, 
 
     HIP_CHECK(hipSetDevice(ctx->device));
     const dim3 B(256);
-    DeviceArray<Counter> counters;
-    Counter h[C_WORDS];
-    std::memset(h, 0, sizeof(h));
-    PROPAGATE(counters.alloc(C_WORDS));
-    HIP_CHECK(hipMemsetAsync(counters.get(), 0, C_WORDS * sizeof(Counter), ctx->stream));
-    HIP_CHECK(hipMemsetAsync(&counters.get()[C_FARTHEST], 0xFF, sizeof(Counter), ctx->stream));         /* a minimum */
-    const auto readBack = [&]() -> int {
-        HIP_CHECK(hipMemcpyAsync(h, counters.get(), sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        return MLSGPU_OK;
-    };
-
-    if (np > 0 || nv > 0)
-    {
-        LAUNCH(ctx, "kernel.deviation.extent", extentKernel, dim3(std::min(divUp(3 * std::max(np, nv), 256), LOOP_BLOCKS)), B, dPoints, 3 * np,
-               dVertices, 3 * nv, counters.get());
-        PROPAGATE(readBack());
-    }
-    if (h[C_BAD_POINTS] != 0 || h[C_BAD_VERTICES] != 0)
-        return setError(MLSGPU_ERR_INVALID, "mesh deviation: %llu point and %llu target coordinates are not finite", h[C_BAD_POINTS],
-                        h[C_BAD_VERTICES]);
-
-    /* the target's box, inflated by D (no finite coordinate lies outside; without vertices there is no triangle to bin) */
-    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, side = 0.0;
-    if (nv > 0)
-        for (int x = 0; x < 3; x++)
-        {
-            const double least = (double) fromOrdered(~(uint32_t) h[C_BOX_MIN + x]), most = (double) fromOrdered((uint32_t) h[C_BOX_MAX + x]);
-            side = std::max(side, most - least);
-            lo[x] = least - D;
-            hi[x] = most + D;
-        }
-
-    /* a triangle's extent is summed in units of 2^-EXTENT_BITS of the power of two above the box's longest side */
-    uint64_t bitsOfSide;
-    std::memcpy(&bitsOfSide, &side, sizeof(side));
-    const int eSide = side > 0.0 ? exponentOfDoubleBits(bitsOfSide) + 1 : 0;
-    if (nv > 0 && nt > 0)
-    {
-        LAUNCH(ctx, "kernel.deviation.classify", classifyKernel, dim3(std::min(divUp(nt, 256), LOOP_BLOCKS)), B, dVertices, nv, dTriangles, nt,
-               powerOfTwo((int) EXTENT_BITS - eSide), counters.get());
-        PROPAGATE(readBack());
-        out->outOfRangeTriangles = h[C_OUT_OF_RANGE];
-        out->degenerateTriangles = h[C_DEGENERATE];
-    }
-    else
-        out->outOfRangeTriangles = nt;          /* every index is >= 0 vertices */
-    const uint64_t live = h[C_LIVE];
+    CounterBlock counters;
+    PROPAGATE(counters.start(ctx, C_WORDS, {C_FARTHEST}));
+    const std::vector<Counter> &h = counters.h;         /* what the last read-back found */
+    TriangleGrid grid = {ctx, NAMES, counters, dVertices, nv, dTriangles, nt, D};
+    PROPAGATE(grid.measure(dPoints, np, C_BAD_POINTS));
+    if (grid.badPoints != 0 || grid.badVertices != 0)
+        return setError(MLSGPU_ERR_INVALID, "mesh deviation: %llu point and %llu target coordinates are not finite",
+                        (unsigned long long) grid.badPoints, (unsigned long long) grid.badVertices);
+    out->outOfRangeTriangles = grid.outOfRange;
+    out->degenerateTriangles = grid.degenerate;
     if (np == 0)
         return MLSGPU_OK;
 
@@ -614,60 +362,20 @@ MLSGPU_API int mlsgpu_hip_mesh_deviation(mlsgpu_ctx *ctx, const float *dPoints, 
         PROPAGATE(ownDistance2.alloc(np));
         dDistance2 = ownDistance2.get();
     }
-    double scratch = (double) (counters.bytes(C_WORDS) + (ownDistance2.get() != nullptr ? ownDistance2.bytes(np) : 0));
-    SortScratch pairs, sortedPoints;
-    DeviceArray<uint32_t> counts, starts, tileSums;
-    if (live == 0)
+    double scratch = (double) (counters.bytes() + (ownDistance2.get() != nullptr ? ownDistance2.bytes(np) : 0));
+    SortScratch sortedPoints;
+    if (grid.live == 0)
         LAUNCH(ctx, "kernel.deviation.distance", beyondKernel, dim3(divUp(np, 256)), B, np, dDistance2, dNearest);
     else
     {
-        PROPAGATE(counts.alloc(nt));
-        PROPAGATE(starts.alloc(nt));
-        PROPAGATE(tileSums.alloc((uint64_t) scanTiles(nt) + 1));
         PROPAGATE(sortedPoints.alloc(np));
-        /* the first cell: twice D, or the mean extent of a triangle where that is larger; then doubled until every axis has
-         * at most CELL_CAP cells and the pairs fit their budget.  One cell holds every live triangle once: the loop ends. */
-        const uint64_t budget = std::max(MIN_PAIR_BUDGET, (uint64_t) PAIRS_PER_TRIANGLE * live);
-        const double meanExtent = (double) h[C_EXTENT] / (double) live * powerOfTwo(eSide - (int) EXTENT_BITS);
-        double cellSize = std::max(2.0 * D, meanExtent);
-        Grid G;
-        uint64_t numPairs = 0;
-        for (;; cellSize *= 2.0)
-        {
-            if (!std::isfinite(cellSize))
-                return setError(MLSGPU_ERR_LENGTH, "mesh deviation: no cell size brings the grid's pairs under %llu",
-                                (unsigned long long) budget);
-            if (!layGrid(lo, hi, cellSize, D, &G))
-                continue;
-            HIP_CHECK(hipMemsetAsync(&counters.get()[C_PAIRS], 0, sizeof(Counter), ctx->stream));
-            LAUNCH(ctx, "kernel.deviation.count", countKernel, dim3(std::min(divUp(nt, 256), LOOP_BLOCKS)), B, G, dVertices, nv, dTriangles, nt,
-                   counts.get(), counters.get());
-            PROPAGATE(readBack());
-            numPairs = h[C_PAIRS];
-            if (numPairs <= budget)
-                break;
-        }
-        REQUIRE(numPairs >= live && numPairs < (uint64_t(1) << 32), MLSGPU_ERR_LENGTH);
-        PROPAGATE(pairs.alloc(numPairs));
-        scratch += (double) (pairs.bytes() + sortedPoints.bytes() + 2 * counts.bytes(nt) + tileSums.bytes((uint64_t) scanTiles(nt) + 1));
-        if (ctx->timing)
-        {
-            ctx->addValue("deviation.pairs", (double) numPairs);
-            ctx->addValue("deviation.cellsize", cellSize);
-        }
-
-        PROPAGATE((exclusiveScan<uint32_t>(ctx, "kernel.deviation.scan", ArrayIn<uint32_t>{counts.get()}, ArrayOut<uint32_t>{starts.get()}, nt,
-                                           0u, tileSums.get(), (uint32_t *) nullptr)));
-        LAUNCH(ctx, "kernel.deviation.emit", emitKernel, dim3(divUp(nt, 256)), B, G, dVertices, nv, dTriangles, nt,
-               (const uint32_t *) starts.get(), numPairs, pairs.keys(), pairs.vals());
+        PROPAGATE(grid.build(grid.firstCell(), nullptr));
+        scratch += (double) (grid.bytes() + sortedPoints.bytes());
         /* (both sorts under one name: a launch site of the sort keeps one stat id per translation unit) */
-        const uint32_t keyBits = G.shiftZ + bitLength(G.n[2] - 1);
-        SortResult<uint64_t> byCell = {nullptr, nullptr}, pointsByCell = {nullptr, nullptr};
-        PROPAGATE(radixSort<uint64_t>(ctx, "kernel.deviation.sort", pairs.keysA, pairs.valsA, pairs.keysB, pairs.valsB, numPairs, keyBits,
-                                      false, pairs.hist, nullptr, &byCell));
-        LAUNCH(ctx, "kernel.deviation.pointkeys", pointKeysKernel, dim3(divUp(np, 256)), B, G, dPoints, np, sortedPoints.keys());
+        SortResult<uint64_t> pointsByCell = {nullptr, nullptr};
+        LAUNCH(ctx, "kernel.deviation.pointkeys", pointKeysKernel, dim3(divUp(np, 256)), B, grid.G, dPoints, np, sortedPoints.keys());
         PROPAGATE(radixSort<uint64_t>(ctx, "kernel.deviation.sort", sortedPoints.keysA, sortedPoints.valsA, sortedPoints.keysB,
-                                      sortedPoints.valsB, np, keyBits, true, sortedPoints.hist, nullptr, &pointsByCell));
+                                      sortedPoints.valsB, np, grid.G.keyBits(), true, sortedPoints.hist, nullptr, &pointsByCell));
         /* lanes per point: a power of two, as many as keep the launch under SPREAD_THREADS lanes.  (MLSGPU_HIP_DEVIATION_LANES
          * is a tuning aid; the result does not depend on it.) */
         uint32_t laneShift = 0;
@@ -676,22 +384,24 @@ MLSGPU_API int mlsgpu_hip_mesh_deviation(mlsgpu_ctx *ctx, const float *dPoints, 
         if (const char *forced = getenv("MLSGPU_HIP_DEVIATION_LANES"))
         {
             const int lanes = atoi(forced);
-            if (lanes >= 1 && lanes <= WAVE_LANES && (lanes & (lanes - 1)) == 0)
+            if (lanes >= 1 && lanes <= WAVE && (lanes & (lanes - 1)) == 0)
                 laneShift = bitLength((uint64_t) lanes) - 1;
         }
         if (ctx->timing)
             ctx->addValue("deviation.lanes", (double) (1u << laneShift));
         LAUNCH(ctx, "kernel.deviation.distance", distanceKernel, dim3(divUp(np << laneShift, 256)), B, dPoints,
-               (const uint64_t *) pointsByCell.keys, (const uint32_t *) pointsByCell.vals, np, laneShift, dVertices, dTriangles, (const uint64_t *) byCell.keys, (const uint32_t *) byCell.vals,
-               (uint32_t) numPairs, D, dDistance2, dNearest, ctx->timing ? &counters.get()[C_HANDED] : (Counter *) nullptr);
+               (const uint64_t *) pointsByCell.keys, (const uint32_t *) pointsByCell.vals, np, laneShift, dVertices, dTriangles,
+               (const uint64_t *) grid.byCell.keys, (const uint32_t *) grid.byCell.vals, (uint32_t) grid.numRecords, D, dDistance2, dNearest,
+               ctx->timing ? &counters.get()[C_HANDED] : (Counter *) nullptr);
     }
     if (ctx->timing)
         ctx->addValue("deviation.scratch.bytes", scratch);
 
+
     LAUNCH(ctx, "kernel.deviation.report", reportKernel, dim3(std::min(divUp(np, 256), LOOP_BLOCKS)), B, (const double *) dDistance2, np, D2,
            powerOfTwo(30 - e), counters.get());
     LAUNCH(ctx, "kernel.deviation.report", farthestKernel, dim3(divUp(np, 256)), B, (const double *) dDistance2, np, counters.get());
-    PROPAGATE(readBack());      /* the scratch goes with the call */
+    PROPAGATE(counters.readBack(ctx));          /* the scratch goes with the call */
     if (ctx->timing)
     {
         ctx->addValue("deviation.pairs.handed", (double) h[C_HANDED]);

@@ -4,13 +4,8 @@
  * fixes every floating-point operation and makes every field of the report a count, a minimum or a maximum: the result depends
  * neither on the schedule nor on anything below that the contract does not name -- the grid's cell size least of all.
  *
- *   extent     over the coordinates: those that are not finite, and the bounding box               -- one read-back --
- *   classify   over the triangles: which take no part (step 1), and the fixed-point sum of the bounding-box extents of the
- *              others, whose mean sizes the first cell                                              -- one read-back --
- *   count      a thread per triangle: the cells its box touches, and the cell of its lower corner.  The host doubles the cell
- *              size and counts again until the records fit their budget                  -- one read-back per size --
- *   emit       a scan over the counts, then a thread per triangle writes its (cell key, triangle) records
- *   sort       the records by cell key
+ *   grid       the triangles that take part (step 1), each in the cells its box touches, as (cell key, triangle) records
+ *              sorted by cell key: meshgrid.hpp, with reach = 0 and the cell of every triangle's lower corner kept
  *   pairs      over the sorted records: a lane owns record i and meets the later records of the same cell; steps 2 to 5 for
  *              each pair that this cell owns                                                       -- one read-back --
  *   list       (where the caller takes the pairs and they fit) the same walk once more, over the triangles that have a
@@ -18,21 +13,19 @@
  *   report     over the partner counts: the triangles that have one, the maximum; then the lowest triangle that attains it
  *                                                                                                   -- one read-back --
  *
- * Why a pair is met exactly once.  cell(x) = clamp(floor((x - origin) / h), 0, n - 1) is three correctly rounded, monotone
- * steps, hence monotone in x.  A triangle goes into every cell from cell(lo) to cell(hi) per axis.  For a candidate pair
- * loA <= hiB and loB <= hiA, so m = max(cell(loA), cell(loB)) lies within cell(lo) .. cell(hi) of both on every axis: both
- * have a record in cell m, and the pair is looked at there and nowhere else -- no atomics to deduplicate, no second sort.  A
- * pair that is no candidate may meet in m or not at all; step 2 drops it.
+ * Why a pair is met exactly once.  cell() is monotone (meshgrid.hpp), and a triangle goes into every cell from cell(lo) to
+ * cell(hi) per axis.  For a candidate pair loA <= hiB and loB <= hiA, so m = max(cell(loA), cell(loB)) lies within cell(lo) ..
+ * cell(hi) of both on every axis: both have a record in cell m, and the pair is looked at there and nowhere else -- no atomics
+ * to deduplicate, no second sort.  A pair that is no candidate may meet in m or not at all; step 2 drops it.
  *
- * An index >= V is compared and counted, never used as an address: a record's triangle is classified again before its
- * corners are read.  No address depends on a coordinate except through cell(), which is clamped to the grid.
+ * A record's triangle is classified again before its corners are read: an index >= V is never an address here either.
  *
  * Scratch belongs to the call: 16 bytes per triangle (its cell count, where its records begin, the packed cell of its lower
  * corner) and 4 more where the caller does not take the partner counts, 24 bytes per grid record (the two sides of the sort's
  * 64-bit keys and 32-bit values), 24 bytes per crossing pair where the list is written, the sorts' histograms (4 KB per 4096
  * records) and the scan's tile sums.  The records are at most max(2^20, 8 T).
  */
-#include "meshpost.hpp"
+#include "meshgrid.hpp"
 
 #include <cmath>
 #include <cstdlib>
@@ -44,73 +37,26 @@ namespace
 
 enum
 {
-    C_BAD_VERTICES = 0,         /* coordinates that are not finite */
-    C_OUT_OF_RANGE = 1,
-    C_DEGENERATE = 2,
-    C_LIVE = 3,                 /* triangles that take part */
-    C_EXTENT = 4,               /* the fixed-point sum of their extents */
-    C_RECORDS = 5,              /* the records of the last count */
-    C_BOX_MIN = 6,              /* 3: the smallest coordinate per axis, as ordered bits */
-    C_BOX_MAX = 9,              /* 3: the largest */
-    C_CANDIDATES = 12,
-    C_CROSSINGS = 13,
-    C_LOWEST = 14,              /* a minimum: the lowest crossing pair, packed */
-    C_CURSOR = 15,              /* the list pass: pairs appended */
-    C_CROSSING_TRIANGLES = 16,
-    C_MAX_PARTNERS = 17,
-    C_MAX_TRIANGLE = 18,        /* a minimum: the lowest triangle with C_MAX_PARTNERS partners */
-    C_MAX_TIES = 19,            /* the triangles that attain the maximum (tally() counts what it finds the first of) */
-    C_TESTED = 20,              /* a timed call: the record pairs the pairs kernel looked at */
-    C_WORDS = 21
+    C_CANDIDATES = G_WORDS,
+    C_CROSSINGS,
+    C_LOWEST,                   /* a minimum: the lowest crossing pair, packed */
+    C_CURSOR,                   /* the list pass: pairs appended */
+    C_CROSSING_TRIANGLES,
+    C_MAX_PARTNERS,
+    C_MAX_TRIANGLE,             /* a minimum: the lowest triangle with C_MAX_PARTNERS partners */
+    C_MAX_TIES,                 /* the triangles that attain the maximum (tally() counts what it finds the first of) */
+    C_TESTED,                   /* a timed call: the record pairs the pairs kernel looked at */
+    C_WORDS
 };
 
-const uint64_t MIN_RECORD_BUDGET = uint64_t(1) << 20;
-const uint32_t RECORDS_PER_TRIANGLE = 8;        /* the budget: what the records may cost per triangle that takes part */
-const uint32_t CELL_CAP = 1u << 21;             /* cells per axis: 3 * 21 bits pack a cell */
-const uint32_t EXTENT_BITS = 20;                /* a triangle's extent as a fraction of the box's, in the classify sum */
+const GridNames NAMES = {"mesh self-intersections", "records", "kernel.intersect.extent", "kernel.intersect.classify",
+                         "kernel.intersect.count", "kernel.intersect.scan", "kernel.intersect.emit", "kernel.intersect.sort",
+                         "intersect.records", "intersect.cellsize"};
+
 const uint32_t OWN_STEPS = 32;                  /* the later records a lane meets alone, before the wave shares the rest */
 const double FILTER = 3.552713678800501e-15;    /* 2^-48 (step 3) */
 
-/* floats to integers of the same order (and back): what atomicMin / atomicMax take */
-__host__ __device__ inline uint32_t orderedBits(uint32_t bits) { return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u); }
-inline float fromOrdered(uint32_t o)
-{
-    const uint32_t bits = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-    float f;
-    std::memcpy(&f, &bits, sizeof(f));
-    return f;
-}
-
-/* The sparse grid: cell (x, y, z) has the key z << (bx + by) | y << bx | x, the axes as wide as their cell counts need.
- * Packed for the owning-cell rule it is z << 42 | y << 21 | x. */
-struct Grid
-{
-    double origin[3];           /* the box's lower corner */
-    double h;
-    uint32_t n[3];              /* cells per axis, each >= 1 and <= CELL_CAP */
-    uint32_t shiftY, shiftZ;
-
-    /* monotone in x: one subtraction, one division, floor, clamp */
-    __device__ __forceinline__ uint32_t cell(int axis, double x) const
-    {
-        const double c = floor((x - origin[axis]) / h);
-        return (uint32_t) fmin(fmax(c, 0.0), (double) (n[axis] - 1));
-    }
-    __device__ __forceinline__ uint64_t key(uint32_t x, uint32_t y, uint32_t z) const
-    {
-        return (uint64_t) z << shiftZ | (uint64_t) y << shiftY | x;
-    }
-    __device__ __forceinline__ uint64_t packedOf(uint64_t key) const
-    {
-        const uint64_t x = key & ((uint64_t(1) << shiftY) - 1);
-        const uint64_t y = (key >> shiftY) & ((uint64_t(1) << (shiftZ - shiftY)) - 1);
-        return (key >> shiftZ) << 42 | y << 21 | x;
-    }
-};
-
-__device__ __forceinline__ uint64_t pack(uint32_t x, uint32_t y, uint32_t z) { return (uint64_t) z << 42 | (uint64_t) y << 21 | x; }
-
-/* per axis the larger of two packed cells */
+/* per axis the larger of two packed cells (packCell(): z << 42 | y << 21 | x) */
 __device__ __forceinline__ uint64_t largerCell(uint64_t p, uint64_t q)
 {
     const uint64_t M = (uint64_t(1) << 21) - 1;
@@ -213,142 +159,6 @@ __device__ __forceinline__ bool crosses(Corners &S, Corners &T)
 }
 
 /* ---------------------------------------------------------------- kernels */
-
-/* A workgroup loops over the 3 V coordinates and sends once: the count of those that are not finite and, of the finite ones,
- * the box. */
-__global__ __launch_bounds__(256) void extentKernel(const float *vertices, uint64_t numCoordinates, Counter *counters)
-{
-    __shared__ GroupCounts<1, 6> totals;
-    totals.clear();
-    const int at[7] = {C_BAD_VERTICES, C_BOX_MAX, C_BOX_MAX + 1, C_BOX_MAX + 2, C_BOX_MIN, C_BOX_MIN + 1, C_BOX_MIN + 2};
-    const uint64_t first = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x, stride = (uint64_t) gridDim.x * blockDim.x;
-    uint32_t bad = 0;
-    /* the smallest is kept as the largest of the complements, which GroupCounts' maxima hold; 0 = none seen (the ordered bits
-     * of a finite float are neither 0 nor all ones) */
-    uint32_t most[3] = {0, 0, 0}, least[3] = {0, 0, 0};
-    for (uint64_t i = first; i < numCoordinates; i += stride)
-    {
-        const float x = vertices[i];
-        const bool ok = isfinite(x);
-        bad += ok ? 0u : 1u;
-        const uint32_t o = orderedBits(__float_as_uint(x)), axis = (uint32_t) (i % 3);
-#pragma unroll
-        for (uint32_t k = 0; k < 3; k++)
-            if (ok && axis == k)
-            {
-                most[k] = max(most[k], o);
-                least[k] = max(least[k], ~o);
-            }
-    }
-    totals.add(0, bad);
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-    {
-        totals.raise(k, most[k]);
-        totals.raise(3 + k, least[k]);
-    }
-    totals.flush(counters, at);
-}
-
-/* Step 1, and the sum of the extents (the longest side of a live triangle's box, as a fraction of `scale`'s unit) that sizes
- * the first cell.  A workgroup loops and sends once; the extents go through one 64-bit atomic per wave. */
-__global__ __launch_bounds__(256) void classifyKernel(const float *vertices, uint64_t numVertices, const uint32_t *tri, uint64_t numTriangles,
-                                                      double scale, Counter *counters)
-{
-    __shared__ GroupCounts<3> totals;
-    totals.clear();
-    const int at[3] = {C_OUT_OF_RANGE, C_DEGENERATE, C_LIVE};
-    uint32_t outOfRange = 0, degenerate = 0, live = 0;
-    long long extents = 0;
-    for (uint64_t t = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; t < numTriangles; t += (uint64_t) gridDim.x * blockDim.x)
-    {
-        const uint64_t i[3] = {tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]};
-        const TriangleDefect d = defectOf(i, numVertices);
-        outOfRange += d.outOfRange ? 1u : 0u;
-        degenerate += d.degenerate ? 1u : 0u;
-        if (!d.none())
-            continue;
-        live++;
-        const Box B = boxOf(cornersOf(vertices, i[0], i[1], i[2]));
-        double extent = 0.0;
-#pragma unroll
-        for (int x = 0; x < 3; x++)
-            extent = fmax(extent, (double) B.hi[x] - (double) B.lo[x]);
-        extents += (long long) fmin(extent * scale, (double) (1u << (EXTENT_BITS + 1)));
-    }
-    totals.add(0, outOfRange);
-    totals.add(1, degenerate);
-    totals.add(2, live);
-    const long long ofWave = waveSum64(extents);
-    if (laneId() == 0 && ofWave != 0)
-        atomicAdd(&counters[C_EXTENT], (Counter) ofWave);
-    totals.flush(counters, at);
-}
-
-/* the cells of triangle t per axis, first and last; false for a triangle that takes no part */
-__device__ __forceinline__ bool cellsOf(const Grid &G, const float *vertices, uint64_t numVertices, const uint32_t *tri, uint64_t t,
-                                        uint32_t first[3], uint32_t last[3])
-{
-    const uint64_t i[3] = {tri[3 * t], tri[3 * t + 1], tri[3 * t + 2]};
-    if (!defectOf(i, numVertices).none())
-        return false;
-    const Box B = boxOf(cornersOf(vertices, i[0], i[1], i[2]));
-#pragma unroll
-    for (int x = 0; x < 3; x++)
-    {
-        first[x] = G.cell(x, (double) B.lo[x]);
-        last[x] = G.cell(x, (double) B.hi[x]);
-    }
-    return true;
-}
-
-/* How many cells every triangle goes into: at most CELL_CAP^3 = 2^63, kept up to 2^32 (which is beyond every budget); and the
- * cell of its lower corner, packed.  The total goes through one 64-bit atomic per wave.  Every lane stays to the end. */
-__global__ __launch_bounds__(256) void countKernel(Grid G, const float *vertices, uint64_t numVertices, const uint32_t *tri,
-                                                   uint64_t numTriangles, uint32_t *counts, uint64_t *lowerCell, Counter *counters)
-{
-    long long records = 0;
-    for (uint64_t base = (uint64_t) blockIdx.x * blockDim.x; base < numTriangles; base += (uint64_t) gridDim.x * blockDim.x)
-    {
-        const uint64_t t = base + threadIdx.x;
-        if (t >= numTriangles)
-            continue;
-        uint32_t first[3] = {0, 0, 0}, last[3] = {0, 0, 0};
-        uint64_t cells = 0;
-        if (cellsOf(G, vertices, numVertices, tri, t, first, last))
-            cells = (uint64_t) (last[0] - first[0] + 1) * (last[1] - first[1] + 1) * (last[2] - first[2] + 1);
-        cells = min(cells, (uint64_t) 1 << 32);
-        counts[t] = (uint32_t) min(cells, (uint64_t) 0xFFFFFFFFu);
-        lowerCell[t] = pack(first[0], first[1], first[2]);
-        records += (long long) cells;
-    }
-    const long long ofWave = waveSum64(records);
-    if (laneId() == 0 && ofWave != 0)
-        atomicAdd(&counters[C_RECORDS], (Counter) ofWave);
-}
-
-/* The records of triangle t, from starts[t] on: counts that passed the budget, so starts[t] + count <= numRecords.  The bound
- * is checked all the same: no store depends on the two kernels agreeing. */
-__global__ __launch_bounds__(256) void emitKernel(Grid G, const float *vertices, uint64_t numVertices, const uint32_t *tri,
-                                                  uint64_t numTriangles, const uint32_t *starts, uint64_t numRecords, uint64_t *keys,
-                                                  uint32_t *vals)
-{
-    const uint64_t t = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= numTriangles)
-        return;
-    uint32_t first[3], last[3];
-    if (!cellsOf(G, vertices, numVertices, tri, t, first, last))
-        return;
-    uint64_t at = starts[t];
-    for (uint32_t z = first[2]; z <= last[2]; z++)
-        for (uint32_t y = first[1]; y <= last[1]; y++)
-            for (uint32_t x = first[0]; x <= last[0]; x++, at++)
-                if (at < numRecords)
-                {
-                    keys[at] = G.key(x, y, z);
-                    vals[at] = (uint32_t) t;
-                }
-}
 
 /* what the pairs kernel reads and writes */
 struct PairsArgs
@@ -543,25 +353,6 @@ __global__ __launch_bounds__(256) void mostKernel(const uint32_t *partners, uint
     tally(hit, &counters[C_MAX_TIES], t, &counters[C_MAX_TRIANGLE]);
 }
 
-/* the grid of cell size h over [lo, hi] per axis, or false if an axis would need more than CELL_CAP cells */
-bool layGrid(const double lo[3], const double hi[3], double h, Grid *G)
-{
-    G->h = h;
-    uint32_t bits[3];
-    for (int x = 0; x < 3; x++)
-    {
-        G->origin[x] = lo[x];
-        const double cells = std::floor((hi[x] - lo[x]) / h) + 1.0;
-        if (!(cells <= (double) CELL_CAP))
-            return false;
-        G->n[x] = (uint32_t) std::max(cells, 1.0);
-        bits[x] = bitLength(G->n[x] - 1);
-    }
-    G->shiftY = bits[0];
-    G->shiftZ = bits[0] + bits[1];
-    return true;
-}
-
 } // namespace
 
 MLSGPU_API int mlsgpu_hip_mesh_self_intersections(mlsgpu_ctx *ctx, const float *dVertices, uint64_t numVertices,
@@ -581,52 +372,16 @@ MLSGPU_API int mlsgpu_hip_mesh_self_intersections(mlsgpu_ctx *ctx, const float *
 
     HIP_CHECK(hipSetDevice(ctx->device));
     const dim3 B(256);
-    DeviceArray<Counter> counters;
-    Counter h[C_WORDS];
-    std::memset(h, 0, sizeof(h));
-    PROPAGATE(counters.alloc(C_WORDS));
-    HIP_CHECK(hipMemsetAsync(counters.get(), 0, C_WORDS * sizeof(Counter), ctx->stream));
-    HIP_CHECK(hipMemsetAsync(&counters.get()[C_LOWEST], 0xFF, sizeof(Counter), ctx->stream));           /* minima */
-    HIP_CHECK(hipMemsetAsync(&counters.get()[C_MAX_TRIANGLE], 0xFF, sizeof(Counter), ctx->stream));
-    const auto readBack = [&]() -> int {
-        HIP_CHECK(hipMemcpyAsync(h, counters.get(), sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        return MLSGPU_OK;
-    };
-
-    if (nv > 0)
-    {
-        LAUNCH(ctx, "kernel.intersect.extent", extentKernel, dim3(std::min(divUp(3 * nv, 256), LOOP_BLOCKS)), B, dVertices, 3 * nv,
-               counters.get());
-        PROPAGATE(readBack());
-    }
-    if (h[C_BAD_VERTICES] != 0)
-        return setError(MLSGPU_ERR_INVALID, "mesh self-intersections: %llu vertex coordinates are not finite", h[C_BAD_VERTICES]);
-
-    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, side = 0.0;
-    if (nv > 0)
-        for (int x = 0; x < 3; x++)
-        {
-            lo[x] = (double) fromOrdered(~(uint32_t) h[C_BOX_MIN + x]);
-            hi[x] = (double) fromOrdered((uint32_t) h[C_BOX_MAX + x]);
-            side = std::max(side, hi[x] - lo[x]);
-        }
-
-    /* a triangle's extent is summed in units of 2^-EXTENT_BITS of the power of two above the box's longest side */
-    uint64_t bitsOfSide;
-    std::memcpy(&bitsOfSide, &side, sizeof(side));
-    const int eSide = side > 0.0 ? exponentOfDoubleBits(bitsOfSide) + 1 : 0;
-    if (nv > 0 && nt > 0)
-    {
-        LAUNCH(ctx, "kernel.intersect.classify", classifyKernel, dim3(std::min(divUp(nt, 256), LOOP_BLOCKS)), B, dVertices, nv, dTriangles, nt,
-               powerOfTwo((int) EXTENT_BITS - eSide), counters.get());
-        PROPAGATE(readBack());
-        out->outOfRangeTriangles = h[C_OUT_OF_RANGE];
-        out->degenerateTriangles = h[C_DEGENERATE];
-    }
-    else
-        out->outOfRangeTriangles = nt;          /* every index is >= 0 vertices */
-    const uint64_t live = h[C_LIVE];
+    CounterBlock counters;
+    PROPAGATE(counters.start(ctx, C_WORDS, {C_LOWEST, C_MAX_TRIANGLE}));
+    const std::vector<Counter> &h = counters.h;
+    TriangleGrid grid = {ctx, NAMES, counters, dVertices, nv, dTriangles, nt, 0.0};
+    PROPAGATE(grid.measure(nullptr, 0, G_BAD_VERTICES));        /* no points: nothing is sent for them */
+    if (grid.badVertices != 0)
+        return setError(MLSGPU_ERR_INVALID, "mesh self-intersections: %llu vertex coordinates are not finite",
+                        (unsigned long long) grid.badVertices);
+    out->outOfRangeTriangles = grid.outOfRange;
+    out->degenerateTriangles = grid.degenerate;
     if (nt == 0)
         return MLSGPU_OK;
 
@@ -637,8 +392,8 @@ MLSGPU_API int mlsgpu_hip_mesh_self_intersections(mlsgpu_ctx *ctx, const float *
         dPartners = ownPartners.get();
     }
     HIP_CHECK(hipMemsetAsync(dPartners, 0, nt * sizeof(uint32_t), ctx->stream));
-    double scratch = (double) (counters.bytes(C_WORDS) + (ownPartners.get() != nullptr ? ownPartners.bytes(nt) : 0));
-    if (live < 2)
+    double scratch = (double) (counters.bytes() + (ownPartners.get() != nullptr ? ownPartners.bytes(nt) : 0));
+    if (grid.live < 2)
     {
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         if (ctx->timing)
@@ -646,62 +401,19 @@ MLSGPU_API int mlsgpu_hip_mesh_self_intersections(mlsgpu_ctx *ctx, const float *
         return MLSGPU_OK;
     }
 
-    SortScratch records, found;
-    DeviceArray<uint32_t> counts, starts, tileSums;
+    SortScratch found;
     DeviceArray<uint64_t> lowerCell;
-    PROPAGATE(counts.alloc(nt));
-    PROPAGATE(starts.alloc(nt));
     PROPAGATE(lowerCell.alloc(nt));
-    PROPAGATE(tileSums.alloc((uint64_t) scanTiles(nt) + 1));
-    /* the first cell: the mean extent of a triangle's box (the box's longest side, or 1, where every triangle is a point);
-     * then doubled until every axis has at most CELL_CAP cells and the records fit their budget.  One cell holds every live
-     * triangle once: the loop ends. */
-    const uint64_t budget = std::max(MIN_RECORD_BUDGET, (uint64_t) RECORDS_PER_TRIANGLE * live);
-    double cellSize = (double) h[C_EXTENT] / (double) live * powerOfTwo(eSide - (int) EXTENT_BITS);
-    if (!(cellSize > 0.0))
-        cellSize = side > 0.0 ? side : 1.0;
-    Grid G;
-    uint64_t numRecords = 0;
-    for (;; cellSize *= 2.0)
-    {
-        if (!std::isfinite(cellSize))
-            return setError(MLSGPU_ERR_LENGTH, "mesh self-intersections: no cell size brings the grid's records under %llu",
-                            (unsigned long long) budget);
-        if (!layGrid(lo, hi, cellSize, &G))
-            continue;
-        HIP_CHECK(hipMemsetAsync(&counters.get()[C_RECORDS], 0, sizeof(Counter), ctx->stream));
-        LAUNCH(ctx, "kernel.intersect.count", countKernel, dim3(std::min(divUp(nt, 256), LOOP_BLOCKS)), B, G, dVertices, nv, dTriangles, nt,
-               counts.get(), lowerCell.get(), counters.get());
-        PROPAGATE(readBack());
-        numRecords = h[C_RECORDS];
-        if (numRecords <= budget)
-            break;
-    }
-    REQUIRE(numRecords >= live && numRecords < (uint64_t(1) << 32), MLSGPU_ERR_LENGTH);
-    PROPAGATE(records.alloc(numRecords));
-    scratch += (double) (records.bytes() + 2 * counts.bytes(nt) + lowerCell.bytes(nt) + tileSums.bytes((uint64_t) scanTiles(nt) + 1));
-    if (ctx->timing)
-    {
-        ctx->addValue("intersect.records", (double) numRecords);
-        ctx->addValue("intersect.cellsize", cellSize);
-    }
-
-    PROPAGATE((exclusiveScan<uint32_t>(ctx, "kernel.intersect.scan", ArrayIn<uint32_t>{counts.get()}, ArrayOut<uint32_t>{starts.get()}, nt,
-                                       0u, tileSums.get(), (uint32_t *) nullptr)));
-    LAUNCH(ctx, "kernel.intersect.emit", emitKernel, dim3(divUp(nt, 256)), B, G, dVertices, nv, dTriangles, nt,
-           (const uint32_t *) starts.get(), numRecords, records.keys(), records.vals());
-    /* (both sorts under one name: a launch site of the sort keeps one stat id per translation unit) */
-    const uint32_t keyBits = G.shiftZ + bitLength(G.n[2] - 1);
-    SortResult<uint64_t> byCell = {nullptr, nullptr};
-    PROPAGATE(radixSort<uint64_t>(ctx, "kernel.intersect.sort", records.keysA, records.valsA, records.keysB, records.valsB, numRecords,
-                                  keyBits, false, records.hist, nullptr, &byCell));
-    PairsArgs args = {G, dVertices, nv, dTriangles, nt, lowerCell.get(), byCell.keys, byCell.vals, (uint32_t) numRecords, dPartners,
-                      nullptr, 0, counters.get(), ctx->timing != 0};
+    PROPAGATE(grid.build(grid.firstCell(), lowerCell.get()));
+    scratch += (double) (grid.bytes() + lowerCell.bytes(nt));
+    const uint64_t numRecords = grid.numRecords;
+    PairsArgs args = {grid.G, dVertices, nv, dTriangles, nt, lowerCell.get(), grid.byCell.keys, grid.byCell.vals, (uint32_t) numRecords,
+                      dPartners, nullptr, 0, counters.get(), ctx->timing != 0};
     LAUNCH(ctx, "kernel.intersect.pairs", (pairsKernel<false>), dim3(divUp(numRecords, 256)), B, args);
     LAUNCH(ctx, "kernel.intersect.report", reportKernel, dim3(std::min(divUp(nt, 256), LOOP_BLOCKS)), B, (const uint32_t *) dPartners, nt,
            counters.get());
     LAUNCH(ctx, "kernel.intersect.report", mostKernel, dim3(divUp(nt, 256)), B, (const uint32_t *) dPartners, nt, counters.get());
-    PROPAGATE(readBack());
+    PROPAGATE(counters.readBack(ctx));
     out->candidatePairs = h[C_CANDIDATES];
     out->crossingPairs = h[C_CROSSINGS];
     out->crossingTriangles = h[C_CROSSING_TRIANGLES];
@@ -733,11 +445,12 @@ MLSGPU_API int mlsgpu_hip_mesh_self_intersections(mlsgpu_ctx *ctx, const float *
         args.list = found.keys();
         args.listCapacity = numPairs;
         LAUNCH(ctx, "kernel.intersect.list", (pairsKernel<true>), dim3(divUp(numRecords, 256)), B, args);
+        /* (both sorts under one name: a launch site of the sort keeps one stat id per translation unit) */
         SortResult<uint64_t> sorted = {nullptr, nullptr};
         PROPAGATE(radixSort<uint64_t>(ctx, "kernel.intersect.sort", found.keysA, found.valsA, found.keysB, found.valsB, numPairs,
                                       32 + bitLength(nt - 1), true, found.hist, nullptr, &sorted));
         LAUNCH(ctx, "kernel.intersect.list", unpackKernel, dim3(divUp(numPairs, 256)), B, (const uint64_t *) sorted.keys, numPairs, dPairs);
-        PROPAGATE(readBack());
+        PROPAGATE(counters.readBack(ctx));
         if (h[C_CURSOR] != numPairs)
             return setError(MLSGPU_ERR_HIP, "mesh self-intersections: the list pass found %llu pairs, the count %llu", h[C_CURSOR],
                             (unsigned long long) numPairs);

@@ -1,5 +1,6 @@
 /*
- * What the stages that work on a finished mesh in HBM share (topology.hip, simplify.hip, normals.hip, smooth.hip, fill.hip):
+ * What the stages that work on a finished mesh in HBM share (topology.hip, simplify.hip, normals.hip, smooth.hip, fill.hip,
+ * repair.hip; flip.hip, collapse.hip and split.hip through meshedges.hpp; deviation.hip and intersect.hip through meshgrid.hpp):
  * wave-level counting, the records of a triangle's directed sides, the scratch of their sort, and the fixed point that makes
  * a sum independent of the schedule.  Three facts the stages rely on are written here once.
  *
@@ -23,6 +24,7 @@
 #define MLSGPU_AMD_MESHPOST_HPP
 
 #include "common.hpp"
+#include "meshgridplan.hpp"      /* bitLength, exponentOfDoubleBits, powerOfTwo: host arithmetic a plain compiler takes too */
 #include "primitives.hpp"
 
 namespace mlsgpu
@@ -32,17 +34,6 @@ typedef unsigned long long Counter;     /* a 64-bit word of a stage's counter bl
 
 /* the most workgroups of a kernel that loops over its elements and sends its counts once (above) */
 const uint32_t LOOP_BLOCKS = 1024;
-
-static inline uint32_t bitLength(uint64_t v)
-{
-    uint32_t b = 0;
-    while (v != 0)
-    {
-        b++;
-        v >>= 1;
-    }
-    return b;
-}
 
 /* ---------------------------------------------------------------- fixed point */
 
@@ -60,27 +51,6 @@ __host__ __device__ inline int exponentOfBits(uint32_t bits)
     while ((bits >> (high + 1)) != 0)
         high++;
     return high - 149;
-}
-
-/* the same from the bits of a double M > 0 */
-__host__ __device__ inline int exponentOfDoubleBits(uint64_t bits)
-{
-    const int field = (int) (bits >> 52);
-    if (field != 0)
-        return field - 1023;
-    int top = 0;
-    for (uint64_t m = bits; m > 1; m >>= 1)
-        top++;
-    return top - 1074;
-}
-
-/* 2^k as a double, for a k that gives a normal one */
-__host__ __device__ inline double powerOfTwo(int k)
-{
-    const long long bits = (long long) (1023 + k) << 52;
-    double d;
-    __builtin_memcpy(&d, &bits, sizeof(d));
-    return d;
 }
 
 #ifdef __HIPCC__
